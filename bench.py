@@ -3,7 +3,7 @@
 bench.py -- `zot kmerize` K=25 on synthetic 150 bp reads, the metric of BASELINE.json, plus the other single-GPU
 configurations as `extra` blocks of the same JSON line.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Headline.  A step is one whole kmerize of the batch: base stream resident in HBM -> sorted distinct k-mers of both
@@ -21,6 +21,10 @@ beside it (`others`); `peak` is the 8 TB/s of the spec,
 verified outside the timed region: order-free checksums of the table against the same sums taken straight from the base
 stream by an independent encoder, and strict ascent of the k-mers (`verified_checksums`, `verified_ascending`).  `cpu_baseline`: the C oracle on one core on a prefix of the same
 reads, and the pure-Python restatement of the reference path on BASELINE config 1.
+
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs: a seeded sample of the sorted table, the whole
+histogram, the stats and the table's checksums) as float64 .npy files; the inputs are fixed by the seed, so two builds compare
+output for output.
 
 `extra` (N = 1): config 3 (`zot dist` on two 100 M-k-mer sets), one GPU's share of config 4 (merge of 8 x 50 M-k-mer
 sets), one GPU's share of config 5 (K = 31, 37.5 M reads), config 2 again with the base stream starting in pinned
@@ -601,6 +605,36 @@ def extra_dist_multi(ctx, ex, steps, scale, world, rank):
             "verified_by": "(a, b, c) equals the single-GPU zk_split of the whole sets"}
 
 
+DUMP_BLOCKS, DUMP_BLOCK = 32, 1 << 16      # the sampled table: 32 runs of 64 K entries (2 M k-mers + counts as float64, 32 MB)
+
+
+def dump_outputs(d, suffix, k, c, st, h, checksum, seed, K):
+    """What the timed step handed its caller, as float64 .npy files under d: the whole histogram, the kmerize stats and the
+    order-free checksums of the whole table, and a fixed, seeded sample of the sorted table itself (DUMP_BLOCKS contiguous
+    runs of DUMP_BLOCK entries at seeded places; all of it when it is smaller), so that two builds can be compared entry for entry."""
+    assert 2 * K <= 53, "k-mers of K > 26 are not exact in float64"
+    os.makedirs(d, exist_ok=True)
+    n = k.n
+    if n <= DUMP_BLOCKS * DUMP_BLOCK:
+        starts, blk = np.zeros(1, np.int64), n
+    else:
+        rng = np.random.default_rng(seed)
+        starts = np.sort(rng.choice(n - DUMP_BLOCK + 1, size=DUMP_BLOCKS, replace=False)).astype(np.int64)
+        blk = DUMP_BLOCK
+    ks = np.concatenate([k.view(blk, int(s)).to_host() for s in starts]) if blk else np.empty(0, np.uint64)
+    cs = np.concatenate([c.view(blk, int(s)).to_host() for s in starts]) if blk else np.empty(0, np.uint32)
+    hv = np.array(sorted(h), dtype=np.float64)
+    # the u64 checksums as exact 32-bit halves (hi, lo)
+    sums = np.array([[v >> 32, v & 0xFFFFFFFF] for v in checksum], dtype=np.float64)
+    arrays = {"kmers_sample": ks.astype(np.float64), "counts_sample": cs.astype(np.float64),
+              "sample_starts": starts.astype(np.float64), "hist_values": hv,
+              "hist_freqs": np.array([h[v] for v in sorted(h)], dtype=np.float64),
+              "stats": np.array([st.n_windows, st.n_instances, st.n_unique, st.n_canonical, *st.acgt], dtype=np.float64),
+              "checksums": sums}
+    for name, arr in arrays.items():
+        np.save(os.path.join(d, name + suffix + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -614,7 +648,11 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="headline only")
     ap.add_argument("--extras-scale", type=float, default=1.0, help="shrink the extra workloads (tests)")
     ap.add_argument("--only-extra", default="", help="run just this extra block (development): skips the headline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; per rank as <name>_rank<r>.npy when N > 1)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -752,6 +790,8 @@ def main():
         ascending = bool(ctx.first_descent(k) == k.n)
         if par is not None:
             ascending = bool(par.comm.all_reduce([0 if ascending else 1])[0] == 0)
+    if a.dump_outputs:          # before the extras, which reuse the output buffers
+        dump_outputs(a.dump_outputs, "_rank%d" % rank if world > 1 else "", k, c, st, h, ctx.checksum_counts(k, c), seed + rank, K)
     peak_measured = copy_peak(ctx) if rank == 0 and not a.no_verify else None          # (not in profiled runs)
 
     extras = {}
