@@ -122,6 +122,7 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_PASS_PACKED 12  /* radix pass of the key kernel over a collapsed list of (k-mer << s | count) words (16 B per word) */
 #define ZK_PROF_SAMPLE 13       /* the look before the sort: the few set-aside blocks, sorted and counted (tiny launches) */
 #define ZK_PROF_TILE_SORT 14    /* the lower bits of a sort finished tile by tile in LDS (tilesort.hip: 16 B per key, 24 per pair, once) */
+#define ZK_PROF_CAPTURE_HITS 15 /* zk_capture_hits: the window lookup, one wave per read (capture.hip) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -151,6 +152,41 @@ int zk_subsample(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, uint64_t seed
  * stream.  d_out holds n_bytes. */
 int zk_capture_filter(zk_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, int K, const uint64_t* d_baits, uint64_t n_baits,
                       uint8_t* d_out, uint64_t* n_reads, uint64_t* n_kept);
+
+/* ---- read capture against a bait panel, `zot capture` (commands/capture.py) ---------------------------------------
+ * A bait table: every K-mer of both strands of every bait sequence -> the ascending indices of the sequences that hold it
+ * (capture.py:85-95 with basics.kmersList(K, seq, True), basics.py:303-347).  Built on the device from a base stream of the
+ * bait sequences, each followed by one '\n' (record i = the piece before the (i+1)-th '\n'); 1 <= K <= 32.  Held as sorted
+ * distinct keys, CSR offsets into u32 record ids, and a directory over the top key bits (about one key per bucket), so that a
+ * lookup that misses costs one directory line.  The memory is the table's own until zk_bait_table_free. */
+typedef struct zk_bait_table zk_bait_table;
+int zk_bait_table_build(zk_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, int K, zk_bait_table** table);
+int zk_bait_table_info(const zk_bait_table* table, uint64_t* n_keys, uint64_t* n_ids, uint64_t* n_records);
+void zk_bait_table_free(zk_bait_table* table);
+
+/* the positions of the '\n' bytes of d_text[0, n), ascending, into d_out (cap entries; ZK_ENOSPC with *n_lines = the count if
+ * they do not fit).  The line structure file.readFastq walks (file.py:38-52): record r of a text cut at a record boundary is
+ * lines 4r .. 4r+3, line i = [d_out[i-1] + 1, d_out[i]). */
+int zk_line_ends(zk_ctx* ctx, const uint8_t* d_text, uint64_t n, uint64_t* d_out, uint64_t cap, uint64_t* n_lines);
+
+/* The reads of capture.py:97-116: read r of FASTQ text (d_lines from zk_line_ends, at least 4 * n_reads of them) hits every
+ * bait record whose table holds one of the forward read_K-mers of its sequence line (reads.reads(..., fwdOnly=True), whose K is
+ * 25 whatever `-k` says: reads.py:38, capture.py:103; windows restart after any byte outside AaCcGgTtUu).  A k-mer matches a
+ * key of equal value, whatever the two K are.  Paired reads (capture.py -p): d_text2 / d_lines2 are mate 2, the hits are the
+ * union over both mates.  veto (may be NULL): a read with any window in it is not captured (the -U of pulldown.py).
+ * Output: the distinct (bait, read) pairs as words bait << 32 | read, ascending (each bait's reads contiguous and in input
+ * order), in d_pairs.  cap must hold the pairs BEFORE deduplication (at most one per read chunk of 64 windows and bait);
+ * ZK_ENOSPC with *n_pairs = that count if it does not. */
+int zk_capture_hits(zk_ctx* ctx, const zk_bait_table* baits, const zk_bait_table* veto, int read_K, const uint8_t* d_text1,
+                    const uint64_t* d_lines1, const uint8_t* d_text2, const uint64_t* d_lines2, uint64_t n_reads, uint64_t* d_pairs,
+                    uint64_t cap, uint64_t* n_pairs);
+
+/* ReadCache.add / flush (capture.py:26-69) for one batch: the records of d_pairs (from zk_capture_hits) as their four lines,
+ * each stripped as str.strip() does (file.py:38-52) and followed by '\n', bait by bait, into d_out (cap bytes; ZK_ENOSPC with
+ * *n_bytes = the size needed if they do not fit).  spans (host, 2 * (n_baits + 1) words): spans[b] = the first pair of bait b,
+ * spans[n_baits + 1 + b] = its first byte in d_out (b = n_baits: the ends).  Paired input: once per mate, with that mate's text. */
+int zk_capture_gather(zk_ctx* ctx, const uint64_t* d_pairs, uint64_t n_pairs, uint32_t n_baits, const uint8_t* d_text,
+                      const uint64_t* d_lines, uint64_t n_lines, uint8_t* d_out, uint64_t cap, uint64_t* spans, uint64_t* n_bytes);
 
 /* basics.can (library/basics.py:231-250; used by `zot vars`): per k-mer, whichever of x and rc(x) has the smaller
  * murmer(., 17) -- x on a tie.  Element-wise, asynchronous; d_out may equal d_kmers. */

@@ -1,0 +1,545 @@
+// capture.hip -- `zot capture` (zotmer/commands/capture.py): reads binned by the bait sequences they touch.
+//
+// Three steps, each an entry of include/zotk.h:
+//   * zk_bait_table_build: every K-mer of both strands of each bait record -> the ascending record ids that contain it
+//     (capture.py:85-95), as sorted distinct keys + CSR offsets into u32 ids + a bucket directory over the top key bits;
+//   * zk_capture_hits: one wave per read slides the read windows over its sequence line(s) in the raw FASTQ text, looks
+//     every window up (directory, then a search inside one bucket of ~1 key) and emits the distinct (bait, read) pairs,
+//     sorted and deduplicated (capture.py:97-116);
+//   * zk_capture_gather: the four stripped lines of every captured record, bait by bait, into one buffer (ReadCache,
+//     capture.py:26-69, file.readFastq, file.py:38-52).
+// Records are located through the positions of the text's '\n' bytes (zk_line_ends): record r is lines 4r .. 4r+3.
+#include "internal.hpp"
+
+// the table behind the opaque zk_bait_table of the C-ABI (device memory of its own, outlives the calls)
+struct zk_bait_table {
+    zk_ctx* ctx = nullptr;
+    u64* keys = nullptr;       // sorted distinct k-mers [n_keys]
+    u32* offs = nullptr;       // [n_keys + 1]: ids[offs[i], offs[i+1]) are the records of keys[i], ascending
+    u32* ids = nullptr;        // [n_ids]
+    u32* dir = nullptr;        // [2^bits + 1]: keys whose top `bits` of `kbits` equal b are keys[dir[b], dir[b+1])
+    uint64_t n_keys = 0, n_ids = 0, n_records = 0;
+    int K = 0, kbits = 0, bits = 0;
+};
+
+namespace zk {
+
+// ---------------------------------------------------------------------------------------
+// Order-preserving compaction: a count pass over tiles of 4096 items, an inclusive scan of the tile counts
+// (scan64_inclusive), a write pass.  Every workgroup owns one tile; nothing waits on another workgroup.
+// P::flag(i) says whether item i is kept, P::store(pos, i) writes it at its rank.
+// ---------------------------------------------------------------------------------------
+constexpr int CP_BLOCK = 256, CP_ITEMS = 16, CP_TILE = CP_BLOCK * CP_ITEMS;
+
+template <class P>
+__global__ __launch_bounds__(CP_BLOCK) void compact_count_kernel(P p, u64 n, u64* __restrict__ tile_counts) {
+    __shared__ u32 part[CP_BLOCK / 64];
+    const u64 base = (u64)blockIdx.x * CP_TILE + (u64)threadIdx.x * CP_ITEMS;
+    u32 k = 0;
+    for (int i = 0; i < CP_ITEMS; i++) k += (base + i < n && p.flag(base + i)) ? 1u : 0u;
+    k = wave_sum_u32(k);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = k;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 t = 0;
+        for (int w = 0; w < CP_BLOCK / 64; w++) t += part[w];
+        tile_counts[blockIdx.x] = t;
+    }
+}
+
+template <class P>
+__global__ __launch_bounds__(CP_BLOCK) void compact_write_kernel(P p, u64 n, const u64* __restrict__ tile_incl) {
+    __shared__ u32 part[CP_BLOCK / 64];
+    const u64 base = (u64)blockIdx.x * CP_TILE + (u64)threadIdx.x * CP_ITEMS;
+    u32 keep = 0;
+    for (int i = 0; i < CP_ITEMS; i++)
+        if (base + i < n && p.flag(base + i)) keep |= 1u << i;
+    const u32 k = (u32)__popc(keep);
+    const u32 incl = wave_incl_scan_u32(k);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 63) part[wave] = incl;
+    __syncthreads();
+    u64 pos = blockIdx.x ? tile_incl[blockIdx.x - 1] : 0;
+    for (int w = 0; w < wave; w++) pos += part[w];
+    pos += incl - k;
+    for (int i = 0; i < CP_ITEMS; i++)
+        if ((keep >> i) & 1u) p.store(pos++, base + i);
+}
+
+// the count pass: *total = kept items; tile_incl (arena, valid until the next arena_reset) feeds compact_write
+template <class P>
+static int compact_count(zk_ctx* c, const P& p, uint64_t n, u64** tile_incl, uint64_t* total) {
+    *total = 0;
+    *tile_incl = nullptr;
+    if (n == 0) return ZK_OK;
+    const u64 tiles = div_up(n, CP_TILE);
+    u64* cnt;
+    ZK_TRY(arena_alloc(c, 8 * tiles, (void**)&cnt));
+    hipLaunchKernelGGL((compact_count_kernel<P>), dim3((u32)tiles), dim3(CP_BLOCK), 0, c->stream, p, (u64)n, cnt);
+    ZK_HIP(c, hipGetLastError());
+    ZK_TRY(scan64_inclusive(c, cnt, tiles));
+    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 49, cnt + tiles - 1, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    ZK_TRY(check_device_error(c));
+    *tile_incl = cnt;
+    *total = c->h_scalars[49];
+    return ZK_OK;
+}
+
+template <class P>
+static int compact_write(zk_ctx* c, const P& p, uint64_t n, const u64* tile_incl) {
+    if (n == 0) return ZK_OK;
+    hipLaunchKernelGGL((compact_write_kernel<P>), dim3((u32)div_up(n, CP_TILE)), dim3(CP_BLOCK), 0, c->stream, p, (u64)n, tile_incl);
+    ZK_HIP(c, hipGetLastError());
+    return ZK_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// predicates
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 base_code(u32 ch, u32& ok) {     // A0 C1 G2 T/U3 (either case); ok = in AaCcGgTtUu
+    const u32 t = (ch >> 1) & 3u;
+    const u32 d = (ch | 0x20u) - 0x61u;
+    ok = (d <= 20u) ? ((0x180045u >> d) & 1u) : 0u;
+    return t ^ (t >> 1);
+}
+
+struct NewlinePos {      // positions of the '\n' bytes
+    const u8* text; u64* out;
+    __device__ bool flag(u64 i) const { return text[i] == '\n'; }
+    __device__ void store(u64 pos, u64 i) const { out[pos] = i; }
+};
+
+// item i = window at position i >> 1 of the bait stream, strand i & 1 (basics.kmersList(K, seq, True): x then rc x)
+struct BaitWindow {
+    const u8* stream; u64 n; int K; const u64* ends; u64 n_ends; u64* keys; u32* ids;
+    __device__ bool window(u64 pos, u64& x, u64& xb) const {
+        if (pos + K > n) return false;
+        x = 0; xb = 0;
+        for (int j = 0; j < K; j++) {
+            u32 ok;
+            const u32 b = base_code(stream[pos + j], ok);
+            if (!ok) return false;
+            x = (x << 2) | b;
+            xb |= (u64)(3u - b) << (2 * j);
+        }
+        return true;
+    }
+    __device__ bool flag(u64 i) const { u64 x, xb; return window(i >> 1, x, xb); }
+    __device__ void store(u64 pos, u64 i) const {
+        u64 x, xb;
+        window(i >> 1, x, xb);
+        keys[pos] = (i & 1) ? xb : x;
+        u64 lo = 0, hi = n_ends;           // record = number of terminators before the window
+        while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (ends[mid] < (i >> 1)) lo = mid + 1; else hi = mid; }
+        ids[pos] = (u32)lo;
+    }
+};
+
+struct DistinctPairs {   // first of each run of equal (key, id) in a key-sorted, id-stable array
+    const u64* k; const u32* v; u64* ok; u32* ov;
+    __device__ bool flag(u64 i) const { return i == 0 || k[i] != k[i - 1] || v[i] != v[i - 1]; }
+    __device__ void store(u64 pos, u64 i) const { ok[pos] = k[i]; ov[pos] = v[i]; }
+};
+
+struct DistinctKeys {    // first of each run of equal keys -> (key, CSR offset)
+    const u64* k; u64* ok; u32* offs;
+    __device__ bool flag(u64 i) const { return i == 0 || k[i] != k[i - 1]; }
+    __device__ void store(u64 pos, u64 i) const { ok[pos] = k[i]; offs[pos] = (u32)i; }
+};
+
+struct DistinctWords {   // first of each run of equal words
+    const u64* k; u64* out;
+    __device__ bool flag(u64 i) const { return i == 0 || k[i] != k[i - 1]; }
+    __device__ void store(u64 pos, u64 i) const { out[pos] = k[i]; }
+};
+
+// ---------------------------------------------------------------------------------------
+// the table
+// ---------------------------------------------------------------------------------------
+struct BaitView {
+    const u64* keys; const u32* offs; const u32* ids; const u32* dir; u64 n_keys; int kbits, shift;
+};
+
+static BaitView view_of(const zk_bait_table* t) {
+    BaitView v{nullptr, nullptr, nullptr, nullptr, 0, 64, 0};
+    if (t && t->n_keys) v = BaitView{t->keys, t->offs, t->ids, t->dir, t->n_keys, t->kbits, t->kbits - t->bits};
+    return v;
+}
+
+// x -> ids[lo, hi) of the key equal to x.  A miss costs the directory's two words (one line) and, in a non-empty
+// bucket, a search among its ~1-2 keys.
+__device__ __forceinline__ bool bait_find(const BaitView& t, u64 x, u32& lo, u32& hi) {
+    if (t.n_keys == 0) return false;
+    if (t.kbits < 64 && (x >> t.kbits) != 0) return false;
+    const u64 bk = x >> t.shift;
+    u32 a = t.dir[bk];
+    const u32 end = t.dir[bk + 1];
+    u32 e = end;
+    while (a < e) { const u32 mid = (a + e) >> 1; if (t.keys[mid] < x) a = mid + 1; else e = mid; }
+    if (a < end && t.keys[a] == x) { lo = t.offs[a]; hi = t.offs[a + 1]; return true; }
+    return false;
+}
+
+__global__ void dir_kernel(const u64* __restrict__ keys, u64 n_keys, int shift, u64 nb, u32* __restrict__ dir) {
+    for (u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x; b <= nb; b += (u64)gridDim.x * blockDim.x) {
+        if (b == nb) { dir[b] = (u32)n_keys; continue; }
+        const u64 q = b << shift;
+        u64 lo = 0, hi = n_keys;
+        while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (keys[mid] < q) lo = mid + 1; else hi = mid; }
+        dir[b] = (u32)lo;
+    }
+}
+
+__global__ void put_u32_kernel(u32* p, u32 v) { *p = v; }
+
+static void table_free(zk_bait_table* t) {
+    if (!t) return;
+    if (t->ctx) { enter(t->ctx); (void)hipStreamSynchronize(t->ctx->stream); }
+    if (t->keys) (void)hipFree(t->keys);
+    if (t->offs) (void)hipFree(t->offs);
+    if (t->ids) (void)hipFree(t->ids);
+    if (t->dir) (void)hipFree(t->dir);
+    delete t;
+}
+
+static int tmalloc(zk_ctx* c, void** p, uint64_t bytes) {
+    hipError_t e = hipMalloc(p, bytes < 256 ? 256 : bytes);
+    if (e != hipSuccess) return fail(c, ZK_ENOMEM, "hipMalloc(%llu) for the bait table failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+    return ZK_OK;
+}
+
+static int bait_table_build(zk_ctx* c, const u8* stream, uint64_t n, int K, zk_bait_table* t) {
+    t->ctx = c; t->K = K; t->kbits = 2 * K;
+    const uint64_t W = 2 * n;             // windows x strands, an upper bound
+    ZK_TRY(arena_require(c, 8 * n + 32 * W + W / 32 + (4 << 20), 8 * n + 32 * W + W / 32 + (4 << 20)));
+    u64* cnt;
+    uint64_t n_rec = 0;
+    NewlinePos nl{stream, nullptr};
+    ZK_TRY(compact_count(c, nl, n, &cnt, &n_rec));
+    u64* ends;
+    ZK_TRY(arena_alloc(c, 8 * (n_rec + 1), (void**)&ends));
+    nl.out = ends;
+    ZK_TRY(compact_write(c, nl, n, cnt));
+    t->n_records = n_rec;
+    u64 *keys, *alt; u32 *ids, *valt;
+    ZK_TRY(arena_alloc(c, 8 * W + 8, (void**)&keys));
+    ZK_TRY(arena_alloc(c, 8 * W + 8, (void**)&alt));
+    ZK_TRY(arena_alloc(c, 4 * W + 4, (void**)&ids));
+    ZK_TRY(arena_alloc(c, 4 * W + 4, (void**)&valt));
+    BaitWindow bw{stream, (u64)n, K, ends, (u64)n_rec, keys, ids};
+    uint64_t nw = 0;
+    ZK_TRY(compact_count(c, bw, W, &cnt, &nw));
+    ZK_TRY(compact_write(c, bw, W, cnt));
+    if (nw >= 0xffffffffull) return fail(c, ZK_ERANGE, "bait table: %llu k-mers (at most 2^32 - 1)", (unsigned long long)nw);
+    u64* rk = keys; u32* rv = ids;
+    if (nw) ZK_TRY(sort_pairs(c, keys, alt, ids, valt, nw, 2 * K, &rk, &rv));
+    u64* k2 = (rk == keys) ? alt : keys;
+    uint64_t n_ids = 0;
+    DistinctPairs dp{rk, rv, k2, nullptr};
+    ZK_TRY(compact_count(c, dp, nw, &cnt, &n_ids));
+    ZK_TRY(tmalloc(c, (void**)&t->ids, 4 * n_ids));
+    dp.ov = t->ids;
+    ZK_TRY(compact_write(c, dp, nw, cnt));
+    uint64_t n_keys = 0;
+    DistinctKeys dk{k2, nullptr, nullptr};
+    ZK_TRY(compact_count(c, dk, n_ids, &cnt, &n_keys));
+    ZK_TRY(tmalloc(c, (void**)&t->keys, 8 * n_keys));
+    ZK_TRY(tmalloc(c, (void**)&t->offs, 4 * (n_keys + 1)));
+    dk.ok = t->keys; dk.offs = t->offs;
+    ZK_TRY(compact_write(c, dk, n_ids, cnt));
+    hipLaunchKernelGGL(put_u32_kernel, dim3(1), dim3(1), 0, c->stream, t->offs + n_keys, (u32)n_ids);
+    ZK_HIP(c, hipGetLastError());
+    t->n_ids = n_ids; t->n_keys = n_keys;
+    // directory: about one key per bucket
+    int bits = 1;
+    while (bits < 26 && (1ull << bits) < n_keys) bits++;
+    if (bits > t->kbits) bits = t->kbits;
+    t->bits = bits;
+    const u64 nb = 1ull << bits;
+    ZK_TRY(tmalloc(c, (void**)&t->dir, 4 * (nb + 1)));
+    u64 g = div_up(nb + 1, 256);
+    if (g > (u64)c->num_cus * 16) g = (u64)c->num_cus * 16;
+    hipLaunchKernelGGL(dir_kernel, dim3((u32)g), dim3(256), 0, c->stream, t->keys, (u64)n_keys, t->kbits - bits, nb, t->dir);
+    ZK_HIP(c, hipGetLastError());
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    return check_device_error(c);
+}
+
+// ---------------------------------------------------------------------------------------
+// window lookup: one wave per read
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ u64 spread_bits(u32 v) {      // bit i -> bit 2i
+    u64 x = v;
+    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+    return x;
+}
+__device__ __forceinline__ u32 bits_from(u64 lo, u64 hi, int l) {   // bits l .. l+31 of hi:lo
+    return l ? (u32)((lo >> l) | (hi << (64 - l))) : (u32)lo;
+}
+
+// The window of RK bases that starts at lane l of the 64-byte chunk text[c0, c0 + 64) of a sequence line ending at e
+// (bytes at or past e do not count).  Each lane loads one byte of the chunk (and lanes 0-31 one of the next 32); three
+// ballots per row turn the codes and validity into bit planes, from which every lane cuts its own 2*RK bits.
+// Called by the whole wave (ballots).
+__device__ __forceinline__ bool chunk_window(const u8* __restrict__ text, u64 c0, u64 e, int RK, int lane, u64& x) {
+    u32 ok1 = 0, ok2 = 0, b1 = 0, b2 = 0;
+    if (c0 + lane < e) b1 = base_code(text[c0 + lane], ok1);
+    if (lane < 32 && c0 + 64 + lane < e) b2 = base_code(text[c0 + 64 + lane], ok2);
+    const u64 lo0 = __ballot(ok1 && (b1 & 1u)), lo1 = __ballot(ok1 && (b1 & 2u)), lov = __ballot(ok1 != 0);
+    const u64 hi0 = __ballot(ok2 && (b2 & 1u)), hi1 = __ballot(ok2 && (b2 & 2u)), hiv = __ballot(ok2 != 0);
+    const u32 v = bits_from(lov, hiv, lane);
+    const u32 need = RK >= 32 ? 0xffffffffu : ((1u << RK) - 1u);
+    const u64 z = (spread_bits(__brev(bits_from(lo1, hi1, lane))) << 1) | spread_bits(__brev(bits_from(lo0, hi0, lane)));
+    x = z >> (64 - 2 * RK);
+    return (v & need) == need;
+}
+
+__device__ __forceinline__ u32 wave_min_u32(u32 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const u32 t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
+    return v;
+}
+
+struct Mate { const u8* text; const u64* lines; };
+
+__global__ __launch_bounds__(256) void capture_hits_kernel(BaitView bt, BaitView vt, int RK, Mate m1, Mate m2, u64 n_reads,
+                                                           u64* __restrict__ pairs, u64 cap, u64* n_raw) {
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    const u64 nw = ((u64)gridDim.x * blockDim.x) >> 6;
+    const int mates = m2.text ? 2 : 1;
+    for (u64 r = wave; r < n_reads; r += nw) {
+        if (vt.n_keys) {      // a read with any window in the veto set is not captured
+            bool veto = false;
+            for (int m = 0; m < mates && !veto; m++) {
+                const Mate mt = m ? m2 : m1;
+                const u64 b = mt.lines[4 * r] + 1, e = mt.lines[4 * r + 1];
+                for (u64 c0 = b; c0 < e && !veto; c0 += 64) {
+                    u64 x; u32 lo, hi;
+                    const bool hit = chunk_window(mt.text, c0, e, RK, lane, x) && bait_find(vt, x, lo, hi);
+                    veto = __ballot(hit) != 0;
+                }
+            }
+            if (veto) continue;
+        }
+        for (int m = 0; m < mates; m++) {
+            const Mate mt = m ? m2 : m1;
+            const u64 b = mt.lines[4 * r] + 1, e = mt.lines[4 * r + 1];
+            for (u64 c0 = b; c0 < e; c0 += 64) {
+                u64 x;
+                u32 p = 0, pe = 0;
+                if (!(chunk_window(mt.text, c0, e, RK, lane, x) && bait_find(bt, x, p, pe))) p = pe = 0;
+                // the distinct ids of the chunk, smallest first: each lane's list ascends, the wave takes the minimum of the heads
+                while (__ballot(p < pe)) {
+                    const u32 my = p < pe ? bt.ids[p] : 0xffffffffu;
+                    const u32 mn = wave_min_u32(my);
+                    if (lane == 0) {
+                        const u64 q = atomicAdd(n_raw, 1ull);
+                        if (q < cap) pairs[q] = ((u64)mn << 32) | r;
+                    }
+                    if (p < pe && my == mn) p++;
+                }
+            }
+        }
+    }
+}
+
+static int capture_hits(zk_ctx* c, const zk_bait_table* baits, const zk_bait_table* veto, int RK, Mate m1, Mate m2,
+                        uint64_t n_reads, u64* pairs, uint64_t cap, uint64_t* n_pairs) {
+    *n_pairs = 0;
+    if (n_reads == 0 || baits->n_keys == 0) return ZK_OK;
+    u64* d_raw = c->d_scalars + 48;
+    ZK_HIP(c, hipMemsetAsync(d_raw, 0, sizeof(u64), c->stream));
+    u64 g = div_up(n_reads, 4);
+    if (g > (u64)c->num_cus * 16) g = (u64)c->num_cus * 16;
+    prof_begin(c, ZK_PROF_CAPTURE_HITS, 0);
+    hipLaunchKernelGGL(capture_hits_kernel, dim3((u32)g), dim3(256), 0, c->stream, view_of(baits), view_of(veto), RK, m1, m2,
+                       (u64)n_reads, pairs, (u64)cap, d_raw);
+    prof_end(c);
+    ZK_HIP(c, hipGetLastError());
+    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 48, d_raw, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    ZK_TRY(check_device_error(c));
+    const uint64_t raw = c->h_scalars[48];
+    if (raw > cap) {
+        *n_pairs = raw;
+        return fail(c, ZK_ENOSPC, "capture: %llu (bait, read) pairs before deduplication, room for %llu", (unsigned long long)raw,
+                    (unsigned long long)cap);
+    }
+    if (raw == 0) return ZK_OK;
+    ZK_TRY(arena_require(c, 16 * raw + raw / 32 + (4 << 20), 16 * raw + raw / 32 + (4 << 20)));
+    u64 *alt, *res;
+    ZK_TRY(arena_alloc(c, 8 * raw, (void**)&alt));
+    int bbits = 1;
+    while (bbits < 32 && (1ull << bbits) < baits->n_records) bbits++;
+    ZK_TRY(sort_keys(c, pairs, alt, raw, 32 + bbits, &res));
+    if (res == pairs) ZK_HIP(c, hipMemcpyAsync(alt, pairs, 8 * raw, hipMemcpyDeviceToDevice, c->stream));
+    DistinctWords dw{alt, pairs};
+    u64* cnt;
+    uint64_t n = 0;
+    ZK_TRY(compact_count(c, dw, raw, &cnt, &n));
+    ZK_TRY(compact_write(c, dw, raw, cnt));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    *n_pairs = n;
+    return check_device_error(c);
+}
+
+// ---------------------------------------------------------------------------------------
+// record gather
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ bool is_space(u32 ch) { return ch == ' ' || (ch >= 9 && ch <= 13); }   // str.strip()
+
+// line i of the text, stripped: [s, e)
+__device__ __forceinline__ void stripped_line(const u8* __restrict__ text, const u64* __restrict__ lines, u64 i, u64& s, u64& e) {
+    s = i ? lines[i - 1] + 1 : 0;
+    e = lines[i];
+    while (s < e && is_space(text[s])) s++;
+    while (e > s && is_space(text[e - 1])) e--;
+}
+
+__global__ void record_len_kernel(const u64* __restrict__ pairs, u64 n, const u8* __restrict__ text, const u64* __restrict__ lines,
+                                  u64 n_lines, u64* __restrict__ len, u32* err) {
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x) {
+        const u64 r = pairs[j] & 0xffffffffull;
+        u64 t = 0;
+        if (4 * r + 3 < n_lines) {
+            for (int i = 0; i < 4; i++) { u64 s, e; stripped_line(text, lines, 4 * r + i, s, e); t += e - s + 1; }
+        } else {
+            atomicOr(err, ZK_DERR_CAPACITY);
+        }
+        len[j] = t;
+    }
+}
+
+// one wave per record: its four stripped lines, each followed by '\n', at out + (exclusive prefix of the lengths)
+__global__ void record_copy_kernel(const u64* __restrict__ pairs, u64 n, const u8* __restrict__ text, const u64* __restrict__ lines,
+                                   u64 n_lines, const u64* __restrict__ incl, u8* __restrict__ out) {
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    const u64 nw = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 j = wave; j < n; j += nw) {
+        const u64 r = pairs[j] & 0xffffffffull;
+        if (4 * r + 3 >= n_lines) continue;
+        u64 o = j ? incl[j - 1] : 0;
+        for (int i = 0; i < 4; i++) {
+            u64 s, e;
+            stripped_line(text, lines, 4 * r + i, s, e);
+            for (u64 k = lane; k < e - s; k += 64) out[o + k] = text[s + k];
+            if (lane == 0) out[o + (e - s)] = '\n';
+            o += e - s + 1;
+        }
+    }
+}
+
+// spans[b] = first pair of bait b, spans[nb + 1 + b] = its first output byte (b = 0 .. nb)
+__global__ void bait_spans_kernel(const u64* __restrict__ pairs, u64 n, const u64* __restrict__ incl, u32 nb, u64* __restrict__ spans) {
+    for (u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x; b <= nb; b += (u64)gridDim.x * blockDim.x) {
+        const u64 q = b << 32;
+        u64 lo = 0, hi = n;
+        while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (pairs[mid] < q) lo = mid + 1; else hi = mid; }
+        spans[b] = lo;
+        spans[nb + 1 + b] = lo ? incl[lo - 1] : 0;
+    }
+}
+
+static int capture_gather(zk_ctx* c, const u64* pairs, uint64_t n, uint32_t nb, const u8* text, const u64* lines, uint64_t n_lines,
+                          u8* out, uint64_t cap, uint64_t* spans, uint64_t* n_bytes) {
+    *n_bytes = 0;
+    const uint64_t need = 8 * n + 16ull * (nb + 1) + (1 << 20);
+    ZK_TRY(arena_require(c, need, need));
+    u64 *len, *d_spans;
+    ZK_TRY(arena_alloc(c, 8 * n + 8, (void**)&len));
+    ZK_TRY(arena_alloc(c, 16ull * (nb + 1), (void**)&d_spans));
+    u64 g = div_up(n, 256);
+    if (g > (u64)c->num_cus * 16) g = (u64)c->num_cus * 16;
+    if (n) {
+        hipLaunchKernelGGL(record_len_kernel, dim3((u32)g), dim3(256), 0, c->stream, pairs, (u64)n, text, lines, (u64)n_lines, len, c->d_err);
+        ZK_HIP(c, hipGetLastError());
+        ZK_TRY(scan64_inclusive(c, len, n));
+    }
+    u64 gs = div_up((u64)nb + 1, 256);
+    if (gs > (u64)c->num_cus * 16) gs = (u64)c->num_cus * 16;
+    hipLaunchKernelGGL(bait_spans_kernel, dim3((u32)gs), dim3(256), 0, c->stream, pairs, (u64)n, len, nb, d_spans);
+    ZK_HIP(c, hipGetLastError());
+    ZK_HIP(c, hipMemcpyAsync(spans, d_spans, 16ull * (nb + 1), hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    ZK_TRY(check_device_error(c));
+    const uint64_t total = spans[2ull * nb + 1];
+    *n_bytes = total;
+    if (total > cap)
+        return fail(c, ZK_ENOSPC, "capture gather: %llu bytes of records, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    if (n) {
+        u64 gw = div_up(n, 4);
+        if (gw > (u64)c->num_cus * 16) gw = (u64)c->num_cus * 16;
+        hipLaunchKernelGGL(record_copy_kernel, dim3((u32)gw), dim3(256), 0, c->stream, pairs, (u64)n, text, lines, (u64)n_lines, len, out);
+        ZK_HIP(c, hipGetLastError());
+    }
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    return check_device_error(c);
+}
+
+}  // namespace zk
+
+using namespace zk;
+
+#define ZK_ARGS(c, cond) do { if (!(c)) return ZK_EINVAL; zk::enter(c); if (!(cond)) return zk::fail((c), ZK_EINVAL, "bad argument: %s", #cond); } while (0)
+
+extern "C" {
+
+int zk_bait_table_build(zk_ctx* c, const uint8_t* d_stream, uint64_t n_bytes, int K, zk_bait_table** table) {
+    ZK_ARGS(c, table && K >= 1 && K <= 32 && (n_bytes == 0 || d_stream));
+    *table = nullptr;
+    arena_reset(c);
+    zk_bait_table* t = new zk_bait_table();
+    const int rc = bait_table_build(c, d_stream, n_bytes, K, t);
+    if (rc != ZK_OK) { table_free(t); return rc; }
+    *table = t;
+    return ZK_OK;
+}
+
+int zk_bait_table_info(const zk_bait_table* t, uint64_t* n_keys, uint64_t* n_ids, uint64_t* n_records) {
+    if (!t || !n_keys || !n_ids || !n_records) return ZK_EINVAL;
+    *n_keys = t->n_keys; *n_ids = t->n_ids; *n_records = t->n_records;
+    return ZK_OK;
+}
+
+void zk_bait_table_free(zk_bait_table* t) { table_free(t); }
+
+int zk_line_ends(zk_ctx* c, const uint8_t* d_text, uint64_t n, uint64_t* d_out, uint64_t cap, uint64_t* n_lines) {
+    ZK_ARGS(c, n_lines && (n == 0 || d_text));
+    *n_lines = 0;
+    arena_reset(c);
+    NewlinePos nl{d_text, (u64*)d_out};
+    u64* cnt;
+    uint64_t total = 0;
+    ZK_TRY(compact_count(c, nl, n, &cnt, &total));
+    *n_lines = total;
+    if (total > cap) return fail(c, ZK_ENOSPC, "zk_line_ends: %llu lines, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    if (total && !d_out) return fail(c, ZK_EINVAL, "bad argument: d_out");
+    ZK_TRY(compact_write(c, nl, n, cnt));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    return check_device_error(c);
+}
+
+int zk_capture_hits(zk_ctx* c, const zk_bait_table* baits, const zk_bait_table* veto, int read_K, const uint8_t* d_text1,
+                    const uint64_t* d_lines1, const uint8_t* d_text2, const uint64_t* d_lines2, uint64_t n_reads, uint64_t* d_pairs,
+                    uint64_t cap, uint64_t* n_pairs) {
+    ZK_ARGS(c, baits && n_pairs && read_K >= 1 && read_K <= 32 && n_reads < (1ull << 32) && (!d_text2 == !d_lines2) &&
+                   (n_reads == 0 || (d_text1 && d_lines1)) && (cap == 0 || d_pairs));
+    arena_reset(c);
+    return capture_hits(c, baits, veto, read_K, Mate{d_text1, (const u64*)d_lines1}, Mate{d_text2, (const u64*)d_lines2}, n_reads, (u64*)d_pairs, cap, n_pairs);
+}
+
+int zk_capture_gather(zk_ctx* c, const uint64_t* d_pairs, uint64_t n_pairs, uint32_t n_baits, const uint8_t* d_text,
+                      const uint64_t* d_lines, uint64_t n_lines, uint8_t* d_out, uint64_t cap, uint64_t* spans, uint64_t* n_bytes) {
+    ZK_ARGS(c, spans && n_bytes && n_baits < 0xffffffffu && (n_pairs == 0 || (d_pairs && d_text && d_lines)) && (cap == 0 || d_out));
+    arena_reset(c);
+    return capture_gather(c, (const u64*)d_pairs, n_pairs, n_baits, d_text, (const u64*)d_lines, n_lines, d_out, cap, spans, n_bytes);
+}
+
+}  // extern "C"

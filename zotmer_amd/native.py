@@ -118,6 +118,12 @@ SIGNATURES = {
     "zk_allreduce_u64": (_i, [_vp, _pu64, _u64, _i]),
     "zk_comm_plan": (_i, [_i, _i, _pu64, _pu64, _pu64, _pu64, _i, _u64, _i, _vp, _u64, _pu64]),
     "zk_stream_checksum": (_i, [_vp, _vp, _u64, _i, _pu64]),
+    "zk_bait_table_build": (_i, [_vp, _vp, _u64, _i, C.POINTER(_vp)]),
+    "zk_bait_table_info": (_i, [_vp, _pu64, _pu64, _pu64]),
+    "zk_bait_table_free": (None, [_vp]),
+    "zk_line_ends": (_i, [_vp, _vp, _u64, _vp, _u64, _pu64]),
+    "zk_capture_hits": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _pu64]),
+    "zk_capture_gather": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _u64, _pu64, _pu64]),
 }
 
 _lib = None
@@ -206,6 +212,28 @@ class Source:
 
     def __exit__(self, *a):
         self.close()
+
+
+class BaitTable:
+    """zk_bait_table: sorted distinct K-mers of both strands of a set of sequences -> the ascending indices of the sequences
+    that hold each one (device memory of its own, freed with the object)."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+        nk, ni, nr = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        ctx._check(ctx.lib.zk_bait_table_info(h, C.byref(nk), C.byref(ni), C.byref(nr)))
+        self.n_keys, self.n_ids, self.n_records = nk.value, ni.value, nr.value
+
+    def free(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.zk_bait_table_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class Context:
@@ -317,7 +345,8 @@ class Context:
 
     # ---- per-launch timing (HIP events on the ctx stream) -----------------------------------
     PROF_TAGS = {"hist_stream": 1, "hist_array": 2, "pass_stream": 3, "pass_keys": 4, "pass_pairs": 5, "rle": 6,
-                 "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14}
+                 "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
+                 "capture_hits": 15}
 
     def tune(self, sort_variant=None, pairs_variant=None, short_sort=None, side_div=None, xcd_group=None, comm_chunk=None,
              early_collapse=None, packed_pairs=None, wide_tiles=None, stream_pass=None, stream_ranges=None, tag_words=None,
@@ -705,6 +734,56 @@ class Context:
         s = (C.c_uint64 * 7)()
         self._check(self.lib.zk_stream_checksum(self.h, stream.ptr, stream.n, K, s))
         return [int(v) for v in s[3:7]]
+
+    # ---- read capture (csrc/capture.hip) ------------------------------------------------------------------
+    def bait_table(self, stream, K):
+        """BaitTable of a base stream of sequences, each followed by one '\\n' (a uint8 DeviceArray)."""
+        h = _vp()
+        self._check(self.lib.zk_bait_table_build(self.h, stream.ptr, stream.n, int(K), C.byref(h)))
+        return BaitTable(self, h.value)
+
+    def line_ends(self, text, out=None):
+        """positions of the '\\n' bytes of a device text -> u64 DeviceArray view (out: a buffer to reuse; grown when too small)"""
+        n = C.c_uint64(0)
+        if out is None:
+            out = self.empty(text.n // 8 + 64, np.uint64)
+        rc = self.lib.zk_line_ends(self.h, text.ptr, text.n, out.ptr, out.n, C.byref(n))
+        if rc == ZK_ENOSPC:
+            out = self.empty(n.value + 64, np.uint64)
+            rc = self.lib.zk_line_ends(self.h, text.ptr, text.n, out.ptr, out.n, C.byref(n))
+        self._check(rc)
+        return out.view(n.value)
+
+    def capture_hits(self, table, read_K, text1, lines1, n_reads, text2=None, lines2=None, veto=None, out=None):
+        """distinct (bait, read) pairs as bait << 32 | read, ascending -> u64 DeviceArray view (out: a buffer to reuse)"""
+        assert 4 * n_reads <= lines1.n and (lines2 is None or 4 * n_reads <= lines2.n)
+        n = C.c_uint64(0)
+        if out is None:
+            out = self.empty(2 * n_reads + 1024, np.uint64)
+        args = lambda o: (self.h, table.h, veto.h if veto is not None else None, int(read_K), text1.ptr, lines1.ptr,
+                          text2.ptr if text2 is not None else None, lines2.ptr if lines2 is not None else None, int(n_reads), o.ptr,
+                          o.n, C.byref(n))
+        rc = self.lib.zk_capture_hits(*args(out))
+        if rc == ZK_ENOSPC:
+            out = self.empty(n.value + 1024, np.uint64)
+            rc = self.lib.zk_capture_hits(*args(out))
+        self._check(rc)
+        return out.view(n.value)
+
+    def capture_gather(self, pairs, n_baits, text, lines, out=None):
+        """the captured records, bait by bait -> (uint8 DeviceArray view, pair offsets u64[n_baits + 1], byte offsets u64[n_baits + 1])"""
+        spans = np.zeros(2 * (n_baits + 1), dtype=np.uint64)
+        n = C.c_uint64(0)
+        if out is None:
+            out = self.empty(text.n + 1024, np.uint8)
+        args = lambda o: (self.h, pairs.ptr, pairs.n, int(n_baits), text.ptr, lines.ptr, lines.n, o.ptr, o.n,
+                          spans.ctypes.data_as(_pu64), C.byref(n))
+        rc = self.lib.zk_capture_gather(*args(out))
+        if rc == ZK_ENOSPC:
+            out = self.empty(n.value + 1024, np.uint8)
+            rc = self.lib.zk_capture_gather(*args(out))
+        self._check(rc)
+        return out.view(n.value), spans[:n_baits + 1], spans[n_baits + 1:]
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
