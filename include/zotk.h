@@ -236,7 +236,8 @@ int zk_mirror_expand(zk_ctx* ctx, const uint64_t* d_canon_kmers, const uint32_t*
                      uint64_t* d_kmers, uint32_t* d_counts, uint64_t cap, uint64_t* n_out);
 
 /* hist[c] += 1 per distinct k-mer (commands/kmerize.py:543-545; merge.py:88-92), as ascending
- * (value, frequency) pairs in HOST arrays of cap_bins entries.  count_bits is 32 or 64. */
+ * (value, frequency) pairs in HOST arrays of cap_bins entries.  count_bits is 32 or 64.  ZK_ENOSPC: more than
+ * cap_bins bins; *n_bins is then the number of bins (the first cap_bins are written), so one more call sizes it. */
 int zk_hist(zk_ctx* ctx, const void* d_counts, int count_bits, uint64_t n,
             uint64_t* vals, uint64_t* freq, uint64_t cap_bins, uint64_t* n_bins);
 

@@ -901,13 +901,16 @@ __global__ __launch_bounds__(256) void count_hist_kernel(const CT* __restrict__ 
 #pragma unroll
       for (int q = 0; q < ROWS; q++) {
           const u64 i = i0 + (u64)q * 256 + threadIdx.x;
-          vv[q] = i < n ? (u64)counts[i] : 1ull << 63;          // (past the end: a value nobody counts)
+          vv[q] = (u64)counts[i < n ? i : n - 1];          // (past the end: the last count again, not counted below; n >= 1)
       }
+      __builtin_amdgcn_sched_barrier(0);          // all four loads issued before the first is waited for
 #pragma unroll
       for (int q = 0; q < ROWS; q++) {
         const u64 v = vv[q];
-        ones += v == 1 ? 1u : 0u;
-        bool act = v != 1 && v != (1ull << 63);
+        // past the end by position, not by value: every u64 (2^63, 2^64 - 1) is a count that may occur
+        const bool valid = i0 + (u64)q * 256 + threadIdx.x < n;
+        ones += valid && v == 1 ? 1u : 0u;
+        bool act = valid && v != 1;
         if (!__any((int)act)) continue;
 #pragma unroll
         for (int r = 0; r < 2; r++) {
@@ -940,49 +943,60 @@ int count_hist(zk_ctx* c, const void* counts, int count_bits, uint64_t n, uint64
                uint64_t cap_bins, uint64_t* n_bins) {
     *n_bins = 0;
     if (n == 0) return ZK_OK;
-    const uint64_t big_cap = n < (1ull << 22) ? n : (1ull << 22);
-    u64 *dense, *big;
-    ZK_TRY(arena_require(c, sizeof(u64) * (HIST_DENSE + big_cap) + 4096, sizeof(u64) * (HIST_DENSE + big_cap) + 4096));
-    ZK_TRY(arena_alloc(c, sizeof(u64) * HIST_DENSE, (void**)&dense));
-    ZK_TRY(arena_alloc(c, sizeof(u64) * big_cap, (void**)&big));
+    // The side list starts at min(n, 4 Mi) entries.  The kernel counts every large count even when the list is full, so a second
+    // launch with the exact size finishes the histogram (zk_hist resets the arena per call: count_hist may start it over).
+    uint64_t big_cap = n < (1ull << 22) ? n : (1ull << 22);
+    u64 *dense = nullptr, *big = nullptr;
     u64* big_n = c->d_scalars + 10;
-    ZK_HIP(c, hipMemsetAsync(dense, 0, sizeof(u64) * HIST_DENSE, c->stream));
-    ZK_HIP(c, hipMemsetAsync(big_n, 0, sizeof(u64), c->stream));
-    u32 grid = (u32)(div_up(n, 256 * 16) < (uint64_t)c->num_cus * 8 ? div_up(n, 256 * 16) : (uint64_t)c->num_cus * 8);
-    prof_begin(c, ZK_PROF_COUNT_HIST, (count_bits / 8) * n);
-    if (count_bits == 32)
-        hipLaunchKernelGGL((count_hist_kernel<u32>), dim3(grid), dim3(256), 0, c->stream, (const u32*)counts, (u64)n, dense, big, (u64)big_cap, big_n);
-    else
-        hipLaunchKernelGGL((count_hist_kernel<u64>), dim3(grid), dim3(256), 0, c->stream, (const u64*)counts, (u64)n, dense, big, (u64)big_cap, big_n);
-    prof_end(c);
-    ZK_HIP(c, hipGetLastError());
     std::vector<u64> hd(HIST_DENSE);
     u64* h_dense = hd.data();
-    ZK_HIP(c, hipMemcpyAsync(h_dense, dense, sizeof(u64) * HIST_DENSE, hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 10, big_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    const uint64_t nb = c->h_scalars[10];
-    if (nb > big_cap) return fail(c, ZK_ENOSPC, "count histogram: %llu counts >= %d exceed the side list", (unsigned long long)nb, HIST_DENSE);
+    uint64_t nb = 0;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        arena_reset(c);
+        ZK_TRY(arena_require(c, sizeof(u64) * (HIST_DENSE + big_cap) + 4096, sizeof(u64) * (HIST_DENSE + big_cap) + 4096));
+        ZK_TRY(arena_alloc(c, sizeof(u64) * HIST_DENSE, (void**)&dense));
+        ZK_TRY(arena_alloc(c, sizeof(u64) * big_cap, (void**)&big));
+        ZK_HIP(c, hipMemsetAsync(dense, 0, sizeof(u64) * HIST_DENSE, c->stream));
+        ZK_HIP(c, hipMemsetAsync(big_n, 0, sizeof(u64), c->stream));
+        u32 grid = (u32)(div_up(n, 256 * 16) < (uint64_t)c->num_cus * 8 ? div_up(n, 256 * 16) : (uint64_t)c->num_cus * 8);
+        prof_begin(c, ZK_PROF_COUNT_HIST, (count_bits / 8) * n);
+        if (count_bits == 32)
+            hipLaunchKernelGGL((count_hist_kernel<u32>), dim3(grid), dim3(256), 0, c->stream, (const u32*)counts, (u64)n, dense, big, (u64)big_cap, big_n);
+        else
+            hipLaunchKernelGGL((count_hist_kernel<u64>), dim3(grid), dim3(256), 0, c->stream, (const u64*)counts, (u64)n, dense, big, (u64)big_cap, big_n);
+        prof_end(c);
+        ZK_HIP(c, hipGetLastError());
+        ZK_HIP(c, hipMemcpyAsync(h_dense, dense, sizeof(u64) * HIST_DENSE, hipMemcpyDeviceToHost, c->stream));
+        ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 10, big_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        ZK_HIP(c, hipStreamSynchronize(c->stream));
+        nb = c->h_scalars[10];
+        if (nb <= big_cap) break;
+        big_cap = nb;          // (nb <= n: the second launch cannot overflow)
+    }
+    if (nb > big_cap) return fail(c, ZK_EINTERNAL, "count histogram: %llu counts >= %d for a side list of %llu", (unsigned long long)nb,
+                                  HIST_DENSE, (unsigned long long)big_cap);
+    // more bins than cap_bins: the rest are still counted, *n_bins says how many the caller must make room for
     uint64_t m = 0;
+    auto emit = [&](u64 v, u64 f) {
+        if (m < cap_bins) { vals[m] = v; freq[m] = f; }
+        m++;
+    };
     for (int v = 0; v < HIST_DENSE; v++)
-        if (h_dense[v]) {
-            if (m >= cap_bins) return fail(c, ZK_ENOSPC, "histogram has more than %llu bins", (unsigned long long)cap_bins);
-            vals[m] = v; freq[m] = h_dense[v]; m++;
-        }
+        if (h_dense[v]) emit((u64)v, h_dense[v]);
     if (nb) {
         std::vector<u64> hb(nb);
         u64* h_big = hb.data();
         ZK_HIP(c, hipMemcpy(h_big, big, sizeof(u64) * nb, hipMemcpyDeviceToHost));
-        std::sort(hb.begin(), hb.end());   // the few counts >= HIST_DENSE
+        std::sort(hb.begin(), hb.end());   // the counts >= HIST_DENSE (usually few)
         for (uint64_t i = 0; i < nb;) {
             uint64_t j = i;
             while (j < nb && h_big[j] == h_big[i]) j++;
-            if (m >= cap_bins) return fail(c, ZK_ENOSPC, "histogram has more than %llu bins", (unsigned long long)cap_bins);
-            vals[m] = h_big[i]; freq[m] = j - i; m++;
+            emit(h_big[i], j - i);
             i = j;
         }
     }
     *n_bins = m;
+    if (m > cap_bins) return fail(c, ZK_ENOSPC, "histogram has %llu bins, room for %llu", (unsigned long long)m, (unsigned long long)cap_bins);
     return ZK_OK;
 }
 

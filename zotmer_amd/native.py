@@ -480,16 +480,16 @@ class Context:
     def hist(self, counts):
         bits = counts.dtype.itemsize * 8
         cap = 1 << 16
-        while True:
+        for _ in range(2):            # ZK_ENOSPC = more bins than cap; n then holds how many there are
             vals = np.empty(cap, dtype=np.uint64)
             freq = np.empty(cap, dtype=np.uint64)
             n = C.c_uint64(0)
             rc = self.lib.zk_hist(self.h, counts.ptr, bits, counts.n, vals.ctypes.data_as(_pu64), freq.ctypes.data_as(_pu64), cap, C.byref(n))
-            if rc == ZK_ENOSPC and cap < (1 << 26):
-                cap *= 8
-                continue
-            self._check(rc)
-            return {int(v): int(f) for v, f in zip(vals[:n.value], freq[:n.value])}
+            if rc != ZK_ENOSPC or n.value <= cap:
+                break
+            cap = n.value
+        self._check(rc)
+        return {int(v): int(f) for v, f in zip(vals[:n.value], freq[:n.value])}
 
     def widen(self, counts32):
         out = self.empty(counts32.n, np.uint64)
