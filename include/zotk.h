@@ -76,10 +76,12 @@ int zk_upload_async(zk_ctx* ctx, void* d_dst, const void* src, uint64_t bytes);
                                     2 = a run-length pass of its own once the copies are neighbours, 0 = off */
 #define ZK_TUNE_PACKED_PAIRS 8   /* zk_kmerize / zk_mirror_expand: 1 (default) = (k-mer, count) pairs travel as one 64-bit word when the counts fit the bits above 2K */
 #define ZK_TUNE_WIDE_TILES 9     /* radix sort: 1 (default) = array passes use 16 K-key tiles, one 1024-thread workgroup per CU; 0 = 8 K-key tiles, two of 512 */
-#define ZK_TUNE_STREAM_PASS 10   /* the first sort pass of zk_kmerize / zk_sort_stream: 1 (default) = static stream ranges, whole 64-byte units written
-                                  * out of LDS (stream_pass.hip); 3 = the same, a tile's units leaving in two bursts (measurements; 2 is accepted and
-                                  * equals 1); 0 = the look-back pipeline.  Other values are refused */
-#define ZK_TUNE_STREAM_RANGES 11 /* ... the number of ranges the stream is cut into, one workgroup each (0 = two per CU, the default; <= 4096) */
+#define ZK_TUNE_STREAM_PASS 10   /* the first sort pass of zk_kmerize / zk_sort_stream: 1 (default) = static stream ranges, one 1024-thread workgroup
+                                  * per CU, whole 128-byte units written out of LDS (stream_pass.hip); 2 = the same with two 512-thread workgroups
+                                  * per CU and 64-byte units; 3 = as 2, a tile's units leaving in two bursts (measurements); 0 = the look-back
+                                  * pipeline.  Other values are refused */
+#define ZK_TUNE_STREAM_RANGES 11 /* ... the number of ranges the stream is cut into, one workgroup each (0 = the default: one per CU for
+                                  * variant 1, two for 2 and 3; <= 4096) */
 #define ZK_TUNE_TAG_WORDS 12     /* zk_kmerize: 1 = the pass before the block dedupe writes 32-bit tags instead of whole keys when the key bits
                                   * below the blocks fit (K <= 25 after two passes); 2 (default) = ... and ranks the keys of a tile by LDS adds
                                   * where the tile lies inside one bucket of the pass before (nobody needs the order inside a block);

@@ -33,6 +33,9 @@ ctx._check(ctx.lib.zk_debug_buffer(ctx.h, None))
 raw = dbg.to_host().reshape(4096, 16).astype(np.float64)
 raw = raw[raw[:, 8] > 0]
 names = ["0 keys + rank", "1 barrier", "2 scan (2 barriers)", "3 park", "4 barrier", "5 next image (+ wait for bytes)", "6 stores issued", "7 barrier"]
+if variant == 1:          # the wide kernel (stream_pass0_wide_kernel): three barriers a tile
+    names = ["0 keys + rank", "1 barrier", "2 counter scan (waves 0-7) / carry copy (8-15)", "3 barrier",
+             "4 unit list + park + next image (+ wait for bytes)", "5 barrier", "6 stores issued", "7 -"]
 tiles = raw[:, 8].sum()
 per = raw[:, :8].sum(axis=0) / tiles * 10.0          # ns per tile
 out = {"reads": reads, "variant": variant, "mode": mode, "K": K, "ranges": int(len(raw)), "tiles_per_range": float(raw[:, 8].mean()),

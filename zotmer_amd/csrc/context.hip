@@ -325,7 +325,7 @@ int zk_tune(zk_ctx* c, int what, int value) {
 #ifdef ZK_PHASES
         c->stream_pass = value < 0 ? 0 : value;          // (bits 8 and up: the measurement modes of tools/p0_phases.py)
 #else
-        if (value < 0 || value > 3) return fail(c, ZK_EINVAL, "stream pass variant %d (0, 1 or 3)", value);
+        if (value < 0 || value > 3) return fail(c, ZK_EINVAL, "stream pass variant %d (0, 1, 2 or 3)", value);
         c->stream_pass = value;
 #endif
         return ZK_OK;

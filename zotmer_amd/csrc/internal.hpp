@@ -26,8 +26,9 @@ struct zk_ctx {
                                // 2 = a run-length pass of its own once the copies are neighbours (the round's first form), 0 = off
     int side_div = 8;          // ... side list capacity = n / side_div (tests shrink it to force the fallback)
     int pairs_variant = 7;     // ... for (key, u32) pairs: 7 = the pipeline with a payload (1024 threads x 8 pairs), 2 = one workgroup per tile, one serial chain per digit
-    int stream_pass = 1;       // the first sort pass (from the base stream): 1 = static ranges, whole 64-byte units written from LDS
-                               // (stream_pass.hip; 3 = a tile's units leave in two bursts, for measurements), 0 = the look-back pipeline
+    int stream_pass = 1;       // the first sort pass (from the base stream), over static ranges (stream_pass.hip): 1 = one 1024-thread workgroup
+                               // per CU writing whole 128-byte units from LDS, 2 = two 512-thread workgroups per CU writing 64-byte units,
+                               // 3 = as 2 with a tile's units leaving in two bursts (measurements); 0 = the look-back pipeline
     int tag_words = 2;         // zk_kmerize, block dedupe after two passes with at most 32 key bits below the blocks: the second pass writes
                                // only those bits, as 32-bit tags (radix_sort.hip); 2 (default) = ... and takes a key's place in its digit's run
                                // from a returning LDS add wherever a tile holds keys of one bucket of the pass before (pass_pipe_kernel VAR 3:
@@ -40,7 +41,7 @@ struct zk_ctx {
     int kway = 1;              // zk_merge_n: 1 = up to 16 lists per pass (kway.hip) from 4 Mi pairs on, 2 = always, 0 = the tree of 2-way passes
     int tile_sort = 1;         // sorts of keys that do not repeat: LSD passes over the top bits, then tiles sorted to the end in LDS (tilesort.hip)
     int dedupe_bits = 0;       // tests: > 0 = the block dedupe with this many block bits whatever the input's size (pipeline.hip)
-    int stream_ranges = 0;     // ... ranges the stream is cut into (0 = two per CU; tests use a few so that a range has many tiles)
+    int stream_ranges = 0;     // ... ranges the stream is cut into (0 = one per CU for variant 1, two for 2 and 3; tests use a few so that a range has many tiles)
 
     // workspace arena: a bump allocator reset at the start of every API call
     char* arena = nullptr;
@@ -181,7 +182,8 @@ int sort_stream(zk_ctx* c, const StreamSrc& src, u64* buf_a, u64* buf_b, uint64_
                 uint64_t acgt[4], u64** result);
 // stream_pass.hip: histogram + first pass over static stream ranges
 struct StreamRows { u32* rows = nullptr; u64* offs = nullptr; u32 ranges = 0, radix = 0; u32* gcodes = nullptr; u16* gvalid = nullptr;
-                    u32 strands = 1; };          // 2 (ZK_KEYS_BOTH): rows [ranges + w] are the reverse strand of range w
+                    u32 strands = 1;             // 2 (ZK_KEYS_BOTH): rows [ranges + w] are the reverse strand of range w
+                    bool wide = false; };        // the ranges are cut for the wide pass (1024 threads, 8 K-window tiles)
 int stream_hist(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, int mode, const PassPlan& plan, u64* ghist, u32 gstride,
                 u64* d_acgt, u64* d_n, u64* rec_info, u64* sample, u32 sample_cap, int sample_shift, u64 sample_value, u32* sample_n,
                 void* image_room, uint64_t image_room_bytes, StreamRows* out);

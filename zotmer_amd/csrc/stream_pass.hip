@@ -26,7 +26,13 @@
 namespace zk {
 
 constexpr int P0_BLOCK = 512, P0_NW = 8, P0_TILE = P0_BLOCK * P0_NW, P0_IMG_WORDS = 320;          // the pass: 2 workgroups per CU
+constexpr int PW_BLOCK = 1024, PW_NW = 8, PW_TILE = PW_BLOCK * PW_NW, PW_IMG_WORDS = 640;         // the wide pass: 1 workgroup per CU
 constexpr int SH_BLOCK = 512, SH_NW = 16, SH_TILE = SH_BLOCK * SH_NW;          // the histogram kernel's tiles: positions
+
+// The pass's tile geometry: threads, windows per thread, image words of a tile.  The histogram kernel cuts the ranges and counts
+// their rows for the form of the pass that will run, so both are given the same geometry.
+struct P0Geom { u32 block, nw, img_words; };
+__host__ __device__ constexpr P0Geom p0_geom(bool wide) { return wide ? P0Geom{PW_BLOCK, PW_NW, PW_IMG_WORDS} : P0Geom{P0_BLOCK, P0_NW, P0_IMG_WORDS}; }
 
 // How the stream is cut.  Decided from the position of the stream's first newline alone (the histogram kernel runs before
 // anybody knows whether the records are uniform), by the same function on the device and on the host.
@@ -39,21 +45,22 @@ struct StreamTiling {
     u64 range_bytes;      // stream bytes per range: a whole number of tiles, a multiple of 16
 };
 
-__host__ __device__ inline StreamTiling make_tiling(u64 n_bytes, u64 first_nl, int K, u32 ranges) {
+__host__ __device__ inline StreamTiling make_tiling(u64 n_bytes, u64 first_nl, int K, u32 ranges, P0Geom g) {
     StreamTiling t = {};
+    const u32 tile = g.block * g.nw;
     t.ranges = ranges ? ranges : 1;
-    t.tile_bytes = P0_TILE;
+    t.tile_bytes = tile;
     if (first_nl < 0x7fffffffull) {
         const u64 rec = first_nl + 1;
         const long long W = (long long)first_nl - K + 1;
         if (rec >= 16 && W >= 1 && n_bytes % rec == 0) {
-            const u32 cpr = (u32)((W + P0_NW - 1) / P0_NW);
-            u32 rpt = cpr <= (u32)P0_BLOCK ? ((u32)P0_BLOCK / cpr) / 16 * 16 : 0;
-            const u32 fit = (u32)((16ull * (P0_IMG_WORDS - 3)) / rec) / 16 * 16;
+            const u32 cpr = (u32)((W + g.nw - 1) / g.nw);
+            u32 rpt = cpr <= g.block ? (g.block / cpr) / 16 * 16 : 0;
+            const u32 fit = (u32)((16ull * (g.img_words - 3)) / rec) / 16 * 16;
             if (rpt > fit) rpt = fit;
             // tiles that follow the records spend no key slot on the windows that run into a separator: worth it when such a
             // tile covers more of the stream than a tile of positions
-            if (rpt >= 16 && (u64)rpt * rec * 50 > (u64)P0_TILE * 51) {
+            if (rpt >= 16 && (u64)rpt * rec * 50 > (u64)tile * 51) {
                 t.rec = (u32)rec; t.rpt = rpt; t.cpr = cpr; t.wpr = (u32)W;
                 t.cpr_inv = (u32)(((1ull << 32) + cpr - 1) / cpr);
                 t.tile_bytes = rpt * (u32)rec;
@@ -167,6 +174,7 @@ struct SHistArgs {
     u32* gcodes;                  // [ceil(n_bytes / 16)] the stream's 2-bit image, 16 bases per word (first base on top) ...
     u16* gvalid;                  // ... and which of them are bases: the pass reads these instead of encoding the bytes again
     int dbg_atomics;              // diagnostic build (-DZK_PHASES) only: LDS adds per window (2 = as in the product)
+    P0Geom geom;                  // the tiles of the pass that follows (make_tiling)
 };
 
 // HI: every digit (and the sample test) looks only at key bits >= 32: the strands are compared on the high words alone --
@@ -187,7 +195,7 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void stream_hist_kernel(SHistArgs h) {
         pbase[tid] = h.binbase[tid];
     }
     const u64 first_nl = h.rec_info[0];
-    const StreamTiling tl = make_tiling(h.n_bytes, first_nl, h.K, h.ranges);
+    const StreamTiling tl = make_tiling(h.n_bytes, first_nl, h.K, h.ranges, h.geom);
     const u32 w = blockIdx.x / h.split, sp = blockIdx.x % h.split;
     const u64 B = (u64)w * tl.range_bytes;
     const u64 E = (B + tl.range_bytes < h.n_bytes) ? B + tl.range_bytes : h.n_bytes;
@@ -788,9 +796,308 @@ __global__ __launch_bounds__(P0_BLOCK, 4) void stream_pass0_kernel(P0Args a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// the wide pass (variant 1): one 1024-thread workgroup per CU, tiles of 8192 windows, whole 128-byte units
+// ---------------------------------------------------------------------------------------
+// A digit's left-over keys (fewer than G) are not parked again with the next tile.  They wait in a carry area of G - 1 slots of
+// their own, and the digit's first unit of the next tile reads its first keys from there and the rest from the tile's parked run:
+// each lane picks its source slot with a select.  Only what is left after a tile is copied into the carry area, and waves 8-15 do
+// that while waves 0-7 (one digit per thread) scan the counters.
+template <int RBITS, int G>
+struct P0WideSmem {
+    static constexpr int RADIX = 1 << RBITS, CARRY = G - 1;
+    static constexpr int DEAD = PW_TILE, CB = PW_TILE + 64;          // one dead slot per lane, then the carry areas
+    static constexpr int SLOTS = CB + RADIX * CARRY;
+    static constexpr int UNITS = (PW_TILE + RADIX * CARRY) / G + 2 * RADIX;
+    u64 exch[SLOTS];               // the tile, grouped by digit; the dead slots; digit d's carry at CB + CARRY * d
+    u64 gbase[RADIX];              // output index of the digit's key named by unit slot 0 (parked slot -16), as seen by this digit
+    u32 units[UNITS];              // what leaves with this tile: unit_pack(16 + parked slot of its first key, keys, digit) | carried keys << 27
+    u32 codes[PW_IMG_WORDS], valid[PW_IMG_WORDS];          // the 2-bit image of the tile whose keys are made next
+    alignas(16) u32 cnt[RADIX + 64];          // this tile's keys of the digit (+ 64 for the dead)
+    u32 mv[RADIX];                 // what the last tile left of the digit: parked slot | carry slot << 14 | keys << 18
+    u16 off[RADIX];                // where the digit's keys of this tile start in exch
+    alignas(16) u16 nu[RADIX];     // units of the digit
+    u32 nunits;
+    u32 anybad;                    // some digit has more keys than its piece holds (the histogram and the pass disagree): no further stores
+};
+
+// Waves 0-7 own one digit per thread (its output cursor, where its piece ends, its carried keys are that thread's registers) and do
+// the two scans; waves 8-15 copy the last tile's left-overs into the carry areas meanwhile and wait only at the barrier after it.
+// Per tile: keys + ranks | barrier | scan of the counters (0-7), carry copy (8-15) | barrier | scan of the unit counts and the unit
+// list (0-7), park (all), next image | barrier | units out.  The next tile's key phase reads only its image and adds to counters
+// that the scans left at zero, so three barriers a tile (the 512-thread kernel has five per 4096 windows).
+template <int RBITS, bool CANON, bool FAST>
+__global__ __launch_bounds__(PW_BLOCK) void stream_pass0_wide_kernel(P0Args a) {
+    constexpr int G = 16;
+    using S = P0WideSmem<RBITS, G>;
+    constexpr int RADIX = S::RADIX, NW = PW_NW, BLOCK = PW_BLOCK;
+    static_assert(2 * RADIX == BLOCK, "one digit per thread of waves 0-7");
+    static_assert(S::SLOTS < (1 << 14) && S::CARRY < 16 && RBITS <= 9, "unit words");
+    static_assert(sizeof(S) <= 160 * 1024, "LDS of a CU");
+    __shared__ S sm;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool owner = wave < RADIX / 64;          // (wave-uniform) a digit's thread
+    const u32 w = blockIdx.x;
+    const bool rev = !CANON && w >= a.ranges;
+    const u32 radix = 1u << a.bits;
+    const u64 B = (u64)(rev ? w - a.ranges : w) * a.tl.range_bytes;
+    if (B >= a.n_bytes) return;
+    const u64 E = (B + a.tl.range_bytes < a.n_bytes) ? B + a.tl.range_bytes : a.n_bytes;
+    const u32 tile_bytes = a.by_record ? a.tl.tile_bytes : (u32)PW_TILE;
+    const u32 ntile = (u32)((E - B + tile_bytes - 1) / tile_bytes);
+    const u32 nch = tile_bytes / 16 + 3;
+    const int K = a.K;
+    const u64 mask = ~0ull >> (64 - 2 * K);
+    const u32 mlo = (u32)mask, mhi = (u32)(mask >> 32);
+    const u32 dmask = radix - 1u;
+    const u32 nchunks = (u32)((a.n_bytes + 15) >> 4);
+    auto digit = [&](u64 k) -> u32 {
+        if constexpr (FAST) return __builtin_amdgcn_ubfe((u32)(k >> 32), (u32)a.shift - 32u, (u32)a.bits);
+        else return (u32)(k >> a.shift) & dmask;
+    };
+    // the digit of this thread (waves 0-7)
+    const bool mine = owner && (u32)tid < radix;
+    u64 F = mine ? a.offs[(u64)w * radix + tid] : 0ull;
+    const u64 Fend = F + (mine ? a.rows[(u64)w * radix + tid] : 0u);
+    u32 r = 0;                     // keys carried over from the last tile
+    u32 bad = 0;
+    u32 flen_dbg = 0;
+    if (tid < RADIX + 64) sm.cnt[tid] = 0;
+    if (owner) sm.mv[tid] = 0;
+    if (tid == 0) { sm.anybad = 0; sm.units[0] = 0; }
+    u32 p0 = (u32)NW * tid, wlim = (1u << NW) - 1u;
+    if (a.by_record) {
+        const u32 rr = (u32)(((u64)tid * a.tl.cpr_inv) >> 32), j = tid - rr * a.tl.cpr;
+        p0 = rr * a.tl.rec + (u32)NW * j;
+        const int left = (int)a.tl.wpr - NW * (int)j;
+        wlim = (rr < a.tl.rpt) ? ((left >= NW) ? (1u << NW) - 1u : ((1u << (left > 0 ? left : 0)) - 1u)) : 0u;
+        if (rr >= a.tl.rpt) p0 = 0;
+    }
+    // as in the 512-thread kernel: the image of tile t + 1 is made, and the bytes of tile t + 2 asked for, before tile t's stores
+    u32 qc = 0, qv = 0;
+    auto fetch = [&](u64 T) {
+        const u64 idx = (T >> 4) + (u32)tid;
+        const bool in = (u32)tid < nch && idx < nchunks;
+        qc = in ? a.gcodes[idx] : 0u;
+        qv = in ? (u32)a.gvalid[idx] : 0u;
+    };
+    fetch(B);
+    if ((u32)tid < nch) { sm.codes[tid] = qc; sm.valid[tid] = qv; }
+    if (ntile > 1) fetch(B + tile_bytes);
+    __syncthreads();
+    u32 ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    u32 tlast = a.dbg ? (u32)__builtin_amdgcn_s_memtime() : 0;
+    (void)tlast;
+    // Units [0, end): G / 2 = 8 lanes per unit, two keys (16 bytes) per lane, so one store instruction of a wave writes eight whole
+    // 128-byte lines.  A unit's first `carried` keys sit in the digit's carry area, the rest in the tile's parked run.
+    struct __attribute__((packed, aligned(8))) Key2 { u64 a, b; };
+    auto store_units = [&](u32 end) {
+        constexpr int NF = 2;
+        constexpr u32 LPU = G / 2, GROUPS = BLOCK / LPU;
+        const u32 j = 2u * ((u32)tid & (LPU - 1)), g0 = (u32)tid / LPU;
+        for (u32 base = 0; base < end; base += NF * GROUPS) {
+            u32 e4[NF];
+            u64 k4[NF], l4[NF], b4[NF];
+#pragma unroll
+            for (int g = 0; g < NF; g++) {
+                const u32 u = base + g * GROUPS + g0;
+                e4[g] = sm.units[u < end ? u : 0u];
+            }
+#pragma unroll
+            for (int g = 0; g < NF; g++) asm volatile("" : "+v"(e4[g]));
+#pragma unroll
+            for (int g = 0; g < NF; g++) {
+                const u32 d = (e4[g] >> 18) & (u32)(RADIX - 1), kc = e4[g] >> 27;
+                const u32 cs = (u32)S::CB + (u32)S::CARRY * d, ps = (e4[g] & 0x3fffu) - 16u;          // (the parked slot is biased by 16)
+                k4[g] = sm.exch[j < kc ? cs + j : ps + j];
+                l4[g] = sm.exch[j + 1 < kc ? cs + j + 1 : ps + j + 1];
+                b4[g] = sm.gbase[d];
+            }
+#pragma unroll
+            for (int g = 0; g < NF; g++) asm volatile("" : "+v"(k4[g]), "+v"(l4[g]), "+v"(b4[g]));
+#pragma unroll
+            for (int g = 0; g < NF; g++) {
+                const u32 u = base + g * GROUPS + g0;
+                const u32 len1 = (e4[g] >> 14) & 15u;
+                u64* dst = a.kout + (b4[g] + (e4[g] & 0x3fffu) + j);          // (inside the digit's piece by construction)
+                const bool fits = P0_MODE != 2 || b4[g] + (e4[g] & 0x3fffu) + G <= a.n;          // (measurement mode 2 runs past the pieces)
+                if (u < end && P0_MODE != 1 && fits) {
+                    if (j < len1) { Key2 v; v.a = k4[g]; v.b = l4[g]; *reinterpret_cast<Key2*>(dst) = v; }
+                    else if (j == len1) *dst = k4[g];
+                }
+            }
+        }
+    };
+    for (u32 t = 0; t < ntile; t++) {
+        const u64 T0 = B + (u64)t * tile_bytes;
+        const bool last = t + 1 == ntile;
+        if (P0_MODE == 2 && t > 1) {
+            __syncthreads();
+            if (owner) sm.gbase[tid] += flen_dbg;
+            __syncthreads();
+        } else {
+        // ---- this thread's keys, ranked by the digit's counter ------------------------------------------
+        u64 key[NW];
+        u32 live;
+        {
+            const u32 j = p0 >> 4, s = p0 & 15u;
+            const u64 sa = ((u64)sm.codes[j] << 32) | sm.codes[j + 1];
+            const u64 sb = ((u64)sm.codes[j + 2] << 32) | sm.codes[j + 3];
+            u64 v = ((u64)sm.valid[j] << 48) | ((u64)sm.valid[j + 1] << 32) | ((u64)sm.valid[j + 2] << 16) | (u64)sm.valid[j + 3];
+            v = runs_of_k(v, K);
+            live = (__brev((u32)((v << s) >> (64 - NW))) >> (32 - NW)) & wlim;
+            if (T0 + p0 >= E) live = 0;
+            WindowWords<NW> ww;
+            ww.init(sa, sb, s, K);
+#pragma unroll
+            for (int i = 0; i < NW; i++) {
+                const u64 x = ((u64)(ww.xhi(i) & mhi) << 32) | (FAST ? ww.xlo(i) : (ww.xlo(i) & mlo));
+                const u64 xb = ((u64)(ww.bhi(i) & mhi) << 32) | (FAST ? ww.blo(i) : (ww.blo(i) & mlo));
+                if constexpr (CANON) key[i] = x < xb ? x : xb;
+                else key[i] = rev ? xb : x;
+            }
+        }
+        u32 rk[NW];
+#pragma unroll
+        for (int i = 0; i < NW; i++) rk[i] = atomicAdd(&sm.cnt[((live >> i) & 1u) ? digit(key[i]) : (u32)RADIX + (u32)lane], 1u);
+        P0_PHASE(0);          // keys made, ranks asked for
+        __syncthreads();
+        P0_PHASE(1);          // ... waiting for the other waves
+        u32 O = 0, tot = 0, flen = 0, head = 0, nu = 0, c = 0;
+        if (owner) {
+            // ---- per digit: how many keys leave now (every wave adds up all the counters by itself) -----------------------
+            const uint4 c0 = reinterpret_cast<const uint4*>(sm.cnt)[2 * lane], c1 = reinterpret_cast<const uint4*>(sm.cnt)[2 * lane + 1];
+            const u32 s8 = c0.x + c0.y + c0.z + c0.w + c1.x + c1.y + c1.z + c1.w;
+            const u32 inc8 = wave_incl_scan_dpp(s8);
+            const u32 before = wave ? (u32)__builtin_amdgcn_readlane((int)inc8, 8 * wave - 1) : 0u;
+            c = sm.cnt[tid];
+            const u32 inc = wave_incl_scan_dpp(c);
+            O = before + inc - c;          // the tile's keys of the digit are parked at O ..
+            tot = r + c;                   // ... behind the r it carries
+            u64 end = F + tot;
+            if (end > Fend) { bad = 1; sm.anybad = 1; end = Fend > F ? Fend : F; }
+            u64 Eo = last ? end : (end & ~(u64)(G - 1));
+            if (Eo < F) Eo = F;
+            flen = (u32)(Eo - F);
+            head = (u32)(F & (G - 1)) ? G - (u32)(F & (G - 1)) : 0u;
+            if (head > flen) head = flen;
+            nu = (head ? 1u : 0u) + (flen - head + G - 1) / G;
+            sm.off[tid] = (u16)O;
+            sm.nu[tid] = (u16)nu;
+        } else {
+            // ---- the last tile's left-overs into the carry areas: 8 lanes per digit, two keys each -------------------------
+            // (no branch around an LDS access: a lane with nothing to move reads and writes its lane's dead slot)
+            const u32 q = (u32)tid - (u32)RADIX, j = 2u * (q & 7u);
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                u32 m4[4], d4[4];
+                u64 v4[4], x4[4];
+#pragma unroll
+                for (int g = 0; g < 4; g++) { d4[g] = (u32)(4 * h + g) * (RADIX / 8) + (q >> 3); m4[g] = sm.mv[d4[g]]; }
+#pragma unroll
+                for (int g = 0; g < 4; g++) asm volatile("" : "+v"(m4[g]));
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const u32 n = m4[g] >> 18, src = m4[g] & 0x3fffu;
+                    v4[g] = sm.exch[j < n ? src + j : (u32)S::DEAD + (u32)lane];
+                    x4[g] = sm.exch[j + 1 < n ? src + j + 1 : (u32)S::DEAD + (u32)lane];
+                }
+#pragma unroll
+                for (int g = 0; g < 4; g++) asm volatile("" : "+v"(v4[g]), "+v"(x4[g]));
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const u32 n = m4[g] >> 18, dst = (u32)S::CB + (u32)S::CARRY * d4[g] + ((m4[g] >> 14) & 15u);
+                    sm.exch[j < n ? dst + j : (u32)S::DEAD + (u32)lane] = v4[g];
+                    sm.exch[j + 1 < n ? dst + j + 1 : (u32)S::DEAD + (u32)lane] = x4[g];
+                }
+            }
+        }
+        P0_PHASE(2);          // scan of the counters / carry copy
+        __syncthreads();
+        P0_PHASE(3);          // ... waiting
+        if (owner) {
+            // ---- the unit list --------------------------------------------------------------------------------------
+            const uint4 c0 = reinterpret_cast<const uint4*>(sm.nu)[lane];
+            const u32 s2 = c0.x + c0.y + c0.z + c0.w;
+            const u32 s8 = (s2 & 0xffffu) + (s2 >> 16);
+            const u32 inc8 = wave_incl_scan_dpp(s8);
+            const u32 before = wave ? (u32)__builtin_amdgcn_readlane((int)inc8, 8 * wave - 1) : 0u;
+            const u32 inc = wave_incl_scan_dpp(nu);
+            u32 U = before + inc - nu;
+            if (tid == 0) sm.nunits = (u32)__builtin_amdgcn_readlane((int)inc8, 63);
+            // Digit key i of this tile (i < tot) goes to output index F + i; it is carry slot i while i < r, else parked slot
+            // O - r + i.  Every unit but the digit's first starts at or after r (a digit that emits anything emits all it carries:
+            // its r keys did not reach its next grid line); the first takes min(r, its length) keys from the carry area.  A unit
+            // names the parked slot of its first key as if it were parked, + 16 so that O - r + i never goes below 0.
+            sm.gbase[tid] = F + r - O - 16u;          // (modulo 2^64: + the unit's slot is F + i)
+            flen_dbg = flen;
+            const u32 ps = O + 16u - r;
+            u32 i = 0, left = flen;
+            if (head) {
+                const u32 kc = r < head ? r : head;
+                if (U < (u32)S::UNITS) sm.units[U] = unit_pack(ps + i, head, (u32)tid) | (kc << 27);
+                U++; i += head; left -= head;
+            }
+            while (left) {
+                const u32 len = left < (u32)G ? left : (u32)G;
+                const u32 kc = i < r ? (r - i < len ? r - i : len) : 0u;
+                if (U < (u32)S::UNITS) sm.units[U] = unit_pack(ps + i, len, (u32)tid) | (kc << 27);
+                U++; i += len; left -= len;
+            }
+            // what is left for the next tile: keys flen .. tot - 1 of this tile, into carry slots from 0 on (the carried ones all
+            // left: flen >= r), or, when nothing leaves, the tile's keys behind the carried ones
+            const u32 keep = tot - flen;
+            u32 src = O, dsto = r, n = c;
+            if (flen && flen >= r) { src = O + flen - r; dsto = 0; n = keep; }
+            if (dsto > (u32)S::CARRY) dsto = S::CARRY;
+            if (n > (u32)S::CARRY - dsto) n = (u32)S::CARRY - dsto;          // (only when `bad`: the launch reports ZK_DERR_MISMATCH)
+            sm.mv[tid] = src | (dsto << 14) | (n << 18);
+            r = keep < (u32)S::CARRY ? keep : (u32)S::CARRY;
+            sm.cnt[tid] = 0;
+            F += flen;
+        }
+        // ---- park ----------------------------------------------------------------------------------
+        {
+            u32 at[NW];
+#pragma unroll
+            for (int i = 0; i < NW; i++) at[i] = sm.off[digit(key[i])];
+            // (at + rank < the tile's keys <= PW_TILE: inside the parked run)
+#pragma unroll
+            for (int i = 0; i < NW; i++) sm.exch[((live >> i) & 1u) ? at[i] + rk[i] : (u32)S::DEAD + (u32)lane] = key[i];
+        }
+        // ---- the next tile's image; the bytes of the tile after it ------------------------------------------
+        if (!last) {
+            if ((u32)tid < nch) { sm.codes[tid] = qc; sm.valid[tid] = qv; }
+            if (t + 2 < ntile) fetch(T0 + 2ull * tile_bytes);
+        }
+        P0_PHASE(4);          // unit list, park, next image (includes the wait for its bytes)
+        __syncthreads();
+        P0_PHASE(5);          // ... waiting
+        }
+        // ---- whole units out ---------------------------------------------------------------------------
+        {
+            const u32 nunits = (sm.anybad || sm.nunits > (u32)S::UNITS) ? 0u : sm.nunits;          // (after `bad` nothing leaves)
+            store_units(nunits);
+        }
+        P0_PHASE(6);          // stores issued
+    }
+    if (a.dbg && tid == 0) {
+        for (int k = 0; k < 8; k++) a.dbg[(u64)w * 16 + k] = (u64)ph[k];
+        a.dbg[(u64)w * 16 + 8] = ntile;
+    }
+    if (P0_MODE) return;
+    if (bad || (mine && (F != Fend || r != 0))) atomicOr(a.err, ZK_DERR_MISMATCH);
+}
+
+// ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-int stream_ranges(zk_ctx* c) { return c->stream_ranges > 0 ? c->stream_ranges : 2 * (c->num_cus > 0 ? c->num_cus : 1); }
+// Which form of the pass runs, decided here once for the histogram kernel (it cuts the ranges and counts their rows for it) and
+// recorded in StreamRows for the pass: variant 1 (the default) is the wide kernel, 2 and 3 the 512-thread kernel.  The tag pass
+// (ZK_TUNE_TAG_PASS, off by default) has pass 0 write two arrays, which only the 512-thread kernel does: it stays there.
+static bool p0_wide(const zk_ctx* c) { return (c->stream_pass & 0xff) == 1 && !c->tag_pass; }
+
+// one range per workgroup: one per CU for the wide kernel, two for the 512-thread one (ZK_KEYS_BOTH doubles the grid)
+int stream_ranges(zk_ctx* c, bool wide) { return c->stream_ranges > 0 ? c->stream_ranges : (wide ? 1 : 2) * (c->num_cus > 0 ? c->num_cus : 1); }
 
 // histogram of every pass's digit + acgt + the uniformity check + (optionally) the set-aside blocks, and pass 0's digit counts per
 // range.  ghist: [MAX_PASSES][gstride] (zeroed here; exclusive prefixes on return, the key count in *d_n).
@@ -811,8 +1118,10 @@ int stream_hist(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, int mode, 
     h.ghist = ghist; h.gstride = gstride;
     h.acgt = d_acgt; h.rec_info = rec_info;
     h.sample = sample; h.sample_n = sample_n; h.sample_cap = sample_cap; h.sample_shift = sample_shift; h.sample_value = sample_value;
-    h.ranges = (u32)stream_ranges(c);
-    h.split = 4;
+    const bool wide = p0_wide(c);
+    h.geom = p0_geom(wide);
+    h.ranges = (u32)stream_ranges(c, wide);
+    h.split = wide ? 8 : 4;          // (the same grid for both forms: half as many ranges, each read by twice as many workgroups)
     h.dbg_atomics = 2;
 #ifdef ZK_PHASES
     if (const char* e = getenv("ZK_HIST_ATOMICS")) h.dbg_atomics = atoi(e);
@@ -844,6 +1153,7 @@ int stream_hist(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, int mode, 
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     out->rows = rows; out->offs = offs; out->ranges = h.ranges; out->strands = strands; out->radix = r0; out->gcodes = h.gcodes; out->gvalid = h.gvalid;
+    out->wide = wide;
     return ZK_OK;
 }
 
@@ -856,14 +1166,14 @@ int stream_pass0(zk_ctx* c, uint64_t n_bytes, int K, int mode, int shift, int bi
     hipLaunchKernelGGL(rows_scan_kernel, dim3((rows.radix + 255) / 256), dim3(256), 0, c->stream, rows.rows, ghist0, grid, rows.radix, rows.offs);
     P0Args a = {};
     a.gcodes = rows.gcodes; a.gvalid = rows.gvalid; a.n_bytes = n_bytes; a.K = K;
-    a.tl = make_tiling(n_bytes, first_nl, K, rows.ranges);
+    a.tl = make_tiling(n_bytes, first_nl, K, rows.ranges, p0_geom(rows.wide));
     a.ranges = rows.ranges;
     a.by_record = (uniform && a.tl.rec) ? 1 : 0;
     a.shift = shift; a.bits = bits; a.offs = rows.offs; a.rows = rows.rows; a.kout = kout; a.n = n; a.err = c->d_err; a.dbg = c->dbg; a.dbg_mode = variant >> 8; a.split_stores = (variant & 0xff) == 3;          // measured: 10.05 vs 8.73 ms on 20 M reads -- the held-back half sits in the key phase's way
     const bool canon = mode == ZK_KEYS_CANONICAL, fast = 2 * K > 32 && shift >= 32;
     if (planes) {
         // two arrays instead of whole keys (the next pass reads them: stream_pass1): only the usual plan asks for it
-        if (!canon || !fast) return fail(c, ZK_EINTERNAL, "stream_pass0: planes need the canonical fast plan");
+        if (!canon || !fast || rows.wide) return fail(c, ZK_EINTERNAL, "stream_pass0: planes need the canonical fast plan and the 512-thread kernel");
         a.dig_out = planes->dig; a.dig_shift = planes->shift; a.dig_mask = (1u << planes->bits) - 1u;
         prof_begin(c, ZK_PROF_PASS_STREAM, n_bytes + 6 * n);
         hipLaunchKernelGGL((stream_pass0_kernel<9, 8, true, true, true>), dim3(rows.ranges), dim3(P0_BLOCK), 0, c->stream, a);
@@ -872,7 +1182,12 @@ int stream_pass0(zk_ctx* c, uint64_t n_bytes, int K, int mode, int shift, int bi
         return ZK_OK;
     }
     prof_begin(c, ZK_PROF_PASS_STREAM, n_bytes + 8 * n);
-    if (canon && fast) hipLaunchKernelGGL((stream_pass0_kernel<9, 8, true, true>), dim3(grid), dim3(P0_BLOCK), 0, c->stream, a);
+    if (rows.wide) {
+        if (canon && fast) hipLaunchKernelGGL((stream_pass0_wide_kernel<9, true, true>), dim3(grid), dim3(PW_BLOCK), 0, c->stream, a);
+        else if (canon) hipLaunchKernelGGL((stream_pass0_wide_kernel<9, true, false>), dim3(grid), dim3(PW_BLOCK), 0, c->stream, a);
+        else if (fast) hipLaunchKernelGGL((stream_pass0_wide_kernel<9, false, true>), dim3(grid), dim3(PW_BLOCK), 0, c->stream, a);
+        else hipLaunchKernelGGL((stream_pass0_wide_kernel<9, false, false>), dim3(grid), dim3(PW_BLOCK), 0, c->stream, a);
+    } else if (canon && fast) hipLaunchKernelGGL((stream_pass0_kernel<9, 8, true, true>), dim3(grid), dim3(P0_BLOCK), 0, c->stream, a);
     else if (canon) hipLaunchKernelGGL((stream_pass0_kernel<9, 8, true, false>), dim3(grid), dim3(P0_BLOCK), 0, c->stream, a);
     else if (fast) hipLaunchKernelGGL((stream_pass0_kernel<9, 8, false, true>), dim3(grid), dim3(P0_BLOCK), 0, c->stream, a);
     else hipLaunchKernelGGL((stream_pass0_kernel<9, 8, false, false>), dim3(grid), dim3(P0_BLOCK), 0, c->stream, a);
