@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """
-bench.py -- `zot kmerize` K=25 on synthetic 150 bp reads, the metric of BASELINE.json, plus the other single-GPU
-configurations as `extra` blocks of the same JSON line.
+bench.py -- `zot kmerize` K=25 on synthetic 150 bp reads, the metric of BASELINE.json; with `--full` also the checks of the
+timed result, the other single-GPU configurations as `extra` blocks of the same JSON line and the CPU baselines.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes the outputs when asked and prints
+the line.  `--full` adds everything else below: the verification of the timed result, `roofline.peak_measured`, the `extra`
+blocks and `cpu_baseline`; `--no-verify`, `--no-extras` and `--no-cpu-baseline` leave parts of it out again, and `--verify`
+alone adds the verification to a plain run.
 
 Headline.  A step is one whole kmerize of the batch: base stream resident in HBM -> sorted distinct k-mers of both
 strands + counts in HBM (hist and acgt included), i.e. zk_kmerize + zk_hist through the C-ABI.  At N = 1 the workload
@@ -17,16 +22,17 @@ second of wall time over the timed steps.  `roofline` is whichever of the two fu
 -- the array pass (8 B/key read + the 4-byte tag written) or pass 0 from the base stream (1 B/stream byte + 8 B/key) -- its
 algorithmic bytes over its mean launch time by HIP events on the library's own stream, the other and the block dedupe listed
 beside it (`others`); `peak` is the 8 TB/s of the spec,
-`peak_measured` what a device-to-device copy reaches on this box in this run.  The result of the last timed step is
-verified outside the timed region: order-free checksums of the table against the same sums taken straight from the base
-stream by an independent encoder, and strict ascent of the k-mers (`verified_checksums`, `verified_ascending`).  `cpu_baseline`: the C oracle on one core on a prefix of the same
-reads, and the pure-Python restatement of the reference path on BASELINE config 1.
+`peak_measured` (`--full`) what a device-to-device copy reaches on this box in this run.  With `--full` the result of the last
+timed step is verified outside the timed region: order-free checksums of the table against the same sums taken straight from
+the base stream by an independent encoder, and strict ascent of the k-mers (`verified_checksums`, `verified_ascending`; null
+in a plain run).  `cpu_baseline` (`--full`): the C oracle on one core on a prefix of the same reads, and the pure-Python
+restatement of the reference path on BASELINE config 1.
 
 `--dump-outputs DIR` writes what the last timed step returned (dump_outputs: a seeded sample of the sorted table, the whole
 histogram, the stats and the table's checksums) as float64 .npy files; the inputs are fixed by the seed, so two builds compare
 output for output.
 
-`extra` (N = 1): config 3 (`zot dist` on two 100 M-k-mer sets), one GPU's share of config 4 (merge of 8 x 50 M-k-mer
+`extra` (`--full`; N = 1): config 3 (`zot dist` on two 100 M-k-mer sets), one GPU's share of config 4 (merge of 8 x 50 M-k-mer
 sets), one GPU's share of config 5 (K = 31, 37.5 M reads), config 2 again with the base stream starting in pinned
 host memory (H2D inside the timed region), and the two inputs the headline does not cover: reads without repeats
 (SURVEY 8(d)'s uniform workload) and reads of varying length.  N > 1: `zot merge` (8 sets per GPU, config 4 at N = 8) and `zot dist`
@@ -642,17 +648,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU (default: config 2 = 50 M)")
     ap.add_argument("--both", action="store_true", help="sort both strands literally instead of canonical + mirror")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the checksum verification of the timed result")
-    ap.add_argument("--verify", action="store_true", help="(default; kept for round-1 command lines)")
-    ap.add_argument("--no-extras", action="store_true", help="headline only")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the timed result, measure the copy peak, run the extra blocks and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-verify", action="store_true", help="--full without the verification of the timed result and the copy peak")
+    ap.add_argument("--verify", action="store_true", help="verify the timed result (implied by --full)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extra blocks")
     ap.add_argument("--extras-scale", type=float, default=1.0, help="shrink the extra workloads (tests)")
-    ap.add_argument("--only-extra", default="", help="run just this extra block (development): skips the headline")
+    ap.add_argument("--only-extra", default="", help="run just this extra block (development): skips the headline, needs no --full")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="write what the last timed step computed to DIR/<name>.npy (float64; per rank as <name>_rank<r>.npy when N > 1)")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    do_verify = (a.full or a.verify) and not a.no_verify
+    do_extras = a.full and not a.no_extras
+    do_cpu_baseline = a.full and not a.no_cpu_baseline
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -780,7 +791,7 @@ def main():
         total_instances = st.n_instances
 
     verify, ascending = None, None
-    if not a.no_verify:
+    if do_verify:
         want = ctx.stream_checksum(stream, K)
         if par is None:
             verify = bool(ctx.checksum(k, c) == want)
@@ -792,10 +803,10 @@ def main():
             ascending = bool(par.comm.all_reduce([0 if ascending else 1])[0] == 0)
     if a.dump_outputs:          # before the extras, which reuse the output buffers
         dump_outputs(a.dump_outputs, "_rank%d" % rank if world > 1 else "", k, c, st, h, ctx.checksum_counts(k, c), seed + rank, K)
-    peak_measured = copy_peak(ctx) if rank == 0 and not a.no_verify else None          # (not in profiled runs)
+    peak_measured = copy_peak(ctx) if rank == 0 and a.full and not a.no_verify else None          # (not in profiled runs)
 
     extras = {}
-    if not a.no_extras:
+    if do_extras:
         sc = a.extras_scale
         if par is None:
             del k, c
@@ -884,7 +895,7 @@ def main():
                 others.append(o)
         out = {
             "metric": "Gk-mers/sec kmerize k=25 on synthetic 150bp FASTQ; achieved HBM GB/s fraction",
-            "value": value, "unit": "Gk-mers/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "value": value, "unit": "Gk-mers/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "full": a.full,
             "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u64", "data": "synthetic",
             "config": {"workload": "zot kmerize k=%d, %d x %dbp genome-sampled synthetic reads per GPU (BASELINE config 2), "
@@ -927,9 +938,9 @@ def main():
             out["balance_max_over_mean"] = max(owned) / (sum(owned) / float(len(owned)))
         if comm_note:
             out["comm_note"] = comm_note
-        if not a.no_cpu_baseline and world == 1:
+        if do_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, seed)
-        elif not a.no_cpu_baseline:
+        elif do_cpu_baseline:
             out["cpu_baseline"] = None
         sys.stdout.flush()
         os.dup2(real_stdout, 1)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collect the round's rocprofv3 evidence on the GPU box (run through gpurun from the repo root):
-#   1. the plain bench line (with extras and CPU baselines)           -> gpurun_out/prof/bench_line.json
+#   1. the full bench line (bench.py --full: extras and CPU baselines) -> $OUT/bench_line.json
 #   2. kernel trace + stats of the headline command                  -> gpurun_out/prof/stats/
 #   3. two PMC passes (FETCH_SIZE, WRITE_SIZE) of the same command   -> gpurun_out/prof/pmc_f, pmc_w -> pmc_traffic.json
 # Counters are collected in their own runs with --kernel-trace only (never with the sys/hip/hsa trace domains).
@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof
 rm -rf "$OUT"; mkdir -p "$OUT"
 CMD="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-verify"
-timeout -k 10 500 python3 bench.py > "$OUT/bench_line.json" 2> "$OUT/bench_line.err" || { echo "bench failed"; tail -5 "$OUT/bench_line.err"; exit 1; }
+timeout -k 10 500 python3 bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench_line.err" || { echo "bench failed"; tail -5 "$OUT/bench_line.err"; exit 1; }
 echo "bench line ok"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 $CMD > "$OUT/bench_line_under_rocprof.json" 2> "$OUT/stats.err" || { echo "stats run failed"; tail -5 "$OUT/stats.err"; exit 1; }
 echo "stats ok"
