@@ -103,6 +103,10 @@ int zk_upload_async(zk_ctx* ctx, void* d_dst, const void* src, uint64_t bytes);
 #define ZK_TUNE_TILE_SORT 19     /* sorts of keys that do not repeat (zk_sort_keys, zk_kmerize on such reads): 1 (default) = LSD passes over the top bits
                                   * only, until blocks of equal top bits are a few dozen keys, then every tile of ~6 K keys sorted to the end in LDS
                                   * (tilesort.hip); 0 = LSD passes over every bit */
+#define ZK_TUNE_STRAND_BLOCKS 20  /* zk_kmerize, block dedupe with 18 block bits at odd K, both strands wanted: 1 (default) = the table is rebuilt block
+                                  * by block -- the mirror words grouped by their top 18 bits in two passes, each block's two lists sorted in LDS and
+                                  * written to a place known in advance (strand_blocks.hip); 0 = the mirror words sorted on 26 bits in three passes
+                                  * and merged with the counted list by the merge-path union */
 #define ZK_TUNE_COMM_SELF_LOOP 16 /* tests: 1 = the piece a rank keeps goes through grouped ncclSend / ncclRecv to itself, in the same rounds as
                                   * the other pieces (instead of a device copy), and zk_allreduce_u64 calls ncclAllReduce with one rank too:
                                   * the RCCL data path of zk_comm_* executed on a box with one GPU; 0 (default) */

@@ -41,6 +41,7 @@ struct zk_ctx {
     int kway = 1;              // zk_merge_n: 1 = up to 16 lists per pass (kway.hip) from 4 Mi pairs on, 2 = always, 0 = the tree of 2-way passes
     int tile_sort = 1;         // sorts of keys that do not repeat: LSD passes over the top bits, then tiles sorted to the end in LDS (tilesort.hip)
     int dedupe_bits = 0;       // tests: > 0 = the block dedupe with this many block bits whatever the input's size (pipeline.hip)
+    int strand_blocks = 1;     // zk_kmerize, block dedupe at odd K: both strands rebuilt block by block (strand_blocks.hip); 0 = mirror sort + merge-path union
     int stream_ranges = 0;     // ... ranges the stream is cut into (0 = one per CU for variant 1, two for 2 and 3; tests use a few so that a range has many tiles)
 
     // workspace arena: a bump allocator reset at the start of every API call
@@ -176,6 +177,9 @@ int expand_tags(zk_ctx* c, const u32* tags, const u64* cuts, uint32_t blocks, in
 int dedupe_finish(zk_ctx* c, const DedupeResult& r, u64* out_k, u32* out_c, u64* out_m = nullptr, int K = 0, int gbases = 0,
                   u64** mirror_hist = nullptr, int* mirror_group_bits = nullptr, bool packed_out = false);
 int sort_keys_upper_counted(zk_ctx* c, u64* keys, u64* alt, uint64_t n, int key_bits, int lo_bit, u64* counted, u64** result);
+// strand_blocks.hip: both strands of the block dedupe's counted list at odd K, block by block (keys_buf: buf_words free words)
+int strand_blocks(zk_ctx* c, const DedupeResult& r, u64* keys_buf, uint64_t buf_words, int K, u64* out_k, u32* out_c, uint64_t cap,
+                  uint64_t* n_out);
 int collapse_pass(zk_ctx* c, const u64* keys, uint64_t n, int shift, int bits, int pack, u64* out, uint64_t cap, uint64_t* n_out,
                   uint64_t max_tiles = 0);
 int sort_stream(zk_ctx* c, const StreamSrc& src, u64* buf_a, u64* buf_b, uint64_t cap, uint64_t* n_keys,

@@ -435,13 +435,19 @@ static int kmerize_full(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, bo
             if (!(r.flags & 1)) {
                 uc = r.n_out;
                 const uint64_t a8 = (8 * uc + 255) & ~255ull, a4 = (4 * uc + 255) & ~255ull;
-                char* aux;
-                ZK_TRY(aux_require(c, a8 + a4, &aux));
                 // Every count fits the field (the usual case) and both strands are wanted: the copy that closes the gaps also
                 // writes the mirrored words grouped by their low 18 bits -- the first stage of the mirror sort (mirror_union's
                 // grouping copy) for free; they go over the keys' buffer (the keys are counted, the words are in the other one).
                 const bool want_m = !(r.flags & 2) && !canonical_only && c->packed_pairs && dedupe_bit == MIRROR_GROUP_BITS &&
                                     2 * K >= MIRROR_GROUP_BITS + 8;
+                // ... at odd K (the two strands share no key) without the dense copy and the full mirror sort: block by block, the
+                // counted list read where the dedupe left it (strand_blocks.hip)
+                if (want_m && (K & 1) && c->strand_blocks && 2 * a8 <= 8 * cap_keys) {
+                    st->n_canonical = uc;
+                    return strand_blocks(c, r, sorted, cap_keys, K, out_k, out_c, cap, n_out);
+                }
+                char* aux;
+                ZK_TRY(aux_require(c, a8 + a4, &aux));
                 // ... and the counted list itself stays in words, (k-mer << pk) | count: nobody but the final union reads it
                 ZK_TRY(dedupe_finish(c, r, (u64*)aux, (u32*)(aux + a8), want_m ? sorted : nullptr, K, MIRROR_GROUP_BASES, &mhist, &mgroup, want_m));
                 if (want_m) { mwords = sorted; malt = other; canon_packed = true; }

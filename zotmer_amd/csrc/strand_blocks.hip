@@ -1,0 +1,362 @@
+// strand_blocks.hip -- both strands of a counted canonical list, rebuilt block by block (odd K).
+//
+// The block dedupe (dedupe2.hip) leaves the counted canonical list C as (k-mer << pack | count) words, cut into 2^18 blocks by the
+// k-mer's first nine bases, each block sorted, block v at work + cuts[v] (nwords[v] words; its place in the dense list starts at
+// incl[v] - nwords[v]).  The table of both strands is C together with its mirror image M = rc(C), sorted.  At odd K no k-mer is its own
+// reverse complement, so the two lists share no key and the table is their union without sums: block b of the table holds exactly
+// C_b and M_b (the mirrored words whose first nine bases are b), and its place is known before anything is merged:
+//
+//     place(b) = (entries of C before block b) + (entries of M before block b).
+//
+// So M needs no more than grouping by its top 18 bits, and the union needs no merge path:
+//   1. strand_mirror_kernel: M written densely, rc(k-mer) << pack | count at the canonical word's own index (whole lines), the digit
+//      counts of the two passes below taken on the way;
+//   2. two passes of the key kernel over M's top 18 key bits (sort_keys_upper_counted): M grouped by block;
+//   3. strand_starts_kernel: where every block of M starts (a binary search per block);
+//   4. strand_block_union_kernel: one workgroup per block reads C_b (in place, where the dedupe wrote it) and M_b, sorts the two in
+//      LDS (tile_group.hpp: the counting sort and the in-group ranks of tilesort.hip) and writes keys and counts at place(b) + rank.
+//      No tile waits for another.
+//
+// Buffers: C's gapped words stay in the dedupe's work buffer until the union has read them; M and the ping-pong buffer of its passes
+// (2 x 8 U bytes for U distinct canonical k-mers) are the first and second half of the keys' buffer, which the dedupe has finished with.
+//
+// A block of more entries than a tile holds (low-complexity sequence, genomes whose 9-base prefixes are far from uniform), or one
+// whose entries crowd a few groups, is declined onto a list, and strand_big_block_kernel takes the listed blocks alone: 256 splitters
+// sampled from C_b and M_b cut the block's value range, one pass over M_b counts every range, the ranges are packed into sub-tiles
+// of at most a tile, and each sub-tile gathers its M entries in one more pass over M_b and is sorted and written like a whole block.
+// A block's cost grows with its own size only.  Should a single range still hold more than a tile (or crowd its groups), the union
+// is made the other way from the same state, exactly: C copied densely, M sorted on every bit, and the merge-path union (setops.hip).
+#include "tile_group.hpp"
+
+namespace zk {
+
+constexpr int SB_ITEMS = 16, SB_GROUPS = 2048;          // tiles of 8 K entries (a block at config 2: ~6.1 K) in 2048 groups
+constexpr u32 SB_GROUP_MAX = 128;                         // a group of more entries declines its tile (the ranks are quadratic in it)
+typedef TileSortSmem<SB_ITEMS, SB_GROUPS, false> StrandSmem;
+constexpr int SB_BLOCK_BITS = 18;
+
+// block v's words w -> out_m[incl[v] - nwords[v] + i] = rc(w >> pack) << pack | (w & count mask), with the digit counts of mh
+__global__ __launch_bounds__(256) void strand_mirror_kernel(const u64* __restrict__ in, const u64* __restrict__ cuts, const u64* __restrict__ incl,
+                                                            const u64* __restrict__ nwords, u32 chunks, int pack, int K, u64* __restrict__ out_m,
+                                                            MirrorHist mh) {
+    __shared__ u32 bins[4 * 512];
+    const bool hist = mh.passes > 0;
+    if (hist) {
+        for (int q = threadIdx.x; q < 4 * 512; q += blockDim.x) bins[q] = 0;
+        __syncthreads();
+    }
+    const u64 maxc = (1ull << pack) - 1;
+    for (u32 v = blockIdx.x; v < chunks; v += gridDim.x) {
+        const u64 cnt = nwords[v];
+        const u64 dst0 = incl[v] - cnt;
+        const u64* src = in + cuts[v];
+        for (u64 i0 = threadIdx.x; i0 < cnt; i0 += 4ull * blockDim.x) {
+            u64 w4[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const u64 i = i0 + (u64)q * blockDim.x;
+                w4[q] = i < cnt ? src[i] : 0;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const u64 i = i0 + (u64)q * blockDim.x;
+                if (i >= cnt) break;
+                const u64 mw = (revcomp(K, w4[q] >> pack) << pack) | (w4[q] & maxc);
+                out_m[dst0 + i] = mw;
+                if (hist) {
+#pragma unroll
+                    for (int p = 0; p < 4; p++)
+                        if (p < mh.passes) atomicAdd(&bins[p * 512 + ((u32)(mw >> mh.shift[p]) & ((1u << mh.bits[p]) - 1u))], 1u);
+                }
+            }
+        }
+    }
+    if (hist) {
+        __syncthreads();
+        for (int q = threadIdx.x; q < mh.passes * 512; q += blockDim.x)
+            if (bins[q]) atomicAdd(&mh.raw[q], (u64)bins[q]);
+    }
+}
+
+// start[g] = first index of m whose bits from `shift` up are >= g (g = 0 .. 2^18; start[2^18] = n)
+__global__ void strand_starts_kernel(const u64* __restrict__ m, u64 n, int shift, u64* __restrict__ start) {
+    const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g > (1u << SB_BLOCK_BITS)) return;
+    u64 lo = 0, hi = n;
+    if (g == (1u << SB_BLOCK_BITS)) lo = n;
+    while (lo < hi) {
+        const u64 mid = (lo + hi) >> 1;
+        if ((m[mid] >> shift) < (u64)g) lo = mid + 1; else hi = mid;
+    }
+    start[g] = lo;
+}
+
+struct StrandArgs {
+    const u64* cw;          // C's words, block v at cuts[v] (nwords[v] of them)
+    const u64* cuts; const u64* nwords; const u64* incl;
+    const u64* m;           // M, grouped by block: block b at [mstart[b], mstart[b + 1])
+    const u64* mstart;
+    u64* ok; u32* oc;       // the table: keys, counts
+    int pack;
+    int pshift;             // the block bits of a word start here
+    u32* n_declined;        // the declined blocks: how many ...
+    u32* declined;          // ... and which
+};
+
+// does any group of the tile just grouped hold more than SB_GROUP_MAX entries?  (every thread looks at four groups; a barrier)
+__device__ __forceinline__ bool strand_crowded(const StrandSmem& sm, int tid) {
+    static_assert(SB_GROUPS == 4 * TS_BLOCK, "four groups a thread");
+    u32 big = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) big |= sm.start[4 * tid + q + 1] - sm.start[4 * tid + q] > SB_GROUP_MAX ? 1u : 0u;
+    return __syncthreads_or((int)big) != 0;
+}
+
+// the tile's entries, grouped (tile_group), ranked and written: keys to ok[place], counts to oc[place]
+__device__ __forceinline__ void strand_write(const StrandSmem& sm, const TileMap& tm, u32 m, u64* ok, u32* oc, int pack, int tid) {
+    const u64 maxc = (1ull << pack) - 1;
+    constexpr int E = 2;
+    for (u32 i0 = (u32)tid; i0 < m; i0 += E * TS_BLOCK) {
+        u32 i[E], place[E];
+        u64 mine[E];
+#pragma unroll
+        for (int e = 0; e < E; e++) i[e] = i0 + e * TS_BLOCK;
+        tile_rank<E, false>(sm, tm, i, m, mine, place);
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            if (i[e] >= m) break;
+            ok[place[e]] = mine[e] >> pack;
+            oc[place[e]] = (u32)(mine[e] & maxc);
+        }
+    }
+}
+
+// One workgroup per block, two per CU.  Every entry of C_b and M_b is loaded once, grouped in LDS by the next 11 bits of its key, ranked
+// in its group, and written to its place: the 64 lanes of a wave hold neighbours of the grouped order, so what a wave writes is a
+// permutation of one contiguous run of the table (512 bytes of keys, 256 of counts).
+__global__ __launch_bounds__(TS_BLOCK, 2 * TS_BLOCK / 256) void strand_block_union_kernel(StrandArgs a) {
+    using S = StrandSmem;
+    constexpr u32 CAP = S::CAP;
+    static_assert(sizeof(S) <= 80 * 1024, "two workgroups per CU");
+    __shared__ S sm;
+    const u32 b = blockIdx.x;
+    const u64 nc = a.nwords[b], m0 = a.mstart[b], nm = a.mstart[b + 1] - m0;
+    const u64 n = nc + nm;
+    if (n == 0) return;
+    if (n > CAP) {          // too large for a tile: strand_big_block_kernel's
+        if (threadIdx.x == 0) a.declined[atomicAdd(a.n_declined, 1u)] = b;
+        return;
+    }
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const u32 m = (u32)n;
+    const TileMap tm = tile_group<SB_ITEMS, SB_GROUPS, false>(sm, a.cw, nullptr, a.cuts[b], m, a.pshift, tid, a.m, m0, (u32)nc);
+    if (strand_crowded(sm, tid)) {          // entries that crowd a few groups: the big blocks' kernel cuts the value range finer
+        if (tid == 0) a.declined[atomicAdd(a.n_declined, 1u)] = b;
+        return;
+    }
+    const u64 out0 = a.incl[b] - nc + m0;
+    strand_write(sm, tm, m, a.ok + out0, a.oc + out0, a.pack, tid);
+}
+
+// ---- the declined blocks, cut by value into sub-tiles ----------------------------------------------------------------------------
+constexpr int SB_SPLIT = 256;          // splitters per block: 257 value ranges
+struct StrandBigSmem {
+    StrandSmem t;
+    u64 sp[SB_SPLIT];                  // the splitters, sorted (while they are sorted: the samples)
+    u32 mcnt[SB_SPLIT + 2];            // M entries per range, then the M entries before each range
+    u32 cpos[SB_SPLIT + 2];            // C index where each range starts (cpos[257] = nc)
+    u32 tile[SB_SPLIT + 2];            // the first range of each sub-tile, tile[ntiles] = 257
+    u32 ntiles, gcount, fail;
+};
+
+// One workgroup per listed block (persistent over the list).  scratch: CAP words per workgroup, where a sub-tile's M entries gather.
+__global__ __launch_bounds__(TS_BLOCK) void strand_big_block_kernel(StrandArgs a, u32 n_list, u64* __restrict__ scratch, u32* __restrict__ fail) {
+    using S = StrandBigSmem;
+    constexpr u32 CAP = StrandSmem::CAP, R = SB_SPLIT + 1;
+    __shared__ S sm;
+    u64* gat = scratch + (u64)blockIdx.x * CAP;
+    const int lane = threadIdx.x & 63;
+    for (u32 li = blockIdx.x; li < n_list; li += gridDim.x) {
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const u32 b = a.declined[li];
+        const u64 nc = a.nwords[b], m0 = a.mstart[b], nm = a.mstart[b + 1] - m0;
+        const u64* C = a.cw + a.cuts[b];
+        const u64* M = a.m + m0;
+        const u64 bmin = (u64)b << a.pshift, bmax = bmin | ((1ull << a.pshift) - 1ull);
+        const u64 out0 = a.incl[b] - nc + m0;
+        // 1. samples: half from C_b, half from M_b, evenly spaced (all from one list if the other is empty), sorted into splitters
+        u64* cand = sm.t.keys;
+        if (tid < SB_SPLIT) {
+            const bool one = nm == 0 || nc == 0;
+            const bool fromc = nm == 0 || (nc && tid < SB_SPLIT / 2);
+            const u32 j = one || fromc ? (u32)tid : (u32)tid - SB_SPLIT / 2, per = one ? SB_SPLIT : SB_SPLIT / 2;
+            cand[tid] = fromc ? C[(u64)j * nc / per] : M[(u64)j * nm / per];
+        }
+        if (tid == 0) { sm.fail = 0; sm.gcount = 0; }
+        if (tid < (int)R + 1) sm.mcnt[tid] = 0;
+        __syncthreads();
+        if (tid < SB_SPLIT) {
+            const u64 v = cand[tid];
+            u32 r = 0;
+            for (int q = 0; q < SB_SPLIT; q++) { const u64 o = cand[q]; r += (o < v || (o == v && q < tid)) ? 1u : 0u; }
+            sm.sp[r] = v;
+        }
+        __syncthreads();
+        // 2. M entries per range (range j: sp[j - 1] <= v < sp[j]); where each range starts in C (a binary search per splitter)
+        auto range_of = [&](u64 v) -> u32 {
+            u32 lo = 0, hi = SB_SPLIT;          // the number of splitters <= v
+            while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (sm.sp[mid] <= v) lo = mid + 1; else hi = mid; }
+            return lo;
+        };
+        for (u64 i = tid; i < nm; i += TS_BLOCK) atomicAdd(&sm.mcnt[range_of(M[i])], 1u);
+        if (tid <= SB_SPLIT) {
+            u32 p = 0;
+            if (tid > 0) {
+                const u64 v = sm.sp[tid - 1];
+                u64 lo = 0, hi = nc;
+                while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (C[mid] < v) lo = mid + 1; else hi = mid; }
+                p = (u32)lo;
+            }
+            sm.cpos[tid] = p;
+        }
+        if (tid == 0) sm.cpos[R] = (u32)nc;
+        __syncthreads();
+        // 3. ranges packed into sub-tiles of at most CAP entries, in order; mcnt becomes the M entries before each range
+        if (tid == 0) {
+            u32 acc = 0, nt = 0, mb = 0;
+            sm.tile[nt++] = 0;
+            for (u32 j = 0; j < R; j++) {
+                const u32 mc = sm.mcnt[j], tot = sm.cpos[j + 1] - sm.cpos[j] + mc;
+                if (tot > CAP) { sm.fail = 1; break; }
+                if (acc + tot > CAP) { sm.tile[nt++] = j; acc = 0; }
+                acc += tot;
+                sm.mcnt[j] = mb;
+                mb += mc;
+            }
+            sm.mcnt[R] = mb;
+            sm.tile[nt] = R;
+            sm.ntiles = nt;
+        }
+        __syncthreads();
+        if (sm.fail) {
+            if (tid == 0) atomicOr(fail, 1u);
+            continue;
+        }
+        const u32 ntiles = sm.ntiles;
+        // 4. every sub-tile: its M entries gathered (one pass over M_b), grouped with its slice of C over its own value range, written
+        for (u32 t = 0; t < ntiles; t++) {
+            const u32 ra = sm.tile[t], rb = sm.tile[t + 1];
+            const u64 vlo = ra == 0 ? bmin : sm.sp[ra - 1];
+            const u64 vhi = rb == R ? bmax : sm.sp[rb - 1] - 1;          // (sp[rb - 1] > vlo: the ranges between are not empty of values)
+            const u32 c_lo = sm.cpos[ra], mc = sm.cpos[rb] - c_lo, mt = sm.mcnt[rb] - sm.mcnt[ra];
+            const u32 m = mc + mt;
+            if (m == 0) continue;
+            if (mt) {
+                for (u64 i0 = 0; i0 < nm; i0 += TS_BLOCK) {
+                    const u64 i = i0 + tid;
+                    const u64 v = i < nm ? M[i] : 0;
+                    const bool in = i < nm && v >= vlo && v <= vhi;
+                    const u64 bal = __ballot(in);
+                    u32 base = 0;
+                    if (lane == 0 && bal) base = atomicAdd(&sm.gcount, (u32)__popcll(bal));
+                    base = (u32)__shfl((int)base, 0, 64);
+                    if (in) gat[base + popc_below(bal)] = v;
+                }
+                __threadfence_block();
+            }
+            __syncthreads();
+            const TileMap tm = tile_group<SB_ITEMS, SB_GROUPS, false>(sm.t, C, nullptr, c_lo, m, a.pshift, tid, gat, 0, mc, true, vlo, vhi);
+            if (strand_crowded(sm.t, tid)) {
+                if (tid == 0) atomicOr(fail, 1u);
+                break;
+            }
+            const u64 o = out0 + c_lo + sm.mcnt[ra];
+            strand_write(sm.t, tm, m, a.ok + o, a.oc + o, a.pack, tid);
+            if (tid == 0) sm.gcount = 0;
+            __syncthreads();          // the tile's LDS and the gathered entries are free again
+        }
+        __syncthreads();
+    }
+}
+
+// The table of both strands from the block dedupe's result r (odd K, every count in the field): see the top of the file.  keys_buf holds
+// buf_words words and is free; r.work must hold C's words until the union is done.
+int strand_blocks(zk_ctx* c, const DedupeResult& r, u64* keys_buf, uint64_t buf_words, int K, u64* out_k, u32* out_c, uint64_t cap,
+                  uint64_t* n_out) {
+    *n_out = 0;
+    const uint64_t uc = r.n_out;
+    if (uc == 0) return ZK_OK;
+    if (!(K & 1) || r.n_big || r.chunks != (1u << SB_BLOCK_BITS)) return fail(c, ZK_EINTERNAL, "strand_blocks: K %d, %u big counts, %u blocks", K, r.n_big, r.chunks);
+    const uint64_t a8w = ((8 * uc + 255) & ~255ull) / 8;
+    if (2 * a8w > buf_words) return fail(c, ZK_EINTERNAL, "strand_blocks: %llu words do not fit twice in %llu", (unsigned long long)uc, (unsigned long long)buf_words);
+    if (2 * uc > cap) return fail(c, ZK_ENOSPC, "output holds %llu entries, the table has %llu", (unsigned long long)cap, (unsigned long long)(2 * uc));
+    const int pk = r.pack, key_bits = 2 * K + pk, lo_bit = key_bits - SB_BLOCK_BITS;
+    u64* mw = keys_buf;
+    u64* malt = keys_buf + a8w;
+    // 1. M, densely, with the digit counts of its passes
+    MirrorHist mh = {};
+    if (c->sort_variant == 3) {
+        const PassPlan plan = sort_plan_upper(c, key_bits, lo_bit);
+        if (plan.passes <= 4) {
+            ZK_TRY(arena_alloc(c, sizeof(u64) * MAX_PASSES * 512, (void**)&mh.raw));
+            ZK_HIP(c, hipMemsetAsync(mh.raw, 0, sizeof(u64) * MAX_PASSES * 512, c->stream));
+            mh.passes = plan.passes;
+            for (int p = 0; p < plan.passes; p++) { mh.shift[p] = plan.shift[p]; mh.bits[p] = plan.bits[p]; }
+        }
+    }
+    prof_begin(c, ZK_PROF_SELECT, 16 * uc);
+    hipLaunchKernelGGL(strand_mirror_kernel, dim3((u32)c->num_cus * 8), dim3(256), 0, c->stream, r.work, r.cuts, r.incl, r.nwords, r.chunks, pk, K, mw, mh);
+    prof_end(c);
+    ZK_HIP(c, hipGetLastError());
+    // 2. grouped by its top 18 key bits
+    u64* sk = nullptr;
+    if (mh.passes) ZK_TRY(sort_keys_upper_counted(c, mw, malt, uc, key_bits, lo_bit, mh.raw, &sk));
+    else ZK_TRY(sort_keys_upper(c, mw, malt, uc, key_bits, lo_bit, &sk));
+    // 3. where its blocks start, 4. the union, block by block
+    u64* mstart;
+    u32* declined;
+    ZK_TRY(arena_alloc(c, sizeof(u64) * ((1ull << SB_BLOCK_BITS) + 1), (void**)&mstart));
+    ZK_TRY(arena_alloc(c, sizeof(u32) * r.chunks, (void**)&declined));
+    StrandArgs a = {};
+    a.cw = r.work; a.cuts = r.cuts; a.nwords = r.nwords; a.incl = r.incl; a.m = sk; a.mstart = mstart;
+    a.ok = out_k; a.oc = out_c; a.pack = pk; a.pshift = lo_bit;
+    a.n_declined = (u32*)(c->d_scalars + 9);
+    a.declined = declined;
+    u32* fail = (u32*)(c->d_scalars + 9) + 1;
+    prof_begin(c, ZK_PROF_UNION, 8 * 2 * uc + 12 * 2 * uc);
+    hipLaunchKernelGGL(strand_starts_kernel, dim3(((1u << SB_BLOCK_BITS) + 256) / 256), dim3(256), 0, c->stream, sk, (u64)uc, lo_bit, mstart);
+    ZK_HIP(c, hipMemsetAsync(c->d_scalars + 9, 0, sizeof(u64), c->stream));
+    hipLaunchKernelGGL(strand_block_union_kernel, dim3(r.chunks), dim3(TS_BLOCK), 0, c->stream, a);
+    prof_end(c);
+    ZK_HIP(c, hipGetLastError());
+    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    ZK_TRY(check_device_error(c));
+    const uint32_t n_declined = (uint32_t)c->h_scalars[9];
+    if (n_declined) {
+        // the declined blocks alone, cut by value into sub-tiles (their bytes: booked as the blocks' share of the union above)
+        const uint32_t grid = n_declined < 2u * (uint32_t)c->num_cus ? n_declined : 2u * (uint32_t)c->num_cus;
+        u64* scratch;
+        ZK_TRY(arena_alloc(c, sizeof(u64) * StrandSmem::CAP * grid, (void**)&scratch));
+        prof_begin(c, ZK_PROF_UNION, 0);
+        hipLaunchKernelGGL(strand_big_block_kernel, dim3(grid), dim3(TS_BLOCK), 0, c->stream, a, n_declined, scratch, fail);
+        prof_end(c);
+        ZK_HIP(c, hipGetLastError());
+        ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        ZK_TRY(check_device_error(c));
+    }
+    if ((uint32_t)(c->h_scalars[9] >> 32) == 0) {
+        *n_out = 2 * uc;
+        return ZK_OK;
+    }
+    // A range of a declined block did not fit a tile: the whole union the other way, from what is still there -- C's words in r.work, M in sk
+    char* aux;
+    ZK_TRY(aux_require(c, 8 * a8w, &aux));
+    ZK_TRY(dedupe_finish(c, r, (u64*)aux, nullptr, nullptr, K, 0, nullptr, nullptr, true));
+    u64* ms = nullptr;
+    ZK_TRY(sort_keys_upper(c, sk, sk == mw ? malt : mw, uc, key_bits, pk, &ms));
+    return union_sum_packed_ab(c, (const u64*)aux, uc, ms, uc, pk, out_k, out_c, cap, n_out, true);
+}
+
+}  // namespace zk

@@ -350,7 +350,10 @@ class Context:
 
     def tune(self, sort_variant=None, pairs_variant=None, short_sort=None, side_div=None, xcd_group=None, comm_chunk=None,
              early_collapse=None, packed_pairs=None, wide_tiles=None, stream_pass=None, stream_ranges=None, tag_words=None,
-             dedupe_variant=None, dedupe_limit=None, dedupe_bits=None, comm_self_loop=None, tag_pass=None, kway=None, tile_sort=None):
+             dedupe_variant=None, dedupe_limit=None, dedupe_bits=None, comm_self_loop=None, tag_pass=None, kway=None, tile_sort=None,
+             strand_blocks=None):
+        if strand_blocks is not None:
+            self._check(self.lib.zk_tune(self.h, 20, int(strand_blocks)))
         if tile_sort is not None:
             self._check(self.lib.zk_tune(self.h, 19, int(tile_sort)))
         if kway is not None:
