@@ -225,7 +225,8 @@ typedef struct {
     uint64_t n_windows;     /* valid windows seen */
     uint64_t n_instances;   /* k-mers the reference would have emitted = 2 * n_windows (kmerize.py:523-525) */
     uint64_t n_unique;      /* entries written to d_kmers / d_counts */
-    uint64_t n_canonical;   /* distinct canonical k-mers (0 in ZK_KMERIZE_BOTH mode) */
+    uint64_t n_canonical;   /* distinct canonical k-mers (0 in ZK_KMERIZE_BOTH mode), the same on every plan; with
+                               ZK_KMERIZE_SUBSAMPLE counted BEFORE the subsample (n_unique is after it) */
     uint64_t acgt[4];       /* acgt[x & 3] over every instance, before any filtering (kmerize.py:492-493) */
 } zk_kmerize_stats;
 

@@ -137,6 +137,36 @@ def test_merge_files(tmp_path):
     assert e.value.code == 1
 
 
+def test_merge_many_files_fresh_workspace(tmp_path):
+    """`zot merge` over 33 sets of 1 Mi pairs right after the device workspace is released -- what a user's process has: zk_merge_n
+    sizes the workspace by its own estimate, and two levels of 16-list passes (one set sits out level 1) must fit in it.  Checked
+    against the oracle's merge."""
+    from oracle import zkoracle as zo
+    from zotmer_amd.library import engine
+    rng = np.random.default_rng(33)
+    n, k = 1 << 20, 33
+    j = np.arange(n, dtype=np.uint64)
+    paths, sets = [], []
+    for i in range(k):
+        km = (j * np.uint64(k - 1) + np.uint64(i % (k - 1))) * np.uint64(5) + np.uint64(i & 3)          # sets 0 and 32 share their keys
+        ct = rng.integers(1, 200, size=n, dtype=np.uint64)
+        p = tmp_path / ("s%02d.k25" % i)
+        with KmerSet(str(p), "w") as z:
+            vectors.write_kmers_and_counts(z, km, ct)
+            z.meta.update({"K": 25})
+        paths.append(p)
+        sets.append((km, ct))
+    zs, zc, _ = zo.merge_n(25, sets)
+    del sets
+    engine.context().release_workspace()
+    out = tmp_path / "m.k25"
+    _, rc = zot("merge", out, *paths)
+    assert not rc
+    with KmerSet(str(out), "r") as z:
+        gk, gc = vectors.read_kmers_and_counts(z)
+    assert np.array_equal(gk, zs) and np.array_equal(gc, zc)
+
+
 def test_dist_stdout(tmp_path):
     g = G.load_json("g5_dist")
     files = {n: make_set(tmp_path, n) for n in ("g4_part0", "g4_part1", "g4_part2", "g4_merge3")}

@@ -169,6 +169,27 @@ static int max_u32(zk_ctx* c, const u32* v, uint64_t n, uint64_t* out) {
     return ZK_OK;
 }
 
+// how many of the n keys are their own reverse complement (even K only; at odd K none is)
+__global__ void palindromes_kernel(const u64* __restrict__ v, u64 n, int K, unsigned long long* out) {
+    u32 m = 0;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) m += revcomp(K, v[i]) == v[i] ? 1u : 0u;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m += (u32)__shfl_xor((int)m, o, 64);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(out, (unsigned long long)m);
+}
+
+static int count_palindromes(zk_ctx* c, const u64* v, uint64_t n, int K, uint64_t* out) {
+    ZK_HIP(c, hipMemsetAsync(c->d_scalars + 26, 0, sizeof(u64), c->stream));
+    if (n) {
+        hipLaunchKernelGGL(palindromes_kernel, dim3(ew_grid(c, n)), dim3(256), 0, c->stream, v, (u64)n, K, (unsigned long long*)(c->d_scalars + 26));
+        ZK_HIP(c, hipGetLastError());
+    }
+    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 26, c->d_scalars + 26, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    *out = c->h_scalars[26];
+    return ZK_OK;
+}
+
 // Both strands from the counted canonical list (c, n), c ascending: the pairs (rc c, n) are sorted by key and union-summed
 // with (c, n); a palindrome (c == rc c, even K) meets itself there and gets n + n -- two emissions per window, as the
 // reference has them (commands/kmerize.py:490, library/reads.py:113-114).  rk / rk2 (8 bytes per entry) and rv / rv2 (4) are
@@ -306,7 +327,10 @@ static int kmerize_full(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, bo
                 ZK_TRY(sort_keys_upper(c, sorted, sorted == buf_a ? buf_b : buf_a, n, 2 * K, 0, &res, ZK_PROF_PASS_KEYS));
                 ZK_TRY(rle(c, res, n, out_k, out_c, cap, n_out));
             }
-            st->n_canonical = (K & 1) ? *n_out / 2 : 0;          // (odd K: no k-mer is its own reverse complement, the table is two lists of equal length)
+            // the table holds x and rc x for every canonical k-mer: two entries each, but one for a palindrome (x == rc x, even K only)
+            uint64_t pal = 0;
+            if (!(K & 1)) ZK_TRY(count_palindromes(c, out_k, *n_out < cap ? *n_out : cap, K, &pal));
+            st->n_canonical = (*n_out + pal) / 2;
             return ZK_OK;
         }
     }
@@ -629,7 +653,6 @@ static int kmerize_short(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, i
     uint64_t um = 0, ns = 0;
     ZK_TRY(rle_prefix(c, sorted, n, lo_bit, sorted, cnt, n, &um, side_k, side_c, side_cap, &ns));
     if (ns > side_cap) return 1;
-    st->n_canonical = um + ns;
     const uint64_t m = um + 2 * ns;
     const uint64_t a8 = (8 * m + 255) & ~255ull, a4 = (4 * m + 255) & ~255ull;
     char* aux;
@@ -655,7 +678,12 @@ static int kmerize_short(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, i
         ZK_TRY(reduce_by_key(c, sk, sv, m, rk, rv, m, &mr));
         sk = rk; sv = rv;
     }
-    return union_sum(c, sorted, cnt, um, sk, sv, mr, out_k, out_c, 32, cap, n_out, nullptr);
+    ZK_TRY(union_sum(c, sorted, cnt, um, sk, sv, mr, out_k, out_c, 32, cap, n_out, nullptr));
+    // (the side list holds a canonical k-mer once per group it was cut into: its length is no count of them -- the table is)
+    uint64_t pal = 0;
+    if (!(K & 1)) ZK_TRY(count_palindromes(c, out_k, *n_out, K, &pal));
+    st->n_canonical = (*n_out + pal) / 2;
+    return ZK_OK;
 }
 
 int kmerize(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, int flags, double p, uint64_t seed, u64* out_k, u32* out_c,
@@ -736,10 +764,14 @@ int merge_many(zk_ctx* c, int k, const u64* const* keys, const void* const* cnts
         // union with the empty set: a plain copy that also yields the count-weighted acgt
         return union_sum(c, keys[0], cnts[0], ns[0], keys[0], cnts[0], 0, out_k, out_c, count_bits, cap, n_out, acgt_w);
     }
-    // two ping-pong regions, each able to hold every intermediate list of one level
+    // two ping-pong regions, each able to hold every intermediate list of one level; behind them the scratch of ONE pass, which is
+    // handed back when the pass returns (each pass synchronises first, so nothing of it is in flight).  The largest pass is a k-way
+    // pass over at most `total` pairs of up to 16 lists: its sample and the sample's sort buffer (16 B per 64 pairs), the tile bounds
+    // (8 B per tile and list, a tile per 16 sample points or more: 0.125 B a pair at 16 lists), the acgt rows, sort_keys' histograms
+    // and tile bounds -- below total / 2 + 8 KB a list + 1 MB.  A 2-way pass needs its merge-path partition and acgt rows only.
     const uint64_t slack = 1 << 20;
     const uint64_t rbytes = (8 + cb) * total + 512ull * k;
-    const uint64_t need = 2 * rbytes + total / 2 + 8192ull * k + slack;   // + merge-path partitions, acgt rows; the k-way pass: its sample (twice), tile bounds
+    const uint64_t need = 2 * rbytes + total / 2 + 8192ull * k + slack;
     ZK_TRY(arena_require(c, need, need));
     struct L { const u64* k; const void* c; uint64_t n; };
     std::vector<L> va(k), vb(k);
@@ -790,6 +822,7 @@ int merge_many(zk_ctx* c, int k, const u64* const* keys, const void* const* cnts
                 capo = capg;
             }
             uint64_t no = 0;
+            const uint64_t mark = c->arena_off;          // this pass's scratch starts here and is dead when it returns
             if (g == 2) {
                 ZK_TRY(union_sum(c, cur[i].k, cur[i].c, cur[i].n, cur[i + 1].k, cur[i + 1].c, cur[i + 1].n, ok, oc, count_bits, capo, &no,
                                  last ? acgt_w : nullptr));
@@ -798,6 +831,7 @@ int merge_many(zk_ctx* c, int k, const u64* const* keys, const void* const* cnts
                 for (int j = 0; j < g; j++) { gk[j] = cur[i + j].k; gc[j] = cur[i + j].c; gn[j] = cur[i + j].n; }
                 ZK_TRY(kway_union_sum(c, g, gk, gc, gn, ok, oc, count_bits, capo, &no, last ? acgt_w : nullptr));
             }
+            c->arena_off = mark;
             nxt[o++] = L{ok, oc, no};
         }
         L* t = cur; cur = nxt; nxt = t;
