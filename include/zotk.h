@@ -105,8 +105,11 @@ int zk_upload_async(zk_ctx* ctx, void* d_dst, const void* src, uint64_t bytes);
                                   * (tilesort.hip); 0 = LSD passes over every bit */
 #define ZK_TUNE_STRAND_BLOCKS 20  /* zk_kmerize, block dedupe with 18 block bits at odd K, both strands wanted: 1 (default) = the table is rebuilt block
                                   * by block -- the mirror words grouped by their top 18 bits in two passes, each block's two lists sorted in LDS and
-                                  * written to a place known in advance (strand_blocks.hip); 0 = the mirror words sorted on 26 bits in three passes
-                                  * and merged with the counted list by the merge-path union */
+                                  * written to a place known in advance (strand_blocks.hip), the dedupe leaving its blocks in table order; 0 = the
+                                  * mirror words sorted on 26 bits in three passes and merged with the counted list by the merge-path union; 2 = block
+                                  * by block, the dedupe sorting its blocks (the route before the unsorted dedupe, for the A / B); 3 = tests: as 1,
+                                  * but blocks declined by the union go straight to the last resort (the counted list sorted and copied densely,
+                                  * the merge-path union) */
 #define ZK_TUNE_COMM_SELF_LOOP 16 /* tests: 1 = the piece a rank keeps goes through grouped ncclSend / ncclRecv to itself, in the same rounds as
                                   * the other pieces (instead of a device copy), and zk_allreduce_u64 calls ncclAllReduce with one rank too:
                                   * the RCCL data path of zk_comm_* executed on a box with one GPU; 0 (default) */

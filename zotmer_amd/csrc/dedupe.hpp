@@ -39,7 +39,8 @@ struct DedupeArgs {
 #define DD_PHASE(k) do { } while (0)
 #endif
 
-// dedupe2.hip: two workgroups per CU, 32-bit tags, 16-bit counts.  variant: zk_tune(ZK_TUNE_DEDUPE_VARIANT)
-int launch_dedupe2(zk_ctx* c, const DedupeArgs& a, bool tagin, int variant);
+// dedupe2.hip: two workgroups per CU, 32-bit tags, 16-bit counts.  variant: zk_tune(ZK_TUNE_DEDUPE_VARIANT); unsorted: the blocks'
+// words are written in table order
+int launch_dedupe2(zk_ctx* c, const DedupeArgs& a, bool tagin, int variant, bool unsorted);
 
 }  // namespace zk

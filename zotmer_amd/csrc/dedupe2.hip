@@ -10,6 +10,8 @@
 //     declined up front and counted by dedupe_kernel afterwards, as are the blocks whose table fills up);
 //   * side lists of 128 entries a wave, drained 64 at a time as soon as 64 are there (full wavefronts, no worst-case tile to hold);
 // -- 11 K entries in 76 KB, and while one workgroup of the CU sorts and writes its block the other one inserts.
+// UNSORTED (the strand route at odd K, strand_blocks.hip, which sorts every block again with its mirror image): the block's distinct
+// words are written compacted in table order instead -- no counting sort, no ranks (12.1 -> 9.4 ms at config 2, profiles/r08).
 #include "dedupe.hpp"
 #include <type_traits>
 
@@ -30,6 +32,7 @@ struct Dedupe2Smem {
         struct { u32 bc[NB]; u32 bbase[NB + 1]; } g;          // afterwards: entries per group (the tag's top ten bits), and before it
     };
     u32 ticket;
+    u32 nout;                             // UNSORTED: the block's entries written so far
 };
 
 // what a workgroup carries from one block to the next: the block it is about to count, with the first tile of its tags already
@@ -78,7 +81,7 @@ __device__ __forceinline__ void dedupe2_load(const DedupeArgs& a, u64 lo, u32 po
     }
 }
 
-template <int BLOCK, int BATCH, int ITEMS_, bool TAGIN>
+template <int BLOCK, int BATCH, int ITEMS_, bool TAGIN, bool UNSORTED>
 __device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, Dedupe2Smem<BLOCK, BATCH, ITEMS_>& sm, Dedupe2Next<ITEMS_>& st, u32 (&ph)[8], u32& tlast) {
     using S = Dedupe2Smem<BLOCK, BATCH, ITEMS_>;
     constexpr int ITEMS = S::ITEMS, TILE = S::TILE, ALL = S::ALL, SPT = S::SPT, NB = S::NB;
@@ -115,6 +118,7 @@ __device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, Dedupe2Smem<B
     }
     for (int q = tid; q < ALL / 4; q += BLOCK) reinterpret_cast<uint4*>(sm.keys)[q] = make_uint4(~0u, ~0u, ~0u, ~0u);
     for (int q = tid; q < ALL / 8; q += BLOCK) reinterpret_cast<uint4*>(sm.cnt)[q] = make_uint4(0, 0, 0, 0);
+    if (UNSORTED && tid == 0) sm.nout = 0;
     __syncthreads();
     DD_PHASE(0);          // table cleared
     const u32 nchunk = (u32)__builtin_amdgcn_readfirstlane((int)sm.ticket);
@@ -193,6 +197,40 @@ __device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, Dedupe2Smem<B
         }
         if (a.sub && tid < 64) a.sub[(u64)chunk * 64 + tid] = 0;
         next_block(nchunk);
+        return;
+    }
+    if constexpr (UNSORTED) {
+        // ---- the block's entries in table order, compacted (the strand route sorts every block again: strand_blocks.hip) ------
+        // thread t owns the entries t, t + BLOCK, ...; a wave counts what its lanes hold (one ballot per round), takes its share of
+        // the block's words with one LDS add and writes them, every round a run of consecutive words
+        next_block(nchunk);          // the next block's first tile travels while this one is written
+        const u16* cnt16 = reinterpret_cast<const u16*>(sm.cnt);
+        u32 wn = 0;
+#pragma unroll
+        for (int j = 0; j < SPT; j++) wn += (u32)__popcll(__ballot(cnt16[tid + j * BLOCK] != 0));
+        u32 wbase = 0;
+        if (lane == 0 && wn) wbase = atomicAdd(&sm.nout, wn);
+        wbase = (u32)__shfl((int)wbase, 0, 64);
+        DD_PHASE(3);          // entries counted, the wave's words placed
+        const u64 hi_part = (u64)chunk << a.tag_bits;
+#pragma unroll
+        for (int j = 0; j < SPT; j++) {
+            const u32 c = cnt16[tid + j * BLOCK];
+            const u64 bal = __ballot(c != 0);          // (again: 22 ballots kept from the count above spill 34 scalar registers)
+            if (c) {
+                const u64 k = hi_part | (u64)sm.keys[tid + j * BLOCK];
+                if (c > maxc) {
+                    const u32 at = atomicAdd(a.n_big, 1u);
+                    if (at < a.big_cap) { a.big[2 * (u64)at] = k; a.big[2 * (u64)at + 1] = c; }
+                    atomicOr(a.flags, 2u);
+                }
+                a.out[lo + wbase + popc_below(bal)] = (k << a.pack) | (u64)(c > maxc ? 0u : c);
+            }
+            wbase += (u32)__popcll(bal);
+        }
+        __syncthreads();
+        if (tid == 0) a.nwords[chunk] = sm.nout;          // (read before the caller's barrier; the next block clears it after)
+        DD_PHASE(5);          // written
         return;
     }
     // ---- the block's entries, sorted: a counting sort on the tag's top ten bits, then ranks inside each group of ~3 -----------
@@ -298,7 +336,7 @@ __device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, Dedupe2Smem<B
 
 // Persistent: two workgroups per CU draw the blocks from a counter -- in order, not strided: the sizes go with the first bases, a
 // stride of the grid would give one workgroup all the big ones.
-template <int BLOCK, int BATCH, int ITEMS, bool TAGIN>
+template <int BLOCK, int BATCH, int ITEMS, bool TAGIN, bool UNSORTED>
 __global__ __launch_bounds__(BLOCK, 2 * BLOCK / 256) void dedupe2_kernel(DedupeArgs a) {
     using S = Dedupe2Smem<BLOCK, BATCH, ITEMS>;
     __shared__ S sm;
@@ -321,7 +359,7 @@ __global__ __launch_bounds__(BLOCK, 2 * BLOCK / 256) void dedupe2_kernel(DedupeA
     (void)tlast;
     u32 nblk = 0;
     while (st.chunk < a.chunks) {
-        dedupe2_block<BLOCK, BATCH, ITEMS, TAGIN>(a, sm, st, ph, tlast);          // leaves the next block in st
+        dedupe2_block<BLOCK, BATCH, ITEMS, TAGIN, UNSORTED>(a, sm, st, ph, tlast);          // leaves the next block in st
         __syncthreads();          // the table and the ticket word are free again
         DD_PHASE(6);
         nblk++;
@@ -335,12 +373,16 @@ __global__ __launch_bounds__(BLOCK, 2 * BLOCK / 256) void dedupe2_kernel(DedupeA
 // variant: bits 0-1 = compare-and-swaps in flight per thread (0: 4, 1: 1, 2: 2).  Tiles of 8 tags a thread; 16 (twice the bytes on
 // their way from memory): 14.5 against 12.6 ms.  (1024-thread workgroups, two to a CU, have 64 registers a thread: the entries a
 // thread holds while the block is sorted do not fit -- 25 to 40 spilled; not instantiated.)
-int launch_dedupe2(zk_ctx* c, const DedupeArgs& a, bool tagin, int variant) {
+int launch_dedupe2(zk_ctx* c, const DedupeArgs& a, bool tagin, int variant, bool unsorted) {
     const u32 want = 2u * (u32)c->num_cus;
     const u32 grid = a.chunks < want ? a.chunks : want;
-#define ZK_DD2(N, T) hipLaunchKernelGGL((dedupe2_kernel<512, N, 8, T>), dim3(grid), dim3(512), 0, c->stream, a)
-#define ZK_DD2B(T) switch (variant & 3) { case 1: ZK_DD2(1, T); break; case 2: ZK_DD2(2, T); break; default: ZK_DD2(4, T); break; }
-    if (tagin) ZK_DD2B(true) else ZK_DD2B(false)
+#define ZK_DD2(N, T, U) hipLaunchKernelGGL((dedupe2_kernel<512, N, 8, T, U>), dim3(grid), dim3(512), 0, c->stream, a)
+#define ZK_DD2B(T, U) switch (variant & 3) { case 1: ZK_DD2(1, T, U); break; case 2: ZK_DD2(2, T, U); break; default: ZK_DD2(4, T, U); break; }
+    if (unsorted) {
+        if (tagin) ZK_DD2B(true, true) else ZK_DD2B(false, true)
+    } else {
+        if (tagin) ZK_DD2B(true, false) else ZK_DD2B(false, false)
+    }
 #undef ZK_DD2B
 #undef ZK_DD2
     ZK_HIP(c, hipGetLastError());

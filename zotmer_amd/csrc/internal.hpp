@@ -41,7 +41,8 @@ struct zk_ctx {
     int kway = 1;              // zk_merge_n: 1 = up to 16 lists per pass (kway.hip) from 4 Mi pairs on, 2 = always, 0 = the tree of 2-way passes
     int tile_sort = 1;         // sorts of keys that do not repeat: LSD passes over the top bits, then tiles sorted to the end in LDS (tilesort.hip)
     int dedupe_bits = 0;       // tests: > 0 = the block dedupe with this many block bits whatever the input's size (pipeline.hip)
-    int strand_blocks = 1;     // zk_kmerize, block dedupe at odd K: both strands rebuilt block by block (strand_blocks.hip); 0 = mirror sort + merge-path union
+    int strand_blocks = 1;     // zk_kmerize, block dedupe at odd K: both strands rebuilt block by block (strand_blocks.hip); 0 = mirror sort + merge-path union;
+                               // 2 = block by block from sorted dedupe blocks (the route before the unsorted dedupe); 3 = tests: as 1, declined blocks go to the merge-path union
     int stream_ranges = 0;     // ... ranges the stream is cut into (0 = one per CU for variant 1, two for 2 and 3; tests use a few so that a range has many tiles)
 
     // workspace arena: a bump allocator reset at the start of every API call
@@ -168,9 +169,15 @@ struct DedupeResult {
     u32* sub = nullptr;          // [chunks][64] or null: how a block's entries split on the 6 bits after the block bits
     uint32_t chunks = 0;
     int pack = 0;
+    int tag_bits = 0;            // key bits below the block bits
+    bool unsorted = false;       // the blocks dedupe2_kernel counted are in table order (dedupe_sort_blocks sorts them)
 };
+// unsorted: dedupe2_kernel leaves its blocks in table order (the strand route sorts every block again; nobody else may read them so)
 int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int pack, u64* work, uint64_t cap, DedupeResult* r,
-                uint64_t* n_in = nullptr, uint64_t max_chunks = 0, const u32* tags = nullptr, const u64* tag_cuts = nullptr);
+                uint64_t* n_in = nullptr, uint64_t max_chunks = 0, const u32* tags = nullptr, const u64* tag_cuts = nullptr,
+                bool unsorted = false);
+// r.unsorted: every block of at most a dedupe2_kernel table's entries sorted in place (strand_blocks.hip); r.unsorted is false after
+int dedupe_sort_blocks(zk_ctx* c, DedupeResult& r);
 // the keys back from their tags: key = (block number << tag_bits) | tag
 int expand_tags(zk_ctx* c, const u32* tags, const u64* cuts, uint32_t blocks, int tag_bits, u64* keys_out, uint64_t first_block = 0, uint64_t n_blocks = 0);
 // packed_out: out_k takes the words themselves, (key << pack) | count, and out_c is not written (the caller merges them as they are)

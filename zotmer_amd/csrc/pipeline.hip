@@ -455,7 +455,10 @@ static int kmerize_full(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, bo
         const u32* tg = stags.written ? (const u32*)sorted : nullptr;
         if (!presampled) ZK_TRY(dedupe_pass(c, sorted, n, 2 * K, dedupe_bit, pk, other, cap_keys, &r, &n_in, (1u << 20) / per + 4, tg, stags.cuts));
         if (presampled || (!(r.flags & 1) && (double)r.n_out <= 0.6 * (double)n_in)) {
-            ZK_TRY(dedupe_pass(c, sorted, n, 2 * K, dedupe_bit, pk, other, cap_keys, &r, nullptr, 0, tg, stags.cuts));
+            // the strand route below sorts every block of the counted list again: the dedupe leaves them unsorted when it may be taken
+            const bool route = !canonical_only && c->packed_pairs && dedupe_bit == MIRROR_GROUP_BITS && 2 * K >= MIRROR_GROUP_BITS + 8 &&
+                               (K & 1) && (c->strand_blocks == 1 || c->strand_blocks == 3);
+            ZK_TRY(dedupe_pass(c, sorted, n, 2 * K, dedupe_bit, pk, other, cap_keys, &r, nullptr, 0, tg, stags.cuts, route));
             if (!(r.flags & 1)) {
                 uc = r.n_out;
                 const uint64_t a8 = (8 * uc + 255) & ~255ull, a4 = (4 * uc + 255) & ~255ull;
@@ -470,6 +473,7 @@ static int kmerize_full(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, bo
                     st->n_canonical = uc;
                     return strand_blocks(c, r, sorted, cap_keys, K, out_k, out_c, cap, n_out);
                 }
+                if (r.unsorted) ZK_TRY(dedupe_sort_blocks(c, r));          // the route is not taken after all: the blocks sorted first
                 char* aux;
                 ZK_TRY(aux_require(c, a8 + a4, &aux));
                 // ... and the counted list itself stays in words, (k-mer << pk) | count: nobody but the final union reads it

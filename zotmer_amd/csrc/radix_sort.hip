@@ -2388,7 +2388,7 @@ int expand_tags(zk_ctx* c, const u32* tags, const u64* cuts, uint32_t blocks, in
 }
 
 int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int pack, u64* work, uint64_t cap, DedupeResult* r,
-                uint64_t* n_in, uint64_t max_chunks, const u32* tags, const u64* tag_cuts) {
+                uint64_t* n_in, uint64_t max_chunks, const u32* tags, const u64* tag_cuts, bool unsorted) {
     *r = DedupeResult();
     if (n_in) *n_in = n;
     if (n == 0) return ZK_OK;
@@ -2422,7 +2422,9 @@ int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int
     // the mirror sort can group by 6 more bits if the blocks say how their entries split on them: 64 counts per block, when the
     // workspace has the room (and the finer grouping's tables after it: dedupe_finish)
     // ... leaving what the sorts and the union after it need (their tables are a few bytes per thousand keys)
-    if (!max_chunks && a.tag_bits >= 14 && c->arena_size - c->arena_off > 64ull * chunks * (4 + 8 + 8) + (32ull << 20) + n / 16)
+    const bool two_per_cu = a.tag_bits <= 32 && c->dedupe_variant >= 0;
+    unsorted = unsorted && two_per_cu;          // (dedupe_kernel's blocks leave it sorted)
+    if (!max_chunks && !unsorted && a.tag_bits >= 14 && c->arena_size - c->arena_off > 64ull * chunks * (4 + 8 + 8) + (32ull << 20) + n / 16)
         ZK_TRY(arena_alloc(c, sizeof(u32) * 64 * chunks, (void**)&a.sub));
     ZK_HIP(c, hipMemsetAsync(c->d_scalars + 27, 0, 5 * sizeof(u64), c->stream));
     // algorithmic bytes: every key read once (a 32-bit tag, or the whole key), one word written per distinct key (added below, once
@@ -2434,12 +2436,11 @@ int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int
         else if (d.tag_bits <= 32) hipLaunchKernelGGL((dedupe_kernel<true, false>), dim3(grid), dim3(1024), 0, c->stream, d);
         else hipLaunchKernelGGL((dedupe_kernel<false, false>), dim3(grid), dim3(1024), 0, c->stream, d);
     };
-    const bool two_per_cu = a.tag_bits <= 32 && c->dedupe_variant >= 0;
     if (two_per_cu) {
         ZK_TRY(arena_alloc(c, sizeof(u32) * chunks, (void**)&a.retry));
         a.n_retry = (u32*)(c->d_scalars + 28);
         a.limit = (u32)c->dedupe_limit;
-        ZK_TRY(launch_dedupe2(c, a, tags != nullptr, c->dedupe_variant));
+        ZK_TRY(launch_dedupe2(c, a, tags != nullptr, c->dedupe_variant, unsorted));
     } else launch_one_per_cu(a);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
@@ -2495,6 +2496,7 @@ int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int
     r->n_out = c->h_scalars[9];
     prof_add_bytes(c, ZK_PROF_RLE, 8 * r->n_out);          // one word written per distinct key
     r->cuts = cuts; r->nwords = nwords; r->incl = incl; r->big = big; r->chunks = (uint32_t)chunks; r->pack = pack; r->work = work; r->sub = a.sub;
+    r->tag_bits = a.tag_bits; r->unsorted = unsorted;
     if (n_in) *n_in = c->h_scalars[32];          // keys covered by the blocks that were counted
     return ZK_OK;
 }

@@ -1,7 +1,8 @@
 // strand_blocks.hip -- both strands of a counted canonical list, rebuilt block by block (odd K).
 //
 // The block dedupe (dedupe2.hip) leaves the counted canonical list C as (k-mer << pack | count) words, cut into 2^18 blocks by the
-// k-mer's first nine bases, each block sorted, block v at work + cuts[v] (nwords[v] words; its place in the dense list starts at
+// k-mer's first nine bases, each block in table order (the dedupe's unsorted mode: nothing here needs more than the block it is in),
+// block v at work + cuts[v] (nwords[v] words; its place in the dense list starts at
 // incl[v] - nwords[v]).  The table of both strands is C together with its mirror image M = rc(C), sorted.  At odd K no k-mer is its own
 // reverse complement, so the two lists share no key and the table is their union without sums: block b of the table holds exactly
 // C_b and M_b (the mirrored words whose first nine bases are b), and its place is known before anything is merged:
@@ -25,7 +26,8 @@
 // sampled from C_b and M_b cut the block's value range, one pass over M_b counts every range, the ranges are packed into sub-tiles
 // of at most a tile, and each sub-tile gathers its M entries in one more pass over M_b and is sorted and written like a whole block.
 // A block's cost grows with its own size only.  Should a single range still hold more than a tile (or crowd its groups), the union
-// is made the other way from the same state, exactly: C copied densely, M sorted on every bit, and the merge-path union (setops.hip).
+// is made the other way from the same state, exactly: C's blocks sorted, C copied densely, M sorted on every bit, and the merge-path
+// union (setops.hip).
 #include "tile_group.hpp"
 
 namespace zk {
@@ -133,7 +135,8 @@ __device__ __forceinline__ void strand_write(const StrandSmem& sm, const TileMap
 
 // One workgroup per block, two per CU.  Every entry of C_b and M_b is loaded once, grouped in LDS by the next 11 bits of its key, ranked
 // in its group, and written to its place: the 64 lanes of a wave hold neighbours of the grouped order, so what a wave writes is a
-// permutation of one contiguous run of the table (512 bytes of keys, 256 of counts).
+// permutation of one contiguous run of the table (512 bytes of keys, 256 of counts).  Neither list needs to be sorted: the grouping
+// reads only the block's number.
 __global__ __launch_bounds__(TS_BLOCK, 2 * TS_BLOCK / 256) void strand_block_union_kernel(StrandArgs a) {
     using S = StrandSmem;
     constexpr u32 CAP = S::CAP;
@@ -164,13 +167,13 @@ constexpr int SB_SPLIT = 256;          // splitters per block: 257 value ranges
 struct StrandBigSmem {
     StrandSmem t;
     u64 sp[SB_SPLIT];                  // the splitters, sorted (while they are sorted: the samples)
-    u32 mcnt[SB_SPLIT + 2];            // M entries per range, then the M entries before each range
-    u32 cpos[SB_SPLIT + 2];            // C index where each range starts (cpos[257] = nc)
+    u32 cnt[SB_SPLIT + 2];             // entries of C_b and M_b per range, then the entries before each range
     u32 tile[SB_SPLIT + 2];            // the first range of each sub-tile, tile[ntiles] = 257
     u32 ntiles, gcount, fail;
 };
 
-// One workgroup per listed block (persistent over the list).  scratch: CAP words per workgroup, where a sub-tile's M entries gather.
+// One workgroup per listed block (persistent over the list).  scratch: CAP words per workgroup, where a sub-tile's entries gather.
+// Neither C_b nor M_b needs to be sorted: both are read whole to count the ranges and once more for every sub-tile.
 __global__ __launch_bounds__(TS_BLOCK) void strand_big_block_kernel(StrandArgs a, u32 n_list, u64* __restrict__ scratch, u32* __restrict__ fail) {
     using S = StrandBigSmem;
     constexpr u32 CAP = StrandSmem::CAP, R = SB_SPLIT + 1;
@@ -181,21 +184,17 @@ __global__ __launch_bounds__(TS_BLOCK) void strand_big_block_kernel(StrandArgs a
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const u32 b = a.declined[li];
-        const u64 nc = a.nwords[b], m0 = a.mstart[b], nm = a.mstart[b + 1] - m0;
+        const u64 nc = a.nwords[b], m0 = a.mstart[b], nm = a.mstart[b + 1] - m0, n = nc + nm;
         const u64* C = a.cw + a.cuts[b];
         const u64* M = a.m + m0;
+        auto entry = [&](u64 i) -> u64 { return i < nc ? C[i] : M[i - nc]; };
         const u64 bmin = (u64)b << a.pshift, bmax = bmin | ((1ull << a.pshift) - 1ull);
         const u64 out0 = a.incl[b] - nc + m0;
-        // 1. samples: half from C_b, half from M_b, evenly spaced (all from one list if the other is empty), sorted into splitters
+        // 1. samples, evenly spaced over C_b and M_b together (all distinct keys: the two lists share none), sorted into splitters
         u64* cand = sm.t.keys;
-        if (tid < SB_SPLIT) {
-            const bool one = nm == 0 || nc == 0;
-            const bool fromc = nm == 0 || (nc && tid < SB_SPLIT / 2);
-            const u32 j = one || fromc ? (u32)tid : (u32)tid - SB_SPLIT / 2, per = one ? SB_SPLIT : SB_SPLIT / 2;
-            cand[tid] = fromc ? C[(u64)j * nc / per] : M[(u64)j * nm / per];
-        }
+        if (tid < SB_SPLIT) cand[tid] = entry((u64)tid * n / SB_SPLIT);
         if (tid == 0) { sm.fail = 0; sm.gcount = 0; }
-        if (tid < (int)R + 1) sm.mcnt[tid] = 0;
+        if (tid < (int)R + 1) sm.cnt[tid] = 0;
         __syncthreads();
         if (tid < SB_SPLIT) {
             const u64 v = cand[tid];
@@ -204,38 +203,27 @@ __global__ __launch_bounds__(TS_BLOCK) void strand_big_block_kernel(StrandArgs a
             sm.sp[r] = v;
         }
         __syncthreads();
-        // 2. M entries per range (range j: sp[j - 1] <= v < sp[j]); where each range starts in C (a binary search per splitter)
+        // 2. entries per range (range j: sp[j - 1] <= v < sp[j])
         auto range_of = [&](u64 v) -> u32 {
             u32 lo = 0, hi = SB_SPLIT;          // the number of splitters <= v
             while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (sm.sp[mid] <= v) lo = mid + 1; else hi = mid; }
             return lo;
         };
-        for (u64 i = tid; i < nm; i += TS_BLOCK) atomicAdd(&sm.mcnt[range_of(M[i])], 1u);
-        if (tid <= SB_SPLIT) {
-            u32 p = 0;
-            if (tid > 0) {
-                const u64 v = sm.sp[tid - 1];
-                u64 lo = 0, hi = nc;
-                while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (C[mid] < v) lo = mid + 1; else hi = mid; }
-                p = (u32)lo;
-            }
-            sm.cpos[tid] = p;
-        }
-        if (tid == 0) sm.cpos[R] = (u32)nc;
+        for (u64 i = tid; i < n; i += TS_BLOCK) atomicAdd(&sm.cnt[range_of(entry(i))], 1u);
         __syncthreads();
-        // 3. ranges packed into sub-tiles of at most CAP entries, in order; mcnt becomes the M entries before each range
+        // 3. ranges packed into sub-tiles of at most CAP entries, in order; cnt becomes the entries before each range
         if (tid == 0) {
-            u32 acc = 0, nt = 0, mb = 0;
+            u32 acc = 0, nt = 0, eb = 0;
             sm.tile[nt++] = 0;
             for (u32 j = 0; j < R; j++) {
-                const u32 mc = sm.mcnt[j], tot = sm.cpos[j + 1] - sm.cpos[j] + mc;
+                const u32 tot = sm.cnt[j];
                 if (tot > CAP) { sm.fail = 1; break; }
                 if (acc + tot > CAP) { sm.tile[nt++] = j; acc = 0; }
                 acc += tot;
-                sm.mcnt[j] = mb;
-                mb += mc;
+                sm.cnt[j] = eb;
+                eb += tot;
             }
-            sm.mcnt[R] = mb;
+            sm.cnt[R] = eb;
             sm.tile[nt] = R;
             sm.ntiles = nt;
         }
@@ -245,40 +233,82 @@ __global__ __launch_bounds__(TS_BLOCK) void strand_big_block_kernel(StrandArgs a
             continue;
         }
         const u32 ntiles = sm.ntiles;
-        // 4. every sub-tile: its M entries gathered (one pass over M_b), grouped with its slice of C over its own value range, written
+        // 4. every sub-tile: its entries gathered (one pass over C_b and M_b), grouped over its own value range, written
         for (u32 t = 0; t < ntiles; t++) {
             const u32 ra = sm.tile[t], rb = sm.tile[t + 1];
             const u64 vlo = ra == 0 ? bmin : sm.sp[ra - 1];
             const u64 vhi = rb == R ? bmax : sm.sp[rb - 1] - 1;          // (sp[rb - 1] > vlo: the ranges between are not empty of values)
-            const u32 c_lo = sm.cpos[ra], mc = sm.cpos[rb] - c_lo, mt = sm.mcnt[rb] - sm.mcnt[ra];
-            const u32 m = mc + mt;
+            const u32 m = sm.cnt[rb] - sm.cnt[ra];
             if (m == 0) continue;
-            if (mt) {
-                for (u64 i0 = 0; i0 < nm; i0 += TS_BLOCK) {
-                    const u64 i = i0 + tid;
-                    const u64 v = i < nm ? M[i] : 0;
-                    const bool in = i < nm && v >= vlo && v <= vhi;
-                    const u64 bal = __ballot(in);
-                    u32 base = 0;
-                    if (lane == 0 && bal) base = atomicAdd(&sm.gcount, (u32)__popcll(bal));
-                    base = (u32)__shfl((int)base, 0, 64);
-                    if (in) gat[base + popc_below(bal)] = v;
-                }
-                __threadfence_block();
+            for (u64 i0 = 0; i0 < n; i0 += TS_BLOCK) {
+                const u64 i = i0 + tid;
+                const u64 v = i < n ? entry(i) : 0;
+                const bool in = i < n && v >= vlo && v <= vhi;
+                const u64 bal = __ballot(in);
+                u32 base = 0;
+                if (lane == 0 && bal) base = atomicAdd(&sm.gcount, (u32)__popcll(bal));
+                base = (u32)__shfl((int)base, 0, 64);
+                if (in) gat[base + popc_below(bal)] = v;
             }
+            __threadfence_block();
             __syncthreads();
-            const TileMap tm = tile_group<SB_ITEMS, SB_GROUPS, false>(sm.t, C, nullptr, c_lo, m, a.pshift, tid, gat, 0, mc, true, vlo, vhi);
+            const TileMap tm = tile_group<SB_ITEMS, SB_GROUPS, false>(sm.t, gat, nullptr, 0, m, a.pshift, tid, nullptr, 0, ~0u, true, vlo, vhi);
             if (strand_crowded(sm.t, tid)) {
                 if (tid == 0) atomicOr(fail, 1u);
                 break;
             }
-            const u64 o = out0 + c_lo + sm.mcnt[ra];
+            const u64 o = out0 + sm.cnt[ra];
             strand_write(sm.t, tm, m, a.ok + o, a.oc + o, a.pack, tid);
             if (tid == 0) sm.gcount = 0;
             __syncthreads();          // the tile's LDS and the gathered entries are free again
         }
         __syncthreads();
     }
+}
+
+// ---- the blocks of an unsorted dedupe, sorted in place (the strand route not taken after all) ------------------------------------
+constexpr int DS_ITEMS = 22, DS_GROUPS = 4096;          // a tile of 11 264 words: the most a dedupe2_kernel table holds
+typedef TileSortSmem<DS_ITEMS, DS_GROUPS, false> BlockSortSmem;
+static_assert(BlockSortSmem::CAP == 11264, "a dedupe2_kernel table");
+
+// One workgroup per CU, strided over the blocks.  A block of more words was counted by dedupe_kernel or the host, and is sorted.
+__global__ __launch_bounds__(TS_BLOCK) void dedupe_sort_blocks_kernel(u64* __restrict__ w, const u64* __restrict__ cuts, const u64* __restrict__ nwords,
+                                                                     u32 chunks, int pshift) {
+    constexpr u32 CAP = BlockSortSmem::CAP;
+    __shared__ BlockSortSmem sm;
+    for (u32 v = blockIdx.x; v < chunks; v += gridDim.x) {
+        const u64 n = nwords[v];
+        if (n < 2 || n > CAP) continue;
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const u32 m = (u32)n;
+        u64* out = w + cuts[v];
+        const TileMap tm = tile_group<DS_ITEMS, DS_GROUPS, false>(sm, w, nullptr, cuts[v], m, pshift, tid);
+        constexpr int E = 2;
+        for (u32 i0 = (u32)tid; i0 < m; i0 += E * TS_BLOCK) {
+            u32 i[E], place[E];
+            u64 mine[E];
+#pragma unroll
+            for (int e = 0; e < E; e++) i[e] = i0 + e * TS_BLOCK;
+            tile_rank<E, false>(sm, tm, i, m, mine, place);
+#pragma unroll
+            for (int e = 0; e < E; e++)
+                if (i[e] < m) out[place[e]] = mine[e];
+        }
+        __syncthreads();          // the tile's LDS is free again
+    }
+}
+
+int dedupe_sort_blocks(zk_ctx* c, DedupeResult& r) {
+    if (!r.unsorted || r.n_out == 0) { r.unsorted = false; return ZK_OK; }
+    // booked with the dedupe (whose sort it is): every word read and written once
+    prof_begin(c, ZK_PROF_RLE, 16 * r.n_out);
+    hipLaunchKernelGGL(dedupe_sort_blocks_kernel, dim3(r.chunks < (u32)c->num_cus ? r.chunks : (u32)c->num_cus), dim3(TS_BLOCK), 0, c->stream, r.work, r.cuts,
+                       r.nwords, r.chunks, r.tag_bits + r.pack);
+    prof_end(c);
+    ZK_HIP(c, hipGetLastError());
+    r.unsorted = false;
+    return ZK_OK;
 }
 
 // The table of both strands from the block dedupe's result r (odd K, every count in the field): see the top of the file.  keys_buf holds
@@ -334,7 +364,8 @@ int strand_blocks(zk_ctx* c, const DedupeResult& r, u64* keys_buf, uint64_t buf_
     ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     ZK_TRY(check_device_error(c));
     const uint32_t n_declined = (uint32_t)c->h_scalars[9];
-    if (n_declined) {
+    if (n_declined && c->strand_blocks == 3) c->h_scalars[9] |= 1ull << 32;          // (tests: the declined blocks the other way)
+    else if (n_declined) {
         // the declined blocks alone, cut by value into sub-tiles (their bytes: booked as the blocks' share of the union above)
         const uint32_t grid = n_declined < 2u * (uint32_t)c->num_cus ? n_declined : 2u * (uint32_t)c->num_cus;
         u64* scratch;
@@ -351,9 +382,12 @@ int strand_blocks(zk_ctx* c, const DedupeResult& r, u64* keys_buf, uint64_t buf_
         return ZK_OK;
     }
     // A range of a declined block did not fit a tile: the whole union the other way, from what is still there -- C's words in r.work, M in sk
+    // (C's blocks sorted first, if the dedupe left them unsorted: the union merges two sorted lists)
+    DedupeResult rs = r;
+    ZK_TRY(dedupe_sort_blocks(c, rs));
     char* aux;
     ZK_TRY(aux_require(c, 8 * a8w, &aux));
-    ZK_TRY(dedupe_finish(c, r, (u64*)aux, nullptr, nullptr, K, 0, nullptr, nullptr, true));
+    ZK_TRY(dedupe_finish(c, rs, (u64*)aux, nullptr, nullptr, K, 0, nullptr, nullptr, true));
     u64* ms = nullptr;
     ZK_TRY(sort_keys_upper(c, sk, sk == mw ? malt : mw, uc, key_bits, pk, &ms));
     return union_sum_packed_ab(c, (const u64*)aux, uc, ms, uc, pk, out_k, out_c, cap, n_out, true);

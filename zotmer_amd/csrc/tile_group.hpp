@@ -39,7 +39,7 @@ __device__ __forceinline__ TileMap tile_group(S& sm, const u64* kin, const u32* 
                                               u64 vhi = 0) {
     constexpr int NW = TS_BLOCK / 64, QPT = G / TS_BLOCK / 4;          // QPT: quads of groups a thread scans
     static_assert(QPT == 1 || QPT == 2, "four or eight groups a thread in the scan");
-    static_assert(S::CAP <= 8192 && G <= 4096, "group | place << 12 in a word");
+    static_assert((S::CAP <= 8192 || (!PAIRS && S::CAP <= 16384)) && G <= 4096, "group | place << 12 in a word; u16 places of pairs");
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const u64* kp = kin + lo;
     u64 k[ITEMS];
