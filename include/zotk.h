@@ -132,6 +132,9 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_SAMPLE 13       /* the look before the sort: the few set-aside blocks, sorted and counted (tiny launches) */
 #define ZK_PROF_TILE_SORT 14    /* the lower bits of a sort finished tile by tile in LDS (tilesort.hip: 16 B per key, 24 per pair, once) */
 #define ZK_PROF_CAPTURE_HITS 15 /* zk_capture_hits: the window lookup, one wave per read (capture.hip) */
+#define ZK_PROF_PROJECT_SUM 16  /* zk_project_sum: the count pass (8 B read per entry) and the write pass (8 + count bytes read per entry,
+                                   16 B written per distinct prefix), one record each (spectrum.hip) */
+#define ZK_PROF_SPECTRUM 17     /* zk_spectrum_sums: the one pass over both lists (16 B read per entry) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -276,6 +279,34 @@ int zk_project_dedupe(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, int shif
                       uint64_t* d_out, uint64_t cap, uint64_t* n_out);
 /* dist.split (library/dist.py:241-265): abc = (|X & Y|, |X \ Y|, |Y \ X|) of two sorted unique arrays. */
 int zk_split(zk_ctx* ctx, const uint64_t* d_x, uint64_t nx, const uint64_t* d_y, uint64_t ny, uint64_t abc[3]);
+
+/* Measure.prep, vector mode (commands/dist.py:35-41: v[x >> S] += c), without the vector: the distinct values of kmer >> shift of
+ * ascending distinct k-mers, ascending, in d_keys, and the sum of the counts under each in d_sums; *total = the sum of all counts.
+ * count_bits (32 or 64) is the element type of d_counts.  shift == 0 copies the k-mers and widens the counts.  The sums are
+ * 64-bit: where the reference's array('I') raises OverflowError above 2^32 - 1 this goes on counting -- the one deliberate
+ * difference.  The counts of a set must add up to less than 2^64.  ZK_ENOSPC with *n_out = the number of prefixes if they
+ * exceed cap. */
+int zk_project_sum(zk_ctx* ctx, const uint64_t* d_kmers, const void* d_counts, int count_bits, uint64_t n, int shift,
+                   uint64_t* d_keys, uint64_t* d_sums, uint64_t cap, uint64_t* n_out, uint64_t* total);
+
+/* What the spectrum measures of library/dist.py (the vec=True branches) need of two spectra held as zk_project_sum leaves them,
+ * in one merge pass.  A key is shared when it is in both lists with non-zero sums x and y (a zero counter is an absent k-mer).
+ * The sum of |x - y| over the union is cx + cy - 2 * s_min and has no field of its own. */
+typedef struct {
+    uint64_t n_shared;   /* shared keys */
+    uint64_t s_min;      /* sum of min(x, y)                          (dist.py:37, :165) */
+    uint64_t x_shared;   /* sum of x over the shared keys: decompose's yxy   (dist.py:276) */
+    uint64_t y_shared;   /* sum of y over the shared keys: decompose's yyx   (dist.py:277) */
+    uint64_t s_xy_lo;    /* sum of x * y, exact, as 128 bits                 (dist.py:64) */
+    uint64_t s_xy_hi;
+    double s_sqrt;       /* sum of sqrt(x * y)                               (dist.py:90) */
+    double s_js;         /* sum of x/cx * log(2*cy*x / (cy*x + cx*y)) + y/cy * log(2*cx*y / (cx*y + cy*x)), each term computed in
+                            the reference's operation order (dist.py:138-139) */
+} zk_spectrum;
+/* cx, cy: the two totals as doubles (they enter s_js only).  The integers are exact.  The doubles are sums of per-workgroup
+ * partial sums taken in a fixed order: the same call on the same device returns the same bits.  Either list may be empty. */
+int zk_spectrum_sums(zk_ctx* ctx, const uint64_t* d_xk, const uint64_t* d_xs, uint64_t nx, const uint64_t* d_yk, const uint64_t* d_ys,
+                     uint64_t ny, double cx, double cy, zk_spectrum* out);
 
 /* positions[q] = how many elements of the sorted device array are < queries[q] (HOST arrays of m
  * entries): the cut points of a value-range partition for the multi-GPU exchange. */

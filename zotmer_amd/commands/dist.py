@@ -5,17 +5,30 @@ Usage:
 Options:
     -M measure  use "measure" for the distance between k-mer frequency sets.
                 Use "-M list" to get a list of available measures.
+
+The *.quant, *.ab and jensen.shannon measures compare k-mer spectra (the counts of the
+<k>-mer prefixes) and need sets that carry counts.  They follow the reference's formulas,
+with these differences:
+  - counters are 64-bit: sums beyond 2^32 - 1 are computed, not refused;
+  - spectra without a common k-mer give jaccard.ab = sorensen.ab = 1 (the limit; the
+    reference divides by zero);
+  - hellinger.quant of identical spectra is 0 (the reference takes the root of a rounding
+    error, which fails when that is negative);
+  - a set with no k-mers is an error (exit status 1).
+With more than one process (torch.distributed.run) only the *.qual measures are available.
 """
-# Drop-in for zotmer/commands/dist.py: per file Measure.prep (dist.py:43-49) = prefix projection +
-# adjacent dedupe on the device (zk_project_dedupe); per pair dist.split (library/dist.py:241-265) =
-# zk_split; the closed-form measures stay on the host (library/measures.py).  Each file is decoded
-# and uploaded once (the reference re-reads the right-hand file for every pair, dist.py:152-159).
+# Drop-in for zotmer/commands/dist.py.  Set measures: per file Measure.prep (dist.py:43-49) = prefix projection +
+# adjacent dedupe on the device (zk_project_dedupe); per pair dist.split (library/dist.py:241-265) = zk_split.
+# Spectrum measures: per file Measure.prep in vector mode (dist.py:35-41) = the prefixes and the sums of their counts
+# (zk_project_sum) instead of 4**K counters; per pair one merge pass (zk_spectrum_sums) gives the sums every vec=True
+# branch of library/dist.py is a function of.  The closed forms stay on the host (library/measures.py).  Each file
+# is decoded and uploaded once (the reference re-reads the right-hand file for every pair, dist.py:152-159).
 import fnmatch
 import sys
 
 from zotmer_amd.library import engine, vectors
 from zotmer_amd.library.container import KmerSet
-from zotmer_amd.library.measures import MEASURES
+from zotmer_amd.library.measures import MEASURES, SPECTRUM
 from zotmer_amd.library.usage import Spec
 
 _SPEC = Spec(options={"-M": "list"}, positionals=["<k>"], rest="<input>", rest_min=0)
@@ -46,24 +59,32 @@ def main(argv):
     if not ms or bad:                               # dist.py:122-123
         return
     vec = [m for m in ms if MEASURES[m][1]]
-    if vec:
-        raise SystemExit("zot dist: %s are spectrum (4**K counter) measures, which the reference cannot compute "
-                         "either (see SURVEY.md appendix C.7); use the *.qual measures" % ", ".join(vec))
+    need_set = len(vec) < len(ms)
 
     K = int(opts["<k>"])
     files = opts["<input>"]
     dist, world, rank = engine.distributed()        # one process per GPU under torch.distributed.run
     ctx = engine.context()
     if dist is not None:
+        if vec:
+            raise SystemExit("zot dist: %s are spectrum measures, which run on a single GPU for now" % ", ".join(vec))
         return _main_distributed(ctx, dist, K, files, ms)
 
-    def prep(path):                                 # dist.py:29-49
+    def prep(path):                                 # dist.py:29-49 -> (the set | None, the spectrum | None)
         with KmerSet(path, "r") as z:
             fK = z.meta["K"]
             if fK < K:
                 raise MismatchedK(K, fK)
-            k = vectors.device_read_kmers(ctx, z)
-        return engine.measure_prep(ctx, k, 2 * (fK - K))
+            if vec:                                 # files.readKmersAndCounts: a set without counts fails there too
+                if "counts" not in z.toc:
+                    raise SystemExit("zot dist: %s has no counts, which %s need%s" % (path, ", ".join(vec), "s" if len(vec) == 1 else ""))
+                k, c = vectors.device_read_kmers_and_counts(ctx, z)
+            else:
+                k, c = vectors.device_read_kmers(ctx, z), None
+        spec = engine.spectrum_prep(ctx, k, c, 2 * (fK - K)) if vec else None
+        if spec is not None and spec[2] == 0:             # measures.EmptySpectrum, said with the file's name
+            raise SystemExit("zot dist: %s holds no k-mers: it has no spectrum to compare" % path)
+        return (engine.measure_prep(ctx, k, 2 * (fK - K)) if need_set else None), spec
 
     print("\t".join(["lhs.name", "rhs.name"] + ms))
     sets = {}
@@ -72,8 +93,10 @@ def main(argv):
             for f in (files[i], files[j]):
                 if f not in sets:
                     sets[f] = prep(f)
-            abc = ctx.split(sets[files[i]], sets[files[j]])
-            vals = [MEASURES[m][2](*abc) for m in ms]
+            (xset, xspec), (yset, yspec) = sets[files[i]], sets[files[j]]
+            abc = ctx.split(xset, yset) if need_set else None
+            sums = ctx.spectrum_sums(xspec[0], xspec[1], xspec[2], yspec[0], yspec[1], yspec[2]) if vec else None
+            vals = [SPECTRUM[m](sums) if MEASURES[m][1] else MEASURES[m][2](*abc) for m in ms]
             print("\t".join([files[i], files[j]] + ["%g" % v for v in vals]))
 
 

@@ -273,6 +273,21 @@ int zk_split(zk_ctx* c, const uint64_t* d_x, uint64_t nx, const uint64_t* d_y, u
     return intersect_count(c, (const u64*)d_x, nx, (const u64*)d_y, ny, abc);
 }
 
+int zk_project_sum(zk_ctx* c, const uint64_t* d_kmers, const void* d_counts, int count_bits, uint64_t n, int shift, uint64_t* d_keys,
+                   uint64_t* d_sums, uint64_t cap, uint64_t* n_out, uint64_t* total) {
+    ZK_ARGS(c, n_out && total && shift >= 0 && shift < 64 && (count_bits == 32 || count_bits == 64) &&
+                   (n == 0 || (d_kmers && d_counts && d_keys && d_sums)));
+    arena_reset(c);
+    return project_sum(c, (const u64*)d_kmers, d_counts, count_bits, n, shift, (u64*)d_keys, (u64*)d_sums, cap, n_out, total);
+}
+
+int zk_spectrum_sums(zk_ctx* c, const uint64_t* d_xk, const uint64_t* d_xs, uint64_t nx, const uint64_t* d_yk, const uint64_t* d_ys,
+                     uint64_t ny, double cx, double cy, zk_spectrum* out) {
+    ZK_ARGS(c, out && (nx == 0 || (d_xk && d_xs)) && (ny == 0 || (d_yk && d_ys)));
+    arena_reset(c);
+    return spectrum_sums(c, (const u64*)d_xk, (const u64*)d_xs, nx, (const u64*)d_yk, (const u64*)d_ys, ny, cx, cy, out);
+}
+
 int zk_trim(zk_ctx* c, const uint64_t* d_kmers, const void* d_counts, int count_bits, uint64_t n, uint64_t lo, uint64_t hi,
             uint64_t* d_ok, void* d_oc, uint64_t cap, uint64_t* n_out) {
     ZK_ARGS(c, n_out && (count_bits == 32 || count_bits == 64));

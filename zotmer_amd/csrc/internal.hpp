@@ -261,4 +261,12 @@ int union_sum_packed_ab(zk_ctx* c, const u64* Ap, u64 nA, const u64* Bp, u64 nB,
 int column_sum(zk_ctx* c, const u64* rows, uint64_t n_rows, int cols, u64* out);   // out[c] = sum of rows[r][c]
 int project(zk_ctx* c, const u64* ref, u64 n_ref, const u64* B, const u64* cB, u64 nB, u64* ok, u64* oc, uint64_t cap, uint64_t* n_out);
 int intersect_count(zk_ctx* c, const u64* A, u64 nA, const u64* B, u64 nB, uint64_t abc[3]);
+// the merge-path cut of two sorted lists into tiles of MERGE_TILE merged elements (ties: A first): part[t] (arena) = the A elements
+// among the first t * MERGE_TILE; packb / packa > 0: that side holds (key << pack) | count words
+constexpr int MERGE_TILE = 4096;
+int make_partition(zk_ctx* c, const u64* A, u64 nA, const u64* B, u64 nB, u64** part, u32* tiles, int packb = 0, int packa = 0);
+// spectrum.hip
+int project_sum(zk_ctx* c, const u64* keys, const void* cnts, int count_bits, uint64_t n, int shift, u64* out_k, u64* out_s, uint64_t cap,
+                uint64_t* n_out, uint64_t* total);
+int spectrum_sums(zk_ctx* c, const u64* A, const u64* sA, u64 nA, const u64* B, const u64* sB, u64 nB, double cx, double cy, zk_spectrum* out);
 }  // namespace zk

@@ -22,6 +22,7 @@ namespace zk {
 constexpr int MRG_BLOCK = 512;
 constexpr int MRG_ITEMS = 8;
 constexpr int MRG_TILE = MRG_BLOCK * MRG_ITEMS;
+static_assert(MRG_TILE == MERGE_TILE, "internal.hpp");
 constexpr int MRG_NW = MRG_BLOCK / 64;
 
 // part[t] = number of A elements among the first min(t*TILE, nA+nB) merged elements
@@ -310,7 +311,7 @@ int column_sum(zk_ctx* c, const u64* rows, uint64_t n_rows, int cols, u64* out) 
     return ZK_OK;
 }
 
-static int make_partition(zk_ctx* c, const u64* A, u64 nA, const u64* B, u64 nB, u64** part, u32* tiles, int packb = 0, int packa = 0) {
+int make_partition(zk_ctx* c, const u64* A, u64 nA, const u64* B, u64 nB, u64** part, u32* tiles, int packb, int packa) {
     *tiles = (u32)div_up(nA + nB, MRG_TILE);
     ZK_TRY(arena_alloc(c, sizeof(u64) * ((uint64_t)*tiles + 1), (void**)part));
     hipLaunchKernelGGL(merge_partition_kernel, dim3((u32)div_up((uint64_t)*tiles + 1, 256)), dim3(256), 0, c->stream, A, nA, B, nB,

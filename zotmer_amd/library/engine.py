@@ -404,3 +404,9 @@ def measure_prep(ctx, kmers, shift):
         return kmers
     return ctx.project_dedupe(kmers, shift)
 
+
+def spectrum_prep(ctx, kmers, counts, shift):
+    """Measure.prep of `zot dist` in vector mode (commands/dist.py:35-41): v[x >> shift] += c, kept as the sorted prefixes that occur
+    and the sum under each instead of 4**K counters (zk_project_sum) -> (prefixes, u64 sums, total)"""
+    return ctx.project_sum(kmers, counts, shift)
+

@@ -33,6 +33,12 @@ class ZotkError(RuntimeError):
         self.code = code
 
 
+class Spectrum(C.Structure):
+    """zk_spectrum: the sums of one zk_spectrum_sums pass over two spectra (include/zotk.h)"""
+    _fields_ = [("n_shared", C.c_uint64), ("s_min", C.c_uint64), ("x_shared", C.c_uint64), ("y_shared", C.c_uint64),
+                ("s_xy_lo", C.c_uint64), ("s_xy_hi", C.c_uint64), ("s_sqrt", C.c_double), ("s_js", C.c_double)]
+
+
 class KmerizeStats(C.Structure):
     _fields_ = [("n_windows", C.c_uint64), ("n_instances", C.c_uint64), ("n_unique", C.c_uint64),
                 ("n_canonical", C.c_uint64), ("acgt", C.c_uint64 * 4)]
@@ -82,6 +88,8 @@ SIGNATURES = {
     "zk_project": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _pu64]),
     "zk_sample": (_i, [_vp, _vp, _vp, _u64, _u64, _d, _vp, _vp, _u64, _pu64]),
     "zk_split": (_i, [_vp, _vp, _u64, _vp, _u64, _pu64]),
+    "zk_project_sum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _vp, _vp, _u64, _pu64, _pu64]),
+    "zk_spectrum_sums": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _d, _d, C.POINTER(Spectrum)]),
     "zk_lower_bound": (_i, [_vp, _vp, _u64, _pu64, _u32, _pu64]),
     "zk_trim": (_i, [_vp, _vp, _vp, _i, _u64, _u64, _u64, _vp, _vp, _u64, _pu64]),
     "zk_codec64_encode": (_i, [_vp, _u64, _i, _vp, _u64, _pu64]),
@@ -346,7 +354,7 @@ class Context:
     # ---- per-launch timing (HIP events on the ctx stream) -----------------------------------
     PROF_TAGS = {"hist_stream": 1, "hist_array": 2, "pass_stream": 3, "pass_keys": 4, "pass_pairs": 5, "rle": 6,
                  "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
-                 "capture_hits": 15}
+                 "capture_hits": 15, "project_sum": 16, "spectrum": 17}
 
     def tune(self, sort_variant=None, pairs_variant=None, short_sort=None, side_div=None, xcd_group=None, comm_chunk=None,
              early_collapse=None, packed_pairs=None, wide_tiles=None, stream_pass=None, stream_ranges=None, tag_words=None,
@@ -545,6 +553,25 @@ class Context:
         abc = (C.c_uint64 * 3)()
         self._check(self.lib.zk_split(self.h, x.ptr, x.n, y.ptr, y.n, abc))
         return tuple(int(v) for v in abc)
+
+    def project_sum(self, kmers, counts, shift):
+        """ascending distinct k-mers and their (u32 | u64) counts -> (distinct kmer >> shift ascending, the u64 sum of the counts
+        under each, the sum of all counts)"""
+        assert counts.n == kmers.n
+        ok, os_ = self.empty(kmers.n, np.uint64), self.empty(kmers.n, np.uint64)
+        n, total = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.zk_project_sum(self.h, kmers.ptr, counts.ptr, counts.dtype.itemsize * 8, kmers.n, int(shift), ok.ptr, os_.ptr,
+                                            kmers.n, C.byref(n), C.byref(total)))
+        return ok.view(n.value), os_.view(n.value), int(total.value)
+
+    def spectrum_sums(self, xk, xs, cx, yk, ys, cy):
+        """two spectra as project_sum leaves them (keys, u64 sums, total) -> dict of the sums every spectrum measure is a
+        function of (library/measures.py: SPECTRUM); the integers exact, S_xy as one Python int"""
+        assert xs.n == xk.n and ys.n == yk.n and xs.dtype.itemsize == 8 and ys.dtype.itemsize == 8
+        r = Spectrum()
+        self._check(self.lib.zk_spectrum_sums(self.h, xk.ptr, xs.ptr, xk.n, yk.ptr, ys.ptr, yk.n, float(cx), float(cy), C.byref(r)))
+        return dict(cx=int(cx), cy=int(cy), n_shared=int(r.n_shared), S_min=int(r.s_min), X_shared=int(r.x_shared),
+                    Y_shared=int(r.y_shared), S_xy=int(r.s_xy_lo) | (int(r.s_xy_hi) << 64), S_sqrt=float(r.s_sqrt), S_js=float(r.s_js))
 
     def codec_encode(self, values, delta):
         """uint64 (or, delta=False, uint32) device values -> device codec64 words (delta=True: ascending k-mers, stored as
