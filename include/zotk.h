@@ -135,6 +135,11 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_PROJECT_SUM 16  /* zk_project_sum: the count pass (8 B read per entry) and the write pass (8 + count bytes read per entry,
                                    16 B written per distinct prefix), one record each (spectrum.hip) */
 #define ZK_PROF_SPECTRUM 17     /* zk_spectrum_sums: the one pass over both lists (16 B read per entry) */
+#define ZK_PROF_STRAND_KEYS 18  /* zk_strand_keys: the window pass, one wave per read (strand_bias.hip; bytes = the keys written) */
+#define ZK_PROF_STRAND_PAIRS 19 /* zk_strand_pairs: the count pass (8 B read per entry) and the write pass (8 + count bytes read per
+                                   entry, 16 B written per line), one record each */
+#define ZK_PROF_FORMAT_PAIRS 20 /* zk_format_pairs: the length pass (16 B read, 8 written per pair) and the write pass (24 B read per
+                                   pair + the text), one record each */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -203,6 +208,35 @@ int zk_capture_gather(zk_ctx* ctx, const uint64_t* d_pairs, uint64_t n_pairs, ui
 /* basics.can (library/basics.py:231-250; used by `zot vars`): per k-mer, whichever of x and rc(x) has the smaller
  * murmer(., 17) -- x on a tie.  Element-wise, asynchronous; d_out may equal d_kmers. */
 int zk_can(zk_ctx* ctx, int K, const uint64_t* d_kmers, uint64_t n, uint64_t* d_out);
+
+/* ---- strand bias of read pairs, `zot strand` (commands/strand.py, the mode without -r) ------------------------------
+ * A window is one TAGGED KEY (c << 1) | (oriented != c), c = min(x, rc x), 2K + 1 bits wide: 1 <= K <= 31 (K = 32 is refused;
+ * basics.rc disclaims K > 30 itself, basics.py:115-121).  Sorted, the two orientations of a k-mer are neighbours.
+ *
+ * zk_strand_keys: the tagged keys of every window of the sequence line of each of the first n_reads records of a FASTQ text
+ * (d_lines from zk_line_ends, at least 4 * n_reads of them; windows restart after any byte outside AaCcGgTtUu, basics.kmersList,
+ * basics.py:303-347).  oriented = x when reverse == 0 (mate 1: kmersList(K, fq1[1], False)), rc x otherwise (mate 2:
+ * [rc(K, x) for x in kmersList(K, fq2[1], False)], strand.py:59).  Only windows with (murmer(c, seed) & (4^K - 1)) <= T are
+ * kept (strand.py:136-139 with seed 17; T = int(M * p), computed by the host as Python does, strand.py:72-73).  The order of
+ * the keys in d_keys is unspecified, the multiset is not.  ZK_ENOSPC with *n_keys = the count if they exceed cap. */
+int zk_strand_keys(zk_ctx* ctx, const uint8_t* d_text, const uint64_t* d_lines, uint64_t n_reads, int K, int reverse, uint64_t seed,
+                   uint64_t T, uint64_t* d_keys, uint64_t cap, uint64_t* n_keys);
+
+/* The output loop of strand.py:142-155 over the ascending distinct tagged keys and their counts (count_bits 32 or 64): for each
+ * k-mer x seen with x <= rc x, xc = its count, yc = the count of rc x (entry i + 1 iff it holds the same c with tag 1; 0 if
+ * absent; xc itself for a palindrome, where rc x is x); d_a[j], d_b[j] = (xc, yc) if murmer(x, seed) >= murmer(rc x, seed), else
+ * (yc, xc) -- one line per such k-mer, in ascending x.  A k-mer seen only as the greater of {x, rc x} (an "orphan": a tag-1
+ * entry whose predecessor is not its partner) prints nothing in the reference; with ZK_STRAND_ORPHANS it is a line with xc = 0.
+ * stats: n_pairs = lines written, n_orphans = orphans (printed or not), n_palindromes.  ZK_ENOSPC with the stats filled in if
+ * n_pairs exceeds cap. */
+#define ZK_STRAND_ORPHANS 1
+typedef struct { uint64_t n_pairs, n_orphans, n_palindromes; } zk_strand_stats;
+int zk_strand_pairs(zk_ctx* ctx, const uint64_t* d_keys, const void* d_counts, int count_bits, uint64_t n, int K, uint64_t seed, int flags,
+                    uint64_t* d_a, uint64_t* d_b, uint64_t cap, zk_strand_stats* stats);
+
+/* print '%d\t%d' % (ac, bc) (strand.py:155) for n pairs of unsigned 64-bit values: the lines, each ended by '\n', one after the
+ * other in d_out.  ZK_ENOSPC with *n_bytes = the size needed if they exceed cap. */
+int zk_format_pairs(zk_ctx* ctx, const uint64_t* d_a, const uint64_t* d_b, uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* n_bytes);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

@@ -10,6 +10,8 @@
 //     capture.py:26-69, file.readFastq, file.py:38-52).
 // Records are located through the positions of the text's '\n' bytes (zk_line_ends): record r is lines 4r .. 4r+3.
 #include "internal.hpp"
+#include "compact.hpp"
+#include "read_window.hpp"
 
 // the table behind the opaque zk_bait_table of the C-ABI (device memory of its own, outlives the calls)
 struct zk_bait_table {
@@ -24,85 +26,10 @@ struct zk_bait_table {
 
 namespace zk {
 
-// ---------------------------------------------------------------------------------------
-// Order-preserving compaction: a count pass over tiles of 4096 items, an inclusive scan of the tile counts
-// (scan64_inclusive), a write pass.  Every workgroup owns one tile; nothing waits on another workgroup.
-// P::flag(i) says whether item i is kept, P::store(pos, i) writes it at its rank.
-// ---------------------------------------------------------------------------------------
-constexpr int CP_BLOCK = 256, CP_ITEMS = 16, CP_TILE = CP_BLOCK * CP_ITEMS;
-
-template <class P>
-__global__ __launch_bounds__(CP_BLOCK) void compact_count_kernel(P p, u64 n, u64* __restrict__ tile_counts) {
-    __shared__ u32 part[CP_BLOCK / 64];
-    const u64 base = (u64)blockIdx.x * CP_TILE + (u64)threadIdx.x * CP_ITEMS;
-    u32 k = 0;
-    for (int i = 0; i < CP_ITEMS; i++) k += (base + i < n && p.flag(base + i)) ? 1u : 0u;
-    k = wave_sum_u32(k);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = k;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 t = 0;
-        for (int w = 0; w < CP_BLOCK / 64; w++) t += part[w];
-        tile_counts[blockIdx.x] = t;
-    }
-}
-
-template <class P>
-__global__ __launch_bounds__(CP_BLOCK) void compact_write_kernel(P p, u64 n, const u64* __restrict__ tile_incl) {
-    __shared__ u32 part[CP_BLOCK / 64];
-    const u64 base = (u64)blockIdx.x * CP_TILE + (u64)threadIdx.x * CP_ITEMS;
-    u32 keep = 0;
-    for (int i = 0; i < CP_ITEMS; i++)
-        if (base + i < n && p.flag(base + i)) keep |= 1u << i;
-    const u32 k = (u32)__popc(keep);
-    const u32 incl = wave_incl_scan_u32(k);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) part[wave] = incl;
-    __syncthreads();
-    u64 pos = blockIdx.x ? tile_incl[blockIdx.x - 1] : 0;
-    for (int w = 0; w < wave; w++) pos += part[w];
-    pos += incl - k;
-    for (int i = 0; i < CP_ITEMS; i++)
-        if ((keep >> i) & 1u) p.store(pos++, base + i);
-}
-
-// the count pass: *total = kept items; tile_incl (arena, valid until the next arena_reset) feeds compact_write
-template <class P>
-static int compact_count(zk_ctx* c, const P& p, uint64_t n, u64** tile_incl, uint64_t* total) {
-    *total = 0;
-    *tile_incl = nullptr;
-    if (n == 0) return ZK_OK;
-    const u64 tiles = div_up(n, CP_TILE);
-    u64* cnt;
-    ZK_TRY(arena_alloc(c, 8 * tiles, (void**)&cnt));
-    hipLaunchKernelGGL((compact_count_kernel<P>), dim3((u32)tiles), dim3(CP_BLOCK), 0, c->stream, p, (u64)n, cnt);
-    ZK_HIP(c, hipGetLastError());
-    ZK_TRY(scan64_inclusive(c, cnt, tiles));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 49, cnt + tiles - 1, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    ZK_TRY(check_device_error(c));
-    *tile_incl = cnt;
-    *total = c->h_scalars[49];
-    return ZK_OK;
-}
-
-template <class P>
-static int compact_write(zk_ctx* c, const P& p, uint64_t n, const u64* tile_incl) {
-    if (n == 0) return ZK_OK;
-    hipLaunchKernelGGL((compact_write_kernel<P>), dim3((u32)div_up(n, CP_TILE)), dim3(CP_BLOCK), 0, c->stream, p, (u64)n, tile_incl);
-    ZK_HIP(c, hipGetLastError());
-    return ZK_OK;
-}
 
 // ---------------------------------------------------------------------------------------
 // predicates
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ u32 base_code(u32 ch, u32& ok) {     // A0 C1 G2 T/U3 (either case); ok = in AaCcGgTtUu
-    const u32 t = (ch >> 1) & 3u;
-    const u32 d = (ch | 0x20u) - 0x61u;
-    ok = (d <= 20u) ? ((0x180045u >> d) & 1u) : 0u;
-    return t ^ (t >> 1);
-}
 
 struct NewlinePos {      // positions of the '\n' bytes
     const u8* text; u64* out;
@@ -269,35 +196,6 @@ static int bait_table_build(zk_ctx* c, const u8* stream, uint64_t n, int K, zk_b
 // ---------------------------------------------------------------------------------------
 // window lookup: one wave per read
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 spread_bits(u32 v) {      // bit i -> bit 2i
-    u64 x = v;
-    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
-    x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
-    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
-    x = (x | (x << 2)) & 0x3333333333333333ull;
-    x = (x | (x << 1)) & 0x5555555555555555ull;
-    return x;
-}
-__device__ __forceinline__ u32 bits_from(u64 lo, u64 hi, int l) {   // bits l .. l+31 of hi:lo
-    return l ? (u32)((lo >> l) | (hi << (64 - l))) : (u32)lo;
-}
-
-// The window of RK bases that starts at lane l of the 64-byte chunk text[c0, c0 + 64) of a sequence line ending at e
-// (bytes at or past e do not count).  Each lane loads one byte of the chunk (and lanes 0-31 one of the next 32); three
-// ballots per row turn the codes and validity into bit planes, from which every lane cuts its own 2*RK bits.
-// Called by the whole wave (ballots).
-__device__ __forceinline__ bool chunk_window(const u8* __restrict__ text, u64 c0, u64 e, int RK, int lane, u64& x) {
-    u32 ok1 = 0, ok2 = 0, b1 = 0, b2 = 0;
-    if (c0 + lane < e) b1 = base_code(text[c0 + lane], ok1);
-    if (lane < 32 && c0 + 64 + lane < e) b2 = base_code(text[c0 + 64 + lane], ok2);
-    const u64 lo0 = __ballot(ok1 && (b1 & 1u)), lo1 = __ballot(ok1 && (b1 & 2u)), lov = __ballot(ok1 != 0);
-    const u64 hi0 = __ballot(ok2 && (b2 & 1u)), hi1 = __ballot(ok2 && (b2 & 2u)), hiv = __ballot(ok2 != 0);
-    const u32 v = bits_from(lov, hiv, lane);
-    const u32 need = RK >= 32 ? 0xffffffffu : ((1u << RK) - 1u);
-    const u64 z = (spread_bits(__brev(bits_from(lo1, hi1, lane))) << 1) | spread_bits(__brev(bits_from(lo0, hi0, lane)));
-    x = z >> (64 - 2 * RK);
-    return (v & need) == need;
-}
 
 __device__ __forceinline__ u32 wave_min_u32(u32 v) {
 #pragma unroll

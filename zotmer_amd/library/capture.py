@@ -10,14 +10,15 @@ at record ends, and each batch is one zk_line_ends (the record structure), one z
 host copies the gathered bytes back once and appends each bait's span to its file.  The output does not depend on
 where the batches are cut.
 """
+import contextlib
 import gzip
 import os
 import sys
 
 import numpy as np
 
-from zotmer_amd import native
 from zotmer_amd.library import seqio
+from zotmer_amd.library.fastq_batches import record_batches, whole
 from zotmer_amd.library.timing import Phase
 
 READ_K = 25     # reads.reads() is built without K in capture.py:103, so reads.py:38's default applies
@@ -34,68 +35,6 @@ def output_paths(prefix, name, paired, z):
     if paired:
         return [b"%s/%s_1.fastq%s" % (pfx, name, suff), b"%s/%s_2.fastq%s" % (pfx, name, suff)]
     return [b"%s/%s.fastq%s" % (pfx, name, suff)]
-
-
-class _Reader:
-    """One FASTQ input as device text batches of at most `batch` bytes that end at a line end.  Plain and gzip files are
-    read by a zk_source ahead of the device; stdin and .bz2 are read (and decompressed) on the host and uploaded.
-    fill() -> (device buffer, bytes in it, end of input reached); consume(cut) keeps the bytes after `cut` for the next
-    batch (carried to the front of the other buffer) and, with `ahead`, starts reading the next batch behind them.  A
-    context has one staging ring for its zk_sources, so only one request may be in flight at a time: the two mates of a
-    pair are read one after the other (ahead=False), a single input is read ahead of the device."""
-
-    def __init__(self, ctx, path, batch, ahead=True):
-        self.ctx, self.path, self.B, self.ahead = ctx, path, int(batch), ahead
-        self.native = path != "-" and not path.endswith(".bz2") and os.path.isfile(path)
-        self.bufs = [ctx.empty(self.B + 64, np.uint8), ctx.empty(self.B + 64, np.uint8)]
-        self.cur, self.carry, self.eof, self.n, self.ready = 0, 0, False, 0, False
-        self.lines = None
-        if self.native:
-            self.src = ctx.source_open(path)
-            if ahead:
-                self.src.start(self.bufs[0], 0, self.B)
-        else:
-            self.src = seqio.open_binary(path)
-
-    def fill(self):
-        ctx, buf = self.ctx, self.bufs[self.cur]
-        if not self.ready:
-            if self.eof:
-                got = 0
-            elif self.native:
-                if not self.ahead:
-                    self.src.start(buf, self.carry, self.B - self.carry)
-                with Phase(ctx, "wait for the reader"):
-                    got, self.eof = self.src.finish()
-            else:
-                want = self.B - self.carry
-                data = self.src.read(want)
-                got = len(data)
-                self.eof = got < want
-                if got:
-                    ctx._check(ctx.lib.zk_upload(ctx.h, buf.ptr + self.carry, data, got))
-            self.n = self.carry + got
-            if self.eof and self.n and buf.view(1, self.n - 1).to_host()[0] != 10:
-                ctx._check(ctx.lib.zk_upload(ctx.h, buf.ptr + self.n, b"\n", 1))      # the last line counts without a terminator
-                self.n += 1
-            self.ready = True
-        return buf, self.n, self.eof
-
-    def consume(self, cut):
-        ctx = self.ctx
-        buf, nxt = self.bufs[self.cur], self.bufs[1 - self.cur]
-        tail = self.n - cut
-        if tail:
-            ctx._check(ctx.lib.zk_copy(ctx.h, nxt.ptr, buf.ptr + cut, tail))
-            ctx.sync()
-        if self.native and self.ahead and not self.eof:
-            self.src.start(nxt, tail, self.B - tail)          # the next batch streams in while this one is worked on
-        self.carry, self.cur, self.ready = tail, 1 - self.cur, False
-
-    def close(self):
-        if self.src is not None and self.path != "-":
-            self.src.close()
-        self.src = None
 
 
 class Sink:
@@ -131,72 +70,33 @@ def capture_inputs(ctx, table, inputs, paired, sink, batch, verbose=False, veto=
 
 
 def capture_files(ctx, table, paths, sink, batch, verbose=False, veto=None):
-    """One input (or one pair of mates), batch by batch.  Both mates' batches must hold the same reads: each is cut after
-    record r = min(complete records of either), by the device positions of their line ends, and the rest of each is
-    carried into its next batch.  A pair ends with mate 1 (reads.py:95-98); if mate 2 ends first there is a warning
-    (the reference meant to print it at reads.py:101) and the pair ends there.  Returns the number of reads."""
-    readers = []
+    """One input (or one pair of mates), batch by batch (fastq_batches.record_batches: both mates' batches hold the same
+    reads).  A pair ends with mate 1 (reads.py:95-98); if mate 2 ends first there is a warning (the reference meant to print
+    it at reads.py:101) and the pair ends there.  Returns the number of reads."""
     n_reads = 0
     pairs_buf = out_buf = None
-    try:
-        for p in paths:
-            readers.append(_Reader(ctx, p, batch, ahead=len(paths) == 1))
-        while True:
-            filled = [rd.fill() for rd in readers]
-            recs = []
-            for rd, (buf, n, eof) in zip(readers, filled):
-                with Phase(ctx, "line ends", n):
-                    rd.lines = ctx.line_ends(buf.view(n), out=_whole(rd.lines))
-                recs.append(rd.lines.n // 4)
-            r = min(recs)
-            eofs = [f[2] for f in filled]
-            done = eofs[0] and r == recs[0]
-            short = (not done) and len(readers) == 2 and eofs[1] and r == recs[1] < recs[0]
-            if r == 0 and not (done or short):
-                raise IOError("%s: a record longer than the batch size (%d bytes); use a larger -m" % (paths[recs.index(0)], batch))
-            cuts = [int(rd.lines.view(1, 4 * r - 1).to_host()[0]) + 1 if r else 0 for rd in readers]
-            texts = [buf.view(cut) for (buf, _, _), cut in zip(filled, cuts)]
-            lines = [rd.lines.view(4 * r) for rd in readers]
-            if not (done or short):
-                for rd, cut in zip(readers, cuts):
-                    rd.consume(cut)
-            if r:
-                with Phase(ctx, "lookup + sort (%d reads)" % r):
-                    pairs_buf = ctx.capture_hits(table, READ_K, texts[0], lines[0], r,
-                                                 texts[1] if len(texts) == 2 else None, lines[1] if len(lines) == 2 else None,
-                                                 veto=veto, out=_whole(pairs_buf))
-                pairs = pairs_buf
-                if pairs.n:
-                    for mate in range(len(readers)):
-                        with Phase(ctx, "gather", cuts[mate]):
-                            out_buf, pair_spans, byte_spans = ctx.capture_gather(pairs, table.n_records, texts[mate], lines[mate],
-                                                                                 out=_whole(out_buf))
-                        with Phase(ctx, "download", out_buf.n):
-                            host = out_buf.to_host()
-                        with Phase(ctx, "file writes", out_buf.n):
-                            sink.write(mate, host, byte_spans)
-                    for b in np.nonzero(pair_spans[1:] > pair_spans[:-1])[0]:
-                        sink.counts[b] += int(pair_spans[b + 1] - pair_spans[b])
-                n_reads += r
-                if verbose:
-                    sys.stderr.write("%s: %d reads\n" % (" & ".join(os.path.basename(p) for p in paths), n_reads))
-            if short:
-                sys.stderr.write("warning: files had unequal length\n")
-            if done or short:
-                return n_reads
-    finally:
-        for rd in readers:
-            rd.close()
-
-
-def _whole(view):
-    """the full allocation behind a view returned earlier (buffers are reused from batch to batch)"""
-    if view is None:
-        return None
-    base = view
-    while base._keep is not None and isinstance(base._keep, native.DeviceArray):
-        base = base._keep
-    return base
+    with contextlib.closing(record_batches(ctx, paths, batch)) as batches:
+        for texts, lines, r, cuts in batches:
+            with Phase(ctx, "lookup + sort (%d reads)" % r):
+                pairs_buf = ctx.capture_hits(table, READ_K, texts[0], lines[0], r,
+                                             texts[1] if len(texts) == 2 else None, lines[1] if len(lines) == 2 else None,
+                                             veto=veto, out=whole(pairs_buf))
+            pairs = pairs_buf
+            if pairs.n:
+                for mate in range(len(texts)):
+                    with Phase(ctx, "gather", cuts[mate]):
+                        out_buf, pair_spans, byte_spans = ctx.capture_gather(pairs, table.n_records, texts[mate], lines[mate],
+                                                                             out=whole(out_buf))
+                    with Phase(ctx, "download", out_buf.n):
+                        host = out_buf.to_host()
+                    with Phase(ctx, "file writes", out_buf.n):
+                        sink.write(mate, host, byte_spans)
+                for b in np.nonzero(pair_spans[1:] > pair_spans[:-1])[0]:
+                    sink.counts[b] += int(pair_spans[b + 1] - pair_spans[b])
+            n_reads += r
+            if verbose:
+                sys.stderr.write("%s: %d reads\n" % (" & ".join(os.path.basename(p) for p in paths), n_reads))
+    return n_reads
 
 
 def build_table(ctx, records, K):

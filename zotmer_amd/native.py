@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("ZOTK_LIB") or os.path.join(_HERE, "libzotk.so")
 
 ZK_OK, ZK_EINVAL, ZK_ENOMEM, ZK_EHIP, ZK_ENOSPC, ZK_EOVERFLOW, ZK_EINTERNAL, ZK_ERANGE = 0, -1, -2, -3, -4, -5, -6, -7
 KMERIZE_CANONICAL, KMERIZE_BOTH, KMERIZE_SUBSAMPLE, KMERIZE_CANONICAL_ONLY = 0, 1, 2, 4
+STRAND_ORPHANS = 1
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -37,6 +38,11 @@ class Spectrum(C.Structure):
     """zk_spectrum: the sums of one zk_spectrum_sums pass over two spectra (include/zotk.h)"""
     _fields_ = [("n_shared", C.c_uint64), ("s_min", C.c_uint64), ("x_shared", C.c_uint64), ("y_shared", C.c_uint64),
                 ("s_xy_lo", C.c_uint64), ("s_xy_hi", C.c_uint64), ("s_sqrt", C.c_double), ("s_js", C.c_double)]
+
+
+class StrandStats(C.Structure):
+    """zk_strand_stats: what zk_strand_pairs found (include/zotk.h)"""
+    _fields_ = [("n_pairs", C.c_uint64), ("n_orphans", C.c_uint64), ("n_palindromes", C.c_uint64)]
 
 
 class KmerizeStats(C.Structure):
@@ -132,6 +138,9 @@ SIGNATURES = {
     "zk_line_ends": (_i, [_vp, _vp, _u64, _vp, _u64, _pu64]),
     "zk_capture_hits": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _pu64]),
     "zk_capture_gather": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _u64, _pu64, _pu64]),
+    "zk_strand_keys": (_i, [_vp, _vp, _vp, _u64, _i, _i, _u64, _u64, _vp, _u64, _pu64]),
+    "zk_strand_pairs": (_i, [_vp, _vp, _vp, _i, _u64, _i, _u64, _i, _vp, _vp, _u64, C.POINTER(StrandStats)]),
+    "zk_format_pairs": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _pu64]),
 }
 
 _lib = None
@@ -354,7 +363,7 @@ class Context:
     # ---- per-launch timing (HIP events on the ctx stream) -----------------------------------
     PROF_TAGS = {"hist_stream": 1, "hist_array": 2, "pass_stream": 3, "pass_keys": 4, "pass_pairs": 5, "rle": 6,
                  "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
-                 "capture_hits": 15, "project_sum": 16, "spectrum": 17}
+                 "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20}
 
     def tune(self, sort_variant=None, pairs_variant=None, short_sort=None, side_div=None, xcd_group=None, comm_chunk=None,
              early_collapse=None, packed_pairs=None, wide_tiles=None, stream_pass=None, stream_ranges=None, tag_words=None,
@@ -814,6 +823,40 @@ class Context:
             rc = self.lib.zk_capture_gather(*args(out))
         self._check(rc)
         return out.view(n.value), spans[:n_baits + 1], spans[n_baits + 1:]
+
+    # ---- strand bias (csrc/strand_bias.hip) ------------------------------------------------------------------
+    def strand_keys(self, text, lines, n_reads, K, reverse, T, out, offset=0, seed=17):
+        """the kept tagged keys of the first n_reads records of a device FASTQ text, written to out[offset:] (a u64 DeviceArray)
+        -> (keys written or, if they did not fit, needed; whether they fit)"""
+        assert 4 * n_reads <= lines.n and 0 <= offset <= out.n
+        n = C.c_uint64(0)
+        rc = self.lib.zk_strand_keys(self.h, text.ptr, lines.ptr, int(n_reads), int(K), int(bool(reverse)), int(seed), int(T),
+                                     out.ptr + 8 * offset, out.n - offset, C.byref(n))
+        if rc != ZK_ENOSPC:
+            self._check(rc)
+        return n.value, rc == ZK_OK
+
+    def strand_pairs(self, keys, counts, K, orphans=False, seed=17):
+        """ascending distinct tagged keys + counts (u32 | u64) -> (a u64 view, b u64 view, StrandStats): the lines of `zot strand`"""
+        assert counts.n == keys.n
+        a, b = self.empty(keys.n, np.uint64), self.empty(keys.n, np.uint64)
+        st = StrandStats()
+        self._check(self.lib.zk_strand_pairs(self.h, keys.ptr, counts.ptr, counts.dtype.itemsize * 8, keys.n, int(K), int(seed),
+                                             STRAND_ORPHANS if orphans else 0, a.ptr, b.ptr, keys.n, C.byref(st)))
+        return a.view(st.n_pairs), b.view(st.n_pairs), st
+
+    def format_pairs(self, a, b, out=None):
+        """'%d\\t%d\\n' per pair -> uint8 DeviceArray view (out: a buffer to reuse; grown when too small)"""
+        assert a.n == b.n
+        n = C.c_uint64(0)
+        if out is None:
+            out = self.empty(8 * a.n + 1024, np.uint8)
+        rc = self.lib.zk_format_pairs(self.h, a.ptr, b.ptr, a.n, out.ptr, out.n, C.byref(n))
+        if rc == ZK_ENOSPC:
+            out = self.empty(n.value + 1024, np.uint8)
+            rc = self.lib.zk_format_pairs(self.h, a.ptr, b.ptr, a.n, out.ptr, out.n, C.byref(n))
+        self._check(rc)
+        return out.view(n.value)
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
