@@ -140,6 +140,7 @@ int zk_tune(zk_ctx* ctx, int what, int value);
                                    entry, 16 B written per line), one record each */
 #define ZK_PROF_FORMAT_PAIRS 20 /* zk_format_pairs: the length pass (16 B read, 8 written per pair) and the write pass (24 B read per
                                    pair + the text), one record each */
+#define ZK_PROF_PROBE_SCAN 21   /* zk_probe_scan: the one pass over the set (8 B read per entry, whatever the number of windows) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -237,6 +238,24 @@ int zk_strand_pairs(zk_ctx* ctx, const uint64_t* d_keys, const void* d_counts, i
 /* print '%d\t%d' % (ac, bc) (strand.py:155) for n pairs of unsigned 64-bit values: the lines, each ended by '\n', one after the
  * other in d_out.  ZK_ENOSPC with *n_bytes = the size needed if they exceed cap. */
 int zk_format_pairs(zk_ctx* ctx, const uint64_t* d_a, const uint64_t* d_b, uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* n_bytes);
+
+/* ---- probe presence within Hamming distance 2, `zot spoligo` (commands/spoligo.py:50-84) ----------------------------
+ * findApprox(J, v, K, xs, D) asks whether the sorted set holds an entry in [y << s, (y + 1) << s), s = 2 (K - J), for y = v or for
+ * one of v's substitution neighbours -- neigh(J, v, d) (spoligo.py:26-45) is the values at Hamming distance exactly d, d = 1, 2 --
+ * one range search per neighbour (spoligo.py:50-67); findProbe (spoligo.py:69-84) cuts a probe longer than K into its windows of
+ * K bases.  Here one pass over the set answers every window of a panel: for window w, tallies[3 * w + d] (d = 0, 1, 2) = the
+ * number of entries x of d_kmers with ham(x >> 2 * (K - J_w), value_w) == d, ham as basics.ham (basics.py:123-133):
+ * popcount((z | z >> 1) & 0x5555...) of the xor z, so a base that differs in both bits is one mismatch.  Distances of 3 and more
+ * are not counted; findApprox(J, v, K, xs, D) is tallies[3 * w + 0] + ... + tallies[3 * w + D] > 0.
+ * d_kmers: ascending distinct K-mers (the order is not used); 1 <= K <= 32, 1 <= J <= K, value < 4^J, n_windows <=
+ * ZK_PROBE_MAX_WINDOWS -- anything else is ZK_EINVAL before any launch.  windows and tallies are HOST arrays (tallies:
+ * 3 * n_windows words); `reserved` is ignored.  n == 0 writes zeros.  The tallies are sums of integers: the same call returns the
+ * same bits.  ZK_PROBE_TILE = the entries a workgroup takes per step (tests place their sizes around it). */
+#define ZK_PROBE_TILE 4096
+#define ZK_PROBE_MAX_WINDOWS 1024
+typedef struct { uint64_t value; int32_t J; int32_t reserved; } zk_probe_window;
+int zk_probe_scan(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, int K, const zk_probe_window* windows, uint32_t n_windows,
+                  uint64_t* tallies);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("ZOTK_LIB") or os.path.join(_HERE, "libzotk.so")
 ZK_OK, ZK_EINVAL, ZK_ENOMEM, ZK_EHIP, ZK_ENOSPC, ZK_EOVERFLOW, ZK_EINTERNAL, ZK_ERANGE = 0, -1, -2, -3, -4, -5, -6, -7
 KMERIZE_CANONICAL, KMERIZE_BOTH, KMERIZE_SUBSAMPLE, KMERIZE_CANONICAL_ONLY = 0, 1, 2, 4
 STRAND_ORPHANS = 1
+PROBE_TILE, PROBE_MAX_WINDOWS = 4096, 1024      # ZK_PROBE_TILE, ZK_PROBE_MAX_WINDOWS
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -43,6 +44,11 @@ class Spectrum(C.Structure):
 class StrandStats(C.Structure):
     """zk_strand_stats: what zk_strand_pairs found (include/zotk.h)"""
     _fields_ = [("n_pairs", C.c_uint64), ("n_orphans", C.c_uint64), ("n_palindromes", C.c_uint64)]
+
+
+class ProbeWindow(C.Structure):
+    """zk_probe_window: the J bases `value` of a probe, compared with the top J bases of every k-mer (include/zotk.h)"""
+    _fields_ = [("value", C.c_uint64), ("J", C.c_int32), ("reserved", C.c_int32)]
 
 
 class KmerizeStats(C.Structure):
@@ -141,6 +147,7 @@ SIGNATURES = {
     "zk_strand_keys": (_i, [_vp, _vp, _vp, _u64, _i, _i, _u64, _u64, _vp, _u64, _pu64]),
     "zk_strand_pairs": (_i, [_vp, _vp, _vp, _i, _u64, _i, _u64, _i, _vp, _vp, _u64, C.POINTER(StrandStats)]),
     "zk_format_pairs": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _pu64]),
+    "zk_probe_scan": (_i, [_vp, _vp, _u64, _i, C.POINTER(ProbeWindow), _u32, _pu64]),
 }
 
 _lib = None
@@ -363,7 +370,8 @@ class Context:
     # ---- per-launch timing (HIP events on the ctx stream) -----------------------------------
     PROF_TAGS = {"hist_stream": 1, "hist_array": 2, "pass_stream": 3, "pass_keys": 4, "pass_pairs": 5, "rle": 6,
                  "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
-                 "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20}
+                 "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
+                 "probe_scan": 21}
 
     def tune(self, sort_variant=None, pairs_variant=None, short_sort=None, side_div=None, xcd_group=None, comm_chunk=None,
              early_collapse=None, packed_pairs=None, wide_tiles=None, stream_pass=None, stream_ranges=None, tag_words=None,
@@ -857,6 +865,19 @@ class Context:
             rc = self.lib.zk_format_pairs(self.h, a.ptr, b.ptr, a.n, out.ptr, out.n, C.byref(n))
         self._check(rc)
         return out.view(n.value)
+
+    # ---- probe presence (csrc/probe_scan.hip) -----------------------------------------------------------------
+    def probe_scan(self, kmers, K, windows):
+        """windows = [(J, value), ...]: per window the number of k-mers whose top J bases are at Hamming distance 0, 1 and 2 of
+        value -> an (n_windows, 3) uint64 array.  Lists longer than PROBE_MAX_WINDOWS take several calls."""
+        out = np.zeros((len(windows), 3), dtype=np.uint64)
+        for lo in range(0, len(windows), PROBE_MAX_WINDOWS):
+            part = windows[lo:lo + PROBE_MAX_WINDOWS]
+            arr = (ProbeWindow * len(part))(*[ProbeWindow(int(v), int(J), 0) for J, v in part])
+            t = np.zeros(3 * len(part), dtype=np.uint64)
+            self._check(self.lib.zk_probe_scan(self.h, kmers.ptr, kmers.n, int(K), arr, len(part), t.ctypes.data_as(_pu64)))
+            out[lo:lo + len(part)] = t.reshape(-1, 3)
+        return out
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
