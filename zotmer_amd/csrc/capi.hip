@@ -127,22 +127,16 @@ __global__ void lower_bound_kernel(const u64* __restrict__ a, u64 n, const u64* 
     pos[t] = lo;
 }
 
-static u32 grid_for(zk_ctx* c, u64 n, u64 per_block) {
-    u64 g = div_up(n, per_block), mx = (u64)c->num_cus * 16;
-    return (u32)(g < mx ? (g ? g : 1) : mx);
-}
 }  // namespace zk
 
 using namespace zk;
-
-#define ZK_ARGS(c, cond) do { if (!(c)) return ZK_EINVAL; zk::enter(c); if (!(cond)) return zk::fail((c), ZK_EINVAL, "bad argument: %s", #cond); } while (0)
 
 extern "C" {
 
 int zk_pack_reads(zk_ctx* c, const uint8_t* d_bases, const uint64_t* d_offs, uint64_t n_reads, uint8_t* d_stream) {
     ZK_ARGS(c, d_offs && d_stream);
     if (n_reads == 0) return ZK_OK;
-    hipLaunchKernelGGL(pack_reads_kernel, dim3(grid_for(c, n_reads, 4)), dim3(256), 0, c->stream, d_bases, (const u64*)d_offs, (u64)n_reads, d_stream);
+    hipLaunchKernelGGL(pack_reads_kernel, dim3(grid_cap(c, div_up(n_reads, 4), 16)), dim3(256), 0, c->stream, d_bases, (const u64*)d_offs, (u64)n_reads, d_stream);
     ZK_HIP(c, hipGetLastError());
     return ZK_OK;
 }
@@ -355,22 +349,22 @@ int zk_synth_reads(zk_ctx* c, uint64_t seed, uint64_t first, uint64_t count, int
     ZK_ARGS(c, L >= 1 && (genome == 0 || genome >= (uint64_t)L));
     if (count == 0) return ZK_OK;
     SynthArgs a{seed, first, count, L, genome, sub_thr, n_thr};
-    hipLaunchKernelGGL(synth_kernel, dim3(grid_for(c, count * (uint64_t)(L + 1), 256 * 16)), dim3(256), 0, c->stream, a, d_stream);
+    hipLaunchKernelGGL(synth_kernel, dim3(grid_cap(c, div_up(count * (uint64_t)(L + 1), 256 * 16), 16)), dim3(256), 0, c->stream, a, d_stream);
     ZK_HIP(c, hipGetLastError());
     return ZK_OK;
 }
 
 int zk_checksum(zk_ctx* c, const uint64_t* d_kmers, const uint32_t* d_counts, uint64_t n, uint64_t sums[3]) {
     ZK_ARGS(c, sums);
-    u64* d = c->d_scalars + 12;
+    u64* d = c->d_scalars->checksum;
     ZK_HIP(c, hipMemsetAsync(d, 0, 3 * sizeof(u64), c->stream));
     if (n) {
-        hipLaunchKernelGGL(checksum_kernel, dim3(grid_for(c, n, 256 * 8)), dim3(256), 0, c->stream, (const u64*)d_kmers, d_counts, (u64)n, d);
+        hipLaunchKernelGGL(checksum_kernel, dim3(grid_cap(c, div_up(n, 256 * 8), 16)), dim3(256), 0, c->stream, (const u64*)d_kmers, d_counts, (u64)n, d);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 12, d, 3 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 3; i++) sums[i] = c->h_scalars[12 + i];
+    ZK_TRY(fetch(c, &c->h_scalars->checksum));
+    ZK_TRY(stream_sync(c));
+    for (int i = 0; i < 3; i++) sums[i] = c->h_scalars->checksum[i];
     return ZK_OK;
 }
 
@@ -383,15 +377,15 @@ int zk_capture_filter(zk_ctx* c, const uint8_t* d_stream, uint64_t n_bytes, int 
 
 int zk_stream_checksum(zk_ctx* c, const uint8_t* d_stream, uint64_t n_bytes, int K, uint64_t sums[7]) {
     ZK_ARGS(c, sums && K >= 1 && K <= 32 && (((uintptr_t)d_stream) & 15) == 0);
-    u64* d = c->d_scalars + 12;
+    u64* d = c->d_scalars->stream_checksum;
     ZK_HIP(c, hipMemsetAsync(d, 0, 7 * sizeof(u64), c->stream));
     if (n_bytes) {
-        hipLaunchKernelGGL(stream_checksum_kernel, dim3(grid_for(c, n_bytes, (u64)CS_BLOCK * CS_SEG)), dim3(CS_BLOCK), 0, c->stream, d_stream, (u64)n_bytes, K, d);
+        hipLaunchKernelGGL(stream_checksum_kernel, dim3(grid_cap(c, div_up(n_bytes, (u64)CS_BLOCK * CS_SEG), 16)), dim3(CS_BLOCK), 0, c->stream, d_stream, (u64)n_bytes, K, d);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 12, d, 7 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 7; i++) sums[i] = c->h_scalars[12 + i];
+    ZK_TRY(fetch(c, &c->h_scalars->stream_checksum));
+    ZK_TRY(stream_sync(c));
+    for (int i = 0; i < 7; i++) sums[i] = c->h_scalars->stream_checksum[i];
     return ZK_OK;
 }
 

@@ -185,9 +185,7 @@ static int bait_table_build(zk_ctx* c, const u8* stream, uint64_t n, int K, zk_b
     t->bits = bits;
     const u64 nb = 1ull << bits;
     ZK_TRY(tmalloc(c, (void**)&t->dir, 4 * (nb + 1)));
-    u64 g = div_up(nb + 1, 256);
-    if (g > (u64)c->num_cus * 16) g = (u64)c->num_cus * 16;
-    hipLaunchKernelGGL(dir_kernel, dim3((u32)g), dim3(256), 0, c->stream, t->keys, (u64)n_keys, t->kbits - bits, nb, t->dir);
+    hipLaunchKernelGGL(dir_kernel, dim3(grid_cap(c, div_up(nb + 1, 256), 16)), dim3(256), 0, c->stream, t->keys, (u64)n_keys, t->kbits - bits, nb, t->dir);
     ZK_HIP(c, hipGetLastError());
     ZK_HIP(c, hipStreamSynchronize(c->stream));
     return check_device_error(c);
@@ -251,19 +249,17 @@ static int capture_hits(zk_ctx* c, const zk_bait_table* baits, const zk_bait_tab
                         uint64_t n_reads, u64* pairs, uint64_t cap, uint64_t* n_pairs) {
     *n_pairs = 0;
     if (n_reads == 0 || baits->n_keys == 0) return ZK_OK;
-    u64* d_raw = c->d_scalars + 48;
+    u64* d_raw = &c->d_scalars->capture_raw;
     ZK_HIP(c, hipMemsetAsync(d_raw, 0, sizeof(u64), c->stream));
-    u64 g = div_up(n_reads, 4);
-    if (g > (u64)c->num_cus * 16) g = (u64)c->num_cus * 16;
     prof_begin(c, ZK_PROF_CAPTURE_HITS, 0);
-    hipLaunchKernelGGL(capture_hits_kernel, dim3((u32)g), dim3(256), 0, c->stream, view_of(baits), view_of(veto), RK, m1, m2,
+    hipLaunchKernelGGL(capture_hits_kernel, dim3(grid_cap(c, div_up(n_reads, 4), 16)), dim3(256), 0, c->stream, view_of(baits), view_of(veto), RK, m1, m2,
                        (u64)n_reads, pairs, (u64)cap, d_raw);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 48, d_raw, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    ZK_TRY(fetch(c, &c->h_scalars->capture_raw));
+    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
-    const uint64_t raw = c->h_scalars[48];
+    const uint64_t raw = c->h_scalars->capture_raw;
     if (raw > cap) {
         *n_pairs = raw;
         return fail(c, ZK_ENOSPC, "capture: %llu (bait, read) pairs before deduplication, room for %llu", (unsigned long long)raw,
@@ -353,16 +349,12 @@ static int capture_gather(zk_ctx* c, const u64* pairs, uint64_t n, uint32_t nb, 
     u64 *len, *d_spans;
     ZK_TRY(arena_alloc(c, 8 * n + 8, (void**)&len));
     ZK_TRY(arena_alloc(c, 16ull * (nb + 1), (void**)&d_spans));
-    u64 g = div_up(n, 256);
-    if (g > (u64)c->num_cus * 16) g = (u64)c->num_cus * 16;
     if (n) {
-        hipLaunchKernelGGL(record_len_kernel, dim3((u32)g), dim3(256), 0, c->stream, pairs, (u64)n, text, lines, (u64)n_lines, len, c->d_err);
+        hipLaunchKernelGGL(record_len_kernel, dim3(grid_cap(c, div_up(n, 256), 16)), dim3(256), 0, c->stream, pairs, (u64)n, text, lines, (u64)n_lines, len, c->d_err);
         ZK_HIP(c, hipGetLastError());
         ZK_TRY(scan64_inclusive(c, len, n));
     }
-    u64 gs = div_up((u64)nb + 1, 256);
-    if (gs > (u64)c->num_cus * 16) gs = (u64)c->num_cus * 16;
-    hipLaunchKernelGGL(bait_spans_kernel, dim3((u32)gs), dim3(256), 0, c->stream, pairs, (u64)n, len, nb, d_spans);
+    hipLaunchKernelGGL(bait_spans_kernel, dim3(grid_cap(c, div_up((u64)nb + 1, 256), 16)), dim3(256), 0, c->stream, pairs, (u64)n, len, nb, d_spans);
     ZK_HIP(c, hipGetLastError());
     ZK_HIP(c, hipMemcpyAsync(spans, d_spans, 16ull * (nb + 1), hipMemcpyDeviceToHost, c->stream));
     ZK_HIP(c, hipStreamSynchronize(c->stream));
@@ -372,9 +364,7 @@ static int capture_gather(zk_ctx* c, const u64* pairs, uint64_t n, uint32_t nb, 
     if (total > cap)
         return fail(c, ZK_ENOSPC, "capture gather: %llu bytes of records, room for %llu", (unsigned long long)total, (unsigned long long)cap);
     if (n) {
-        u64 gw = div_up(n, 4);
-        if (gw > (u64)c->num_cus * 16) gw = (u64)c->num_cus * 16;
-        hipLaunchKernelGGL(record_copy_kernel, dim3((u32)gw), dim3(256), 0, c->stream, pairs, (u64)n, text, lines, (u64)n_lines, len, out);
+        hipLaunchKernelGGL(record_copy_kernel, dim3(grid_cap(c, div_up(n, 4), 16)), dim3(256), 0, c->stream, pairs, (u64)n, text, lines, (u64)n_lines, len, out);
         ZK_HIP(c, hipGetLastError());
     }
     ZK_HIP(c, hipStreamSynchronize(c->stream));
@@ -384,8 +374,6 @@ static int capture_gather(zk_ctx* c, const u64* pairs, uint64_t n, uint32_t nb, 
 }  // namespace zk
 
 using namespace zk;
-
-#define ZK_ARGS(c, cond) do { if (!(c)) return ZK_EINVAL; zk::enter(c); if (!(cond)) return zk::fail((c), ZK_EINVAL, "bad argument: %s", #cond); } while (0)
 
 extern "C" {
 

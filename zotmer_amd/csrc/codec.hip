@@ -151,7 +151,7 @@ int scan64_inclusive(zk_ctx* c, u64* d_v, uint64_t n) {
     CdState s2;
     s2.tiles = (u32)div_up(n, SCAN_TILE);
     ZK_TRY(lookback_begin(c, 2ull * s2.tiles, s2.tiles, &s2.epoch, &s2.ticket_base));
-    s2.status = c->status; s2.ticket = c->d_ticket; s2.err = c->d_err; s2.d_total = c->d_scalars + 9;
+    s2.status = c->status; s2.ticket = c->d_ticket; s2.err = c->d_err; s2.d_total = &c->d_scalars->total;
     hipLaunchKernelGGL(scan64_kernel, dim3(s2.tiles), dim3(CD_BLOCK), 0, c->stream, d_v, (u64)n, c->status, c->status + s2.tiles, s2);
     ZK_HIP(c, hipGetLastError());
     return ZK_OK;
@@ -164,8 +164,7 @@ __global__ void add_u64_kernel(u64* __restrict__ v, u64 n, u64 x) {
 // v[i] += x for i < n (asynchronous)
 int add_u64(zk_ctx* c, u64* d_v, uint64_t n, u64 x) {
     if (n == 0 || x == 0) return ZK_OK;
-    u64 g = div_up(n, 256 * 8), mx = (u64)c->num_cus * 16;
-    hipLaunchKernelGGL(add_u64_kernel, dim3((u32)(g < mx ? g : mx)), dim3(256), 0, c->stream, d_v, (u64)n, x);
+    hipLaunchKernelGGL(add_u64_kernel, dim3(grid_cap(c, div_up(n, 256 * 8), 16)), dim3(256), 0, c->stream, d_v, (u64)n, x);
     ZK_HIP(c, hipGetLastError());
     return ZK_OK;
 }
@@ -176,12 +175,12 @@ int codec_decode(zk_ctx* c, const u64* d_words, uint64_t nw, int delta, u64* d_o
     CdState st;
     st.tiles = (u32)div_up(nw, DEC_TILE);
     ZK_TRY(lookback_begin(c, st.tiles, st.tiles, &st.epoch, &st.ticket_base));
-    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = c->d_scalars + 9;
+    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = &c->d_scalars->total;
     hipLaunchKernelGGL(decode_kernel, dim3(st.tiles), dim3(CD_BLOCK), 0, c->stream, d_words, (u64)nw, d_out, (u64)cap, st);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    const uint64_t n = c->h_scalars[9];
+    ZK_TRY(fetch(c, &c->h_scalars->total));
+    ZK_TRY(stream_sync(c));
+    const uint64_t n = c->h_scalars->total;
     *n_out = n;                      // also when the output was too small: lets the caller size it
     ZK_TRY(check_device_error(c));
     if (delta && n) {
@@ -330,20 +329,18 @@ static int codec_encode_t(zk_ctx* c, const T* d_vals, uint64_t n, int delta, u64
     u8* len;
     ZK_TRY(arena_require(c, n + (1 << 20), n + (1 << 20)));
     ZK_TRY(arena_alloc(c, n + 64, (void**)&len));
-    u64 g = div_up(n, 256 * 8);
-    if (g > (u64)c->num_cus * 16) g = (u64)c->num_cus * 16;
-    hipLaunchKernelGGL((enc_len_kernel<T>), dim3((u32)g), dim3(256), 0, c->stream, d_vals, (u64)n, delta, len, c->d_err);
+    hipLaunchKernelGGL((enc_len_kernel<T>), dim3(grid_cap(c, div_up(n, 256 * 8), 16)), dim3(256), 0, c->stream, d_vals, (u64)n, delta, len, c->d_err);
     ZK_HIP(c, hipGetLastError());
     CdState st;
     st.tiles = (u32)div_up(n, ENC_TILE);
     ZK_TRY(lookback_begin(c, 2ull * st.tiles, st.tiles, &st.epoch, &st.ticket_base));
-    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = c->d_scalars + 9;
+    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = &c->d_scalars->total;
     hipLaunchKernelGGL((encode_kernel<T>), dim3(st.tiles), dim3(CD_BLOCK), 0, c->stream, d_vals, (u64)n, delta, len, d_words, (u64)cap,
                        c->status + st.tiles, st);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *n_words = c->h_scalars[9];
+    ZK_TRY(fetch(c, &c->h_scalars->total));
+    ZK_TRY(stream_sync(c));
+    *n_words = c->h_scalars->total;
     return check_device_error(c);
 }
 int codec_encode(zk_ctx* c, const u64* d_vals, uint64_t n, int delta, u64* d_words, uint64_t cap, uint64_t* n_words) {
@@ -409,12 +406,12 @@ int fastq_mask(zk_ctx* c, const u8* d_text, uint64_t n, uint32_t line_phase, u8*
     CdState st;
     st.tiles = (u32)div_up(n, FQ_TILE);
     ZK_TRY(lookback_begin(c, st.tiles, st.tiles, &st.epoch, &st.ticket_base));
-    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = c->d_scalars + 9;
+    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = &c->d_scalars->total;
     hipLaunchKernelGGL(fastq_mask_kernel, dim3(st.tiles), dim3(CD_BLOCK), 0, c->stream, d_text, (u64)n, line_phase & 3u, d_out, st);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *n_newlines = c->h_scalars[9];
+    ZK_TRY(fetch(c, &c->h_scalars->total));
+    ZK_TRY(stream_sync(c));
+    *n_newlines = c->h_scalars->total;
     return check_device_error(c);
 }
 

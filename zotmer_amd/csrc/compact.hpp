@@ -58,11 +58,11 @@ static int compact_count(zk_ctx* c, const P& p, uint64_t n, u64** tile_incl, uin
     hipLaunchKernelGGL((compact_count_kernel<P>), dim3((u32)tiles), dim3(CP_BLOCK), 0, c->stream, p, (u64)n, cnt);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(scan64_inclusive(c, cnt, tiles));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 49, cnt + tiles - 1, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    ZK_TRY(fetch(c, &c->h_scalars->compact_total, cnt + tiles - 1));
+    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     *tile_incl = cnt;
-    *total = c->h_scalars[49];
+    *total = c->h_scalars->compact_total;
     return ZK_OK;
 }
 

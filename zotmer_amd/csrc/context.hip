@@ -126,6 +126,17 @@ int part16_begin(zk_ctx* c, uint64_t words, unsigned short** out) {
     return ZK_OK;
 }
 
+int fetch_span(zk_ctx* c, void* h_first, size_t bytes, const void* from) {
+    if (!from) from = (const char*)c->d_scalars + ((const char*)h_first - (const char*)c->h_scalars);
+    ZK_HIP(c, hipMemcpyAsync(h_first, from, bytes, hipMemcpyDeviceToHost, c->stream));
+    return ZK_OK;
+}
+
+int stream_sync(zk_ctx* c) {
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    return ZK_OK;
+}
+
 int check_device_error(zk_ctx* c) {
     u32 e = 0;
     ZK_HIP(c, hipMemcpyAsync(&e, c->d_err, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
@@ -214,8 +225,8 @@ zk_ctx* zk_create(int device, uint64_t workspace_bytes) {
     c->own_stream = true;
     ZK_CREATE_STEP(hipMalloc((void**)&c->d_ticket, sizeof(u32)));
     ZK_CREATE_STEP(hipMalloc((void**)&c->d_err, sizeof(u32)));
-    ZK_CREATE_STEP(hipMalloc((void**)&c->d_scalars, 64 * sizeof(u64)));
-    ZK_CREATE_STEP(hipHostMalloc((void**)&c->h_scalars, 64 * sizeof(u64), hipHostMallocDefault));
+    ZK_CREATE_STEP(hipMalloc((void**)&c->d_scalars, sizeof(zk_scalars)));
+    ZK_CREATE_STEP(hipHostMalloc((void**)&c->h_scalars, sizeof(zk_scalars), hipHostMallocDefault));
     // On the context's OWN stream, then waited for: hipMemset runs on the null stream, asynchronously for device memory, and a
     // non-blocking stream does not order against it -- with other threads keeping the null stream busy the clear of the
     // ticket counter could land in the middle of this context's first kernel (duplicate tickets, no scanner, spin timeout).
@@ -223,7 +234,7 @@ zk_ctx* zk_create(int device, uint64_t workspace_bytes) {
     ZK_CREATE_STEP(hipMalloc((void**)&c->d_xticket, 8 * 32 * sizeof(u32)));
     ZK_CREATE_STEP(hipMemsetAsync(c->d_xticket, 0, 8 * 32 * sizeof(u32), c->stream));
     ZK_CREATE_STEP(hipMemsetAsync(c->d_err, 0, sizeof(u32), c->stream));
-    ZK_CREATE_STEP(hipMemsetAsync(c->d_scalars, 0, 64 * sizeof(u64), c->stream));
+    ZK_CREATE_STEP(hipMemsetAsync(c->d_scalars, 0, sizeof(zk_scalars), c->stream));
     ZK_CREATE_STEP(hipStreamSynchronize(c->stream));
     c->num_xcd = probe_xcds(c);
     if (workspace_bytes) {

@@ -294,12 +294,12 @@ int zk_last_newline(zk_ctx* c, const uint8_t* d_text, uint64_t n, uint64_t* cut)
     enter(c);
     *cut = 0;
     if (n == 0) return ZK_OK;
-    u64* d = c->d_scalars + 19;
+    u64* d = &c->d_scalars->ingest_cut;
     hipLaunchKernelGGL(last_newline_kernel, dim3(1), dim3(1024), 0, c->stream, (const u8*)d_text, (u64)n, d);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 19, d, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *cut = c->h_scalars[19];
+    ZK_TRY(fetch(c, &c->h_scalars->ingest_cut));
+    ZK_TRY(stream_sync(c));
+    *cut = c->h_scalars->ingest_cut;
     return ZK_OK;
 }
 

@@ -1,6 +1,7 @@
 // internal.hpp -- host-side context shared by the libzotk translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
@@ -8,6 +9,65 @@
 
 #include "../../include/zotk.h"
 #include "common.hpp"
+
+// Small results (a total, a flag, a few sums) travel from the kernels to the host through one block of device words and its
+// pinned mirror.  One field per purpose: a new kernel adds a field here, it never borrows one.  Kernels only ever get raw
+// pointers into the device block, so the layout is free to change -- except where a comment below says that fields are
+// adjacent: those are written through one pointer or copied as one range (ZK_SPAN), and the static_asserts after the struct
+// hold them in place.  A u32 counter keeps a whole u64 word (kernels take (u32*)&field, the host reads the low half).
+struct zk_strand_counters { u32 n_declined, fail; };   // strand_blocks.hip: the union kernel's declined blocks, the big-block kernel's give-up flag
+struct zk_scalars {
+    // -- adjacent: rle_prefix reads back [rle_side .. total], the merges [total .. acgt], sort_stream [acgt .. sample_n] --
+    u64 rle_side;            // rle_prefix: entries on the side list
+    u64 total;               // SHARED BY DESIGN: the look-back total of the launch in flight, written by every SelState / MergeState / KwayState /
+                             // tile-sort-count / collapse kernel (select, setops, kway, codec, tilesort, radix_sort) and read back right after it
+    u64 acgt[4];             // base totals: column_sum of encode_list / union_sum / kway_union_sum, the stream histogram
+    u64 n_keys;              // hist_scan_kernel: live keys of a sort
+    u64 rec_info[3];         // first_newline_kernel + the stream histogram: first newline, newlines, bad bytes (one pointer)
+    u64 sample_n;            // (u32) StreamSample: keys set aside; cleared together with rec_info
+    // -- adjacent: dedupe_pass clears and reads back [dedupe_flags .. dedupe_n_bad] as one range --
+    u64 dedupe_flags, dedupe_n_retry, dedupe_counter, dedupe_n_big, dedupe_n_bad;   // (u32 each) DedupeArgs
+    // -- no order below this line --
+    u64 dedupe_n_in;         // landing: cuts[chunks]
+    u64 dedupe_n_out;        // landing: incl[chunks - 1]
+    zk_strand_counters strand;
+    u64 hist_big_n;          // count_hist: counts >= HIST_DENSE
+    u64 capture_kept;        // capture_filter
+    u64 capture_raw;         // capture.hip
+    u64 intersect_n;         // intersect_count
+    u64 checksum[3];         // zk_checksum
+    u64 checksum_any[3];     // checksum_any
+    u64 stream_checksum[7];  // zk_stream_checksum
+    u64 first_descent;       // zk_first_descent
+    u64 ingest_cut;          // ingest.hip
+    u64 sample_heads;        // sample_heads
+    u64 rle_overflow;        // (u32) rle, packed: a count beyond the field
+    u64 reduce_max;          // (u32) reduce_by_key: largest sum
+    u64 max_u32;             // (u32) pipeline.hip max_u32
+    u64 palindromes;         // pipeline.hip count_palindromes
+    u64 tag_nseg;            // (u32) tag_pass.hip: segments planned
+    u64 tile_declined;       // (u32) tilesort.hip: a tile declined
+    u64 strand_cursor;       // strand_keys: keys written
+    u64 strand_sums[2];      // strand_pairs: orphans, palindromes
+    u64 strand_n_pairs;      // landing: strand_pairs' last tile total
+    u64 format_bytes;        // landing: format_pairs' last line end
+    u64 compact_total;       // landing: compact_count's last tile total
+    u64 project_heads;       // landing: project_sum's last tile total
+    u64 project_total;       // project_sum: column_sum of the tiles' sums
+    u64 spectrum[8];         // landing: spectrum_sums' partial sums (SP_WORDS)
+};
+// bytes of the fields first .. last (declared in that order, adjacent)
+#define ZK_SPAN(first, last) (offsetof(zk_scalars, last) + sizeof(zk_scalars::last) - offsetof(zk_scalars, first))
+static_assert(sizeof(zk_scalars) == 61 * sizeof(u64), "zk_scalars: u64 words only, no padding");
+static_assert(ZK_SPAN(rle_side, total) == 2 * sizeof(u64), "rle_prefix reads rle_side and total back as one range");
+static_assert(ZK_SPAN(total, acgt) == 5 * sizeof(u64), "the merges read total and acgt back as one range");
+static_assert(ZK_SPAN(acgt, n_keys) == 5 * sizeof(u64) && ZK_SPAN(acgt, sample_n) == 9 * sizeof(u64),
+              "sort_stream reads acgt, n_keys, rec_info and sample_n back as one range");
+static_assert(ZK_SPAN(rec_info, sample_n) == 4 * sizeof(u64), "sort_stream clears rec_info and sample_n as one range");
+static_assert(offsetof(zk_scalars, dedupe_n_retry) == offsetof(zk_scalars, dedupe_flags) + 8 &&
+              offsetof(zk_scalars, dedupe_counter) == offsetof(zk_scalars, dedupe_flags) + 16 &&
+              offsetof(zk_scalars, dedupe_n_big) == offsetof(zk_scalars, dedupe_flags) + 24 &&
+              ZK_SPAN(dedupe_flags, dedupe_n_bad) == 5 * sizeof(u64), "dedupe_pass clears and reads its five words as one range");
 
 struct zk_ctx {
     int device = 0;
@@ -68,8 +128,8 @@ struct zk_ctx {
     u32 ticket_base = 0;
 
     u32* d_err = nullptr;      // device error word
-    u64* d_scalars = nullptr;  // 64 device scalars for small results
-    u64* h_scalars = nullptr;  // pinned mirror
+    zk_scalars* d_scalars = nullptr;  // small results of the kernels, on the device (kernels get pointers to its fields)
+    zk_scalars* h_scalars = nullptr;  // pinned mirror: fetch() fills a field, stream_sync() makes it readable
 
     std::string last_error;
     u64* dbg = nullptr;        // diagnostic stamp buffer (zk_debug_buffer), normally null
@@ -104,6 +164,8 @@ static inline void enter(zk_ctx* c) {
         if (e__ != hipSuccess)                                                                  \
             return zk::fail((c), ZK_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
     } while (0)
+// the argument check every C-ABI entry starts with
+#define ZK_ARGS(c, cond) do { if (!(c)) return ZK_EINVAL; zk::enter(c); if (!(cond)) return zk::fail((c), ZK_EINVAL, "bad argument: %s", #cond); } while (0)
 #define ZK_TRY(expr)             \
     do {                         \
         int r__ = (expr);        \
@@ -127,7 +189,19 @@ void prof_begin(zk_ctx* c, int tag, uint64_t algorithmic_bytes);
 void prof_end(zk_ctx* c);
 void prof_add_bytes(zk_ctx* c, int tag, uint64_t bytes);   // to the tag's last record: bytes written that only the launch's result tells
 
+// Reading small results back.  fetch_span queues the copy of `bytes` device bytes into the pinned block, starting at the field
+// h_first of *c->h_scalars: from that field's own device copy, or from `from` (arena memory) when h_first is a pure landing.
+// The host may read the field after stream_sync (or check_device_error, which synchronises too).
+int fetch_span(zk_ctx* c, void* h_first, size_t bytes, const void* from = nullptr);
+template <class T> static inline int fetch(zk_ctx* c, T* h_field, const void* from = nullptr) { return fetch_span(c, h_field, sizeof(T), from); }
+int stream_sync(zk_ctx* c);
+
 static inline uint64_t div_up(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
+// a grid of `blocks` workgroups, at most per_cu of them for every CU (the kernels stride over what is left)
+static inline u32 grid_cap(const zk_ctx* c, uint64_t blocks, int per_cu) {
+    const uint64_t mx = (uint64_t)c->num_cus * per_cu;
+    return (u32)(blocks < mx ? blocks : mx);
+}
 
 // ---- launchers implemented in the kernel files (all asynchronous on c->stream) -------------
 // radix_sort.hip

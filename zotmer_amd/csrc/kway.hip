@@ -305,7 +305,7 @@ int kway_union_sum(zk_ctx* c, int k, const u64* const* keys, const void* const* 
     ZK_HIP(c, hipGetLastError());
     KwayState st = {};
     ZK_TRY(lookback_begin(c, tiles, tiles, &st.epoch, &st.ticket_base));
-    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = c->d_scalars + 9; st.tiles = tiles;
+    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = &c->d_scalars->total; st.tiles = tiles;
 #ifdef ZK_PHASES
     st.dbg_nolook = getenv("ZK_KWAY_NOLOOK") ? atoi(getenv("ZK_KWAY_NOLOOK")) : 0;
 #endif
@@ -317,12 +317,12 @@ int kway_union_sum(zk_ctx* c, int k, const u64* const* keys, const void* const* 
 #undef ZK_KW
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    if (acgt_w) ZK_TRY(column_sum(c, rows, tiles, 4, c->d_scalars + 0));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, sizeof(u64) * 16, hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *n_out = c->h_scalars[9];
+    if (acgt_w) ZK_TRY(column_sum(c, rows, tiles, 4, c->d_scalars->acgt));
+    ZK_TRY(fetch_span(c, &c->h_scalars->total, ZK_SPAN(total, acgt)));
+    ZK_TRY(stream_sync(c));
+    *n_out = c->h_scalars->total;
     prof_add_bytes(c, ZK_PROF_UNION, (8 + cb) * *n_out);
-    if (acgt_w) for (int b = 0; b < 4; b++) acgt_w[b] = c->h_scalars[b];
+    if (acgt_w) for (int b = 0; b < 4; b++) acgt_w[b] = c->h_scalars->acgt[b];
     return check_device_error(c);
 }
 

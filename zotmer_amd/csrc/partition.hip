@@ -146,20 +146,19 @@ __global__ void checksum_any_kernel(const u64* __restrict__ k, const CT* __restr
 }
 
 int checksum_any(zk_ctx* c, const u64* keys, const void* cnts, int count_bits, uint64_t n, uint64_t sums[3]) {
-    u64* d = c->d_scalars + 12;
+    u64* d = c->d_scalars->checksum_any;
     ZK_HIP(c, hipMemsetAsync(d, 0, 3 * sizeof(u64), c->stream));
     if (n) {
-        u64 g = div_up(n, 256 * 8), mx = (u64)c->num_cus * 16;
-        const u32 grid = (u32)(g < mx ? g : mx);
+        const u32 grid = grid_cap(c, div_up(n, 256 * 8), 16);
         if (count_bits == 32)
             hipLaunchKernelGGL((checksum_any_kernel<u32>), dim3(grid), dim3(256), 0, c->stream, keys, (const u32*)cnts, (u64)n, d);
         else
             hipLaunchKernelGGL((checksum_any_kernel<u64>), dim3(grid), dim3(256), 0, c->stream, keys, (const u64*)cnts, (u64)n, d);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 12, d, 3 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 3; i++) sums[i] = c->h_scalars[12 + i];
+    ZK_TRY(fetch(c, &c->h_scalars->checksum_any));
+    ZK_TRY(stream_sync(c));
+    for (int i = 0; i < 3; i++) sums[i] = c->h_scalars->checksum_any[i];
     return ZK_OK;
 }
 
@@ -219,8 +218,7 @@ int zk_can(zk_ctx* c, int K, const uint64_t* d_kmers, uint64_t n, uint64_t* d_ou
     enter(c);
     if (K < 1 || K > 32 || (n && (!d_kmers || !d_out))) return fail(c, ZK_EINVAL, "zk_can: bad argument");
     if (n == 0) return ZK_OK;
-    u64 g = div_up(n, 256 * 8), mx = (u64)c->num_cus * 16;
-    hipLaunchKernelGGL(can_kernel, dim3((u32)(g < mx ? g : mx)), dim3(256), 0, c->stream, (const u64*)d_kmers, (u64)n, K, (u64*)d_out);
+    hipLaunchKernelGGL(can_kernel, dim3(grid_cap(c, div_up(n, 256 * 8), 16)), dim3(256), 0, c->stream, (const u64*)d_kmers, (u64)n, K, (u64*)d_out);
     ZK_HIP(c, hipGetLastError());
     return ZK_OK;
 }
@@ -249,16 +247,15 @@ int zk_first_descent(zk_ctx* c, const uint64_t* d_kmers, uint64_t n, uint64_t* f
     if (!c) return ZK_EINVAL;
     enter(c);
     if (!first_bad || (n && !d_kmers)) return fail(c, ZK_EINVAL, "zk_first_descent: bad argument");
-    u64* d = c->d_scalars + 12;
+    u64* d = &c->d_scalars->first_descent;
     ZK_HIP(c, hipMemsetAsync(d, 0xff, sizeof(u64), c->stream));
     if (n > 1) {
-        const u64 g = (n + 255) / 256, mx = (u64)c->num_cus * 16;
-        hipLaunchKernelGGL(first_descent_kernel, dim3((u32)(g < mx ? g : mx)), dim3(256), 0, c->stream, (const u64*)d_kmers, (u64)n, d);
+        hipLaunchKernelGGL(first_descent_kernel, dim3(grid_cap(c, div_up(n, 256), 16)), dim3(256), 0, c->stream, (const u64*)d_kmers, (u64)n, d);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 12, d, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *first_bad = c->h_scalars[12] == ~0ull ? n : c->h_scalars[12];
+    ZK_TRY(fetch(c, &c->h_scalars->first_descent));
+    ZK_TRY(stream_sync(c));
+    *first_bad = c->h_scalars->first_descent == ~0ull ? n : c->h_scalars->first_descent;
     return ZK_OK;
 }
 
@@ -279,8 +276,7 @@ int zk_synth_keys(zk_ctx* c, uint64_t seed, uint64_t first, uint64_t count, int 
     if (top >> 64) return fail(c, ZK_EINVAL, "zk_synth_keys: mul * (first + count) + add overflows 64 bits");
     if (count == 0) return ZK_OK;
     const u64 mask = key_bits == 64 ? ~0ull : ((1ull << key_bits) - 1);
-    u64 g = div_up(count, 256 * 8), mx = (u64)c->num_cus * 16;
-    hipLaunchKernelGGL(synth_keys_kernel, dim3((u32)(g < mx ? g : mx)), dim3(256), 0, c->stream, (u64)seed, (u64)first, (u64)count,
+    hipLaunchKernelGGL(synth_keys_kernel, dim3(grid_cap(c, div_up(count, 256 * 8), 16)), dim3(256), 0, c->stream, (u64)seed, (u64)first, (u64)count,
                        (u64)mul, (u64)add, (u64)mod, mask, (u64*)d_out);
     ZK_HIP(c, hipGetLastError());
     return ZK_OK;
@@ -290,8 +286,7 @@ int zk_synth_counts(zk_ctx* c, uint64_t seed, const uint64_t* d_keys, uint64_t n
     if (!c) return ZK_EINVAL;
     enter(c);
     if (n == 0) return ZK_OK;
-    u64 g = div_up(n, 256 * 8), mx = (u64)c->num_cus * 16;
-    hipLaunchKernelGGL(synth_counts_kernel, dim3((u32)(g < mx ? g : mx)), dim3(256), 0, c->stream, (u64)seed, (const u64*)d_keys, (u64)n,
+    hipLaunchKernelGGL(synth_counts_kernel, dim3(grid_cap(c, div_up(n, 256 * 8), 16)), dim3(256), 0, c->stream, (u64)seed, (const u64*)d_keys, (u64)n,
                        (u64*)d_counts);
     ZK_HIP(c, hipGetLastError());
     return ZK_OK;

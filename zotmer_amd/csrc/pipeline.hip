@@ -115,15 +115,9 @@ __global__ void widen_kernel(const u32* __restrict__ in, u64* __restrict__ out, 
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (u64)gridDim.x * blockDim.x) out[i] = in[i];
 }
 
-static u32 ew_grid(zk_ctx* c, u64 n) {
-    u64 g = div_up(n, 256);
-    u64 mx = (u64)c->num_cus * 16;
-    return (u32)(g < mx ? (g ? g : 1) : mx);
-}
-
 int widen_counts(zk_ctx* c, const u32* in, u64* out, uint64_t n) {
     if (n == 0) return ZK_OK;
-    hipLaunchKernelGGL(widen_kernel, dim3(ew_grid(c, n)), dim3(256), 0, c->stream, in, out, (u64)n);
+    hipLaunchKernelGGL(widen_kernel, dim3(grid_cap(c, div_up(n, 256), 16)), dim3(256), 0, c->stream, in, out, (u64)n);
     ZK_HIP(c, hipGetLastError());
     return ZK_OK;
 }
@@ -157,15 +151,15 @@ __global__ void max_u32_kernel(const u32* __restrict__ v, u64 n, u32* out) {
 }
 
 static int max_u32(zk_ctx* c, const u32* v, uint64_t n, uint64_t* out) {
-    u32* d = (u32*)(c->d_scalars + 26);
+    u32* d = (u32*)&c->d_scalars->max_u32;
     ZK_HIP(c, hipMemsetAsync(d, 0, sizeof(u64), c->stream));
     if (n) {
-        hipLaunchKernelGGL(max_u32_kernel, dim3(ew_grid(c, n)), dim3(256), 0, c->stream, v, (u64)n, d);
+        hipLaunchKernelGGL(max_u32_kernel, dim3(grid_cap(c, div_up(n, 256), 16)), dim3(256), 0, c->stream, v, (u64)n, d);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 26, c->d_scalars + 26, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *out = c->h_scalars[26] & 0xffffffffull;
+    ZK_TRY(fetch(c, &c->h_scalars->max_u32));
+    ZK_TRY(stream_sync(c));
+    *out = c->h_scalars->max_u32 & 0xffffffffull;
     return ZK_OK;
 }
 
@@ -179,14 +173,14 @@ __global__ void palindromes_kernel(const u64* __restrict__ v, u64 n, int K, unsi
 }
 
 static int count_palindromes(zk_ctx* c, const u64* v, uint64_t n, int K, uint64_t* out) {
-    ZK_HIP(c, hipMemsetAsync(c->d_scalars + 26, 0, sizeof(u64), c->stream));
+    ZK_HIP(c, hipMemsetAsync(&c->d_scalars->palindromes, 0, sizeof(u64), c->stream));
     if (n) {
-        hipLaunchKernelGGL(palindromes_kernel, dim3(ew_grid(c, n)), dim3(256), 0, c->stream, v, (u64)n, K, (unsigned long long*)(c->d_scalars + 26));
+        hipLaunchKernelGGL(palindromes_kernel, dim3(grid_cap(c, div_up(n, 256), 16)), dim3(256), 0, c->stream, v, (u64)n, K, (unsigned long long*)&c->d_scalars->palindromes);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 26, c->d_scalars + 26, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *out = c->h_scalars[26];
+    ZK_TRY(fetch(c, &c->h_scalars->palindromes));
+    ZK_TRY(stream_sync(c));
+    *out = c->h_scalars->palindromes;
     return ZK_OK;
 }
 
@@ -241,7 +235,7 @@ static int mirror_union(zk_ctx* c, const u64* sorted, const u32* cnt, uint64_t u
         hipLaunchKernelGGL(mirror_sizes_kernel, dim3(groups / 256), dim3(256), 0, c->stream, (const u64*)start, gbits, incl);
         ZK_TRY(scan64_inclusive(c, incl, groups));
         hipLaunchKernelGGL(mirror_place_kernel, dim3(groups / 256), dim3(256), 0, c->stream, (const u64*)start, (const u64*)incl, gbits, place);
-        hipLaunchKernelGGL(mirror_copy_kernel, dim3(ew_grid(c, uc)), dim3(256), 0, c->stream, sorted, cnt, (u64)uc, K, gbits, (const u64*)place, rk, rv, pack, mh);
+        hipLaunchKernelGGL(mirror_copy_kernel, dim3(grid_cap(c, div_up(uc, 256), 16)), dim3(256), 0, c->stream, sorted, cnt, (u64)uc, K, gbits, (const u64*)place, rk, rv, pack, mh);
         prof_end(c);
         ZK_HIP(c, hipGetLastError());
         if (pack) {
@@ -665,12 +659,12 @@ static int kmerize_short(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, i
     u32* pv = (u32*)(aux + 2 * a8); u32* pv2 = (u32*)(aux + 2 * a8 + a4);
     if (um) {
         prof_begin(c, ZK_PROF_MIRROR, 24 * um);
-        hipLaunchKernelGGL(mirror_kernel, dim3(ew_grid(c, um)), dim3(256), 0, c->stream, sorted, cnt, (u64)um, K, pk, pv);
+        hipLaunchKernelGGL(mirror_kernel, dim3(grid_cap(c, div_up(um, 256), 16)), dim3(256), 0, c->stream, sorted, cnt, (u64)um, K, pk, pv);
         prof_end(c);
         ZK_HIP(c, hipGetLastError());
     }
     if (ns) {
-        hipLaunchKernelGGL(side_expand_kernel, dim3(ew_grid(c, ns)), dim3(256), 0, c->stream, side_k, side_c, (u64)ns, K, pk + um, pv + um);
+        hipLaunchKernelGGL(side_expand_kernel, dim3(grid_cap(c, div_up(ns, 256), 16)), dim3(256), 0, c->stream, side_k, side_c, (u64)ns, K, pk + um, pv + um);
         ZK_HIP(c, hipGetLastError());
     }
     u64* sk; u32* sv;

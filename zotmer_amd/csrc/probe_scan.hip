@@ -93,8 +93,7 @@ static int probe_scan(zk_ctx* c, const u64* keys, uint64_t n, int K, const zk_pr
         params[W + w] = PB_LOW_BITS & ~((1ull << shift) - 1);          // bits above 2K are zero in every entry and every value
     }
     const u64 tiles = div_up(n, PB_TILE);
-    u64 grid = (u64)c->num_cus * 8;
-    if (grid > tiles) grid = tiles;
+    const u64 grid = grid_cap(c, tiles, 8);
     // the LDS tally is 32 bits wide: a workgroup must see fewer than 2^32 entries in one launch
     if (div_up(tiles, grid) * PB_TILE >= 1ull << 32)
         return fail(c, ZK_EINVAL, "zk_probe_scan: %llu entries are more than one launch can tally", (unsigned long long)n);

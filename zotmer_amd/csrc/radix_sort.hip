@@ -1979,8 +1979,8 @@ struct Sorter {
                            u64* sample = nullptr, u32 sample_cap = 0, int sample_shift = 0, u64 sample_value = 0) {
         HistArgs h;
         h.sample = sample; h.sample_cap = sample_cap; h.sample_shift = sample_shift; h.sample_value = sample_value;
-        h.sample_n = (u32*)(c->d_scalars + 23);
-        if (sample) ZK_HIP(c, hipMemsetAsync(c->d_scalars + 23, 0, sizeof(u64), c->stream));
+        h.sample_n = (u32*)&c->d_scalars->sample_n;
+        if (sample) ZK_HIP(c, hipMemsetAsync(h.sample_n, 0, sizeof(u64), c->stream));
         h.src = src;
         h.plan = plan;
         h.ghist = ghist;
@@ -1989,12 +1989,12 @@ struct Sorter {
         h.rec_info = nullptr;
         ZK_HIP(c, hipMemsetAsync(ghist, 0, sizeof(u64) * MAX_PASSES * C::RADIX, c->stream));
         if (SRC == SRC_STREAM && src.n_bytes) {
-            h.rec_info = c->d_scalars + 20;
+            h.rec_info = c->d_scalars->rec_info;
             ZK_HIP(c, hipMemsetAsync(h.rec_info, 0, 3 * sizeof(u64), c->stream));
             hipLaunchKernelGGL(first_newline_kernel, dim3(1), dim3(256), 0, c->stream, src.stream, (u64)src.n_bytes, h.rec_info);
         }
         if (acgt) ZK_HIP(c, hipMemsetAsync(acgt, 0, sizeof(u64) * 4, c->stream));
-        u32 grid = h.tiles < (u32)(c->num_cus * 8) ? h.tiles : (u32)(c->num_cus * 8);
+        u32 grid = grid_cap(c, h.tiles, 8);
         if (grid == 0) grid = 1;
         prof_begin(c, SRC == SRC_STREAM ? ZK_PROF_HIST_STREAM : ZK_PROF_HIST_ARRAY, SRC == SRC_STREAM ? src.n_bytes : 8 * src.n);
         if constexpr (SRC == SRC_STREAM && C::ITEMS == 16 && C::BLOCK <= 512) {
@@ -2021,10 +2021,10 @@ struct Sorter {
         a.kin = keys; a.n = n;
         a.prof_tag = prof_tag;      // the upper-bit passes over collapsed / packed lists are timed apart
         if (counted) {
-            hipLaunchKernelGGL(hist_scan_kernel, dim3(1), dim3(256), 0, c->stream, ghist, plan.passes, (int)C::RADIX, c->d_scalars + 8);
+            hipLaunchKernelGGL(hist_scan_kernel, dim3(1), dim3(256), 0, c->stream, ghist, plan.passes, (int)C::RADIX, &c->d_scalars->n_keys);
             ZK_HIP(c, hipGetLastError());
         } else {
-            ZK_TRY(launch_hist<SRC_ARRAY>(c, a, plan, ghist, nullptr, c->d_scalars + 8));
+            ZK_TRY(launch_hist<SRC_ARRAY>(c, a, plan, ghist, nullptr, &c->d_scalars->n_keys));
         }
         u64* in = keys; u64* out = alt;
         for (int p = 0; p < plan.passes; p++) {
@@ -2050,7 +2050,7 @@ struct Sorter {
         ZK_TRY(arena_alloc(c, sizeof(u64) * MAX_PASSES * C::RADIX, (void**)&ghist));
         SortArgs a = {};
         a.kin = mirror_K ? src_k : keys; a.n = n; a.mirror_K = mirror_K;
-        ZK_TRY(launch_hist<SRC_ARRAY>(c, a, plan, ghist, nullptr, c->d_scalars + 8));
+        ZK_TRY(launch_hist<SRC_ARRAY>(c, a, plan, ghist, nullptr, &c->d_scalars->n_keys));
         const u64* in = mirror_K ? src_k : keys; const u32* vi = mirror_K ? src_v : vals;
         u64* out = mirror_K ? keys : alt; u32* vo = mirror_K ? vals : valt;
         for (int p = 0; p < plan.passes; p++) {
@@ -2092,8 +2092,8 @@ struct Sorter {
         ZK_TRY(arena_alloc(c, sizeof(u64) * MAX_PASSES * C::RADIX, (void**)&ghist));
         SortArgs a = {};
         a.stream = src.stream; a.n_bytes = src.n_bytes; a.K = src.K; a.mode = src.mode;
-        u64* d_acgt = c->d_scalars + 0;
-        u64* d_n = c->d_scalars + 8;
+        u64* d_acgt = c->d_scalars->acgt;
+        u64* d_n = &c->d_scalars->n_keys;
         // the look before the sort (StreamSample): the set-aside keys go to the second sort buffer, which is idle until pass 1
         const u32 sample_cap = 1u << 20;
         const bool sampling = src.sample && cap >= 4ull * sample_cap && src.mode == ZK_KEYS_CANONICAL;
@@ -2101,12 +2101,12 @@ struct Sorter {
         const bool ranged = c->stream_pass != 0;          // (ZK_KEYS_BOTH: the two strands of a range as two ranges)
         StreamRows srows;
         if (ranged) {
-            u64* rec_info = c->d_scalars + 20;
-            ZK_HIP(c, hipMemsetAsync(rec_info, 0, 4 * sizeof(u64), c->stream));          // [20..22] the records, [23] the sample counter
+            u64* rec_info = c->d_scalars->rec_info;
+            ZK_HIP(c, hipMemsetAsync(rec_info, 0, ZK_SPAN(rec_info, sample_n), c->stream));          // the records and the sample counter
             hipLaunchKernelGGL(first_newline_kernel, dim3(1), dim3(256), 0, c->stream, src.stream, (u64)src.n_bytes, rec_info);
             ZK_TRY(stream_hist(c, src.stream, src.n_bytes, src.K, src.mode, plan, ghist, (u32)C::RADIX, d_acgt, d_n, rec_info,
                                sampling ? buf_b : nullptr, sample_cap, sampling ? src.sample->shift : 0, sampling ? src.sample->value : 0,
-                               (u32*)(c->d_scalars + 23),
+                               (u32*)&c->d_scalars->sample_n,
                                // the stream's image goes behind the set-aside keys in the second sort buffer (idle until pass 1)
                                (char*)buf_b + (sampling ? 24ull * sample_cap : 0), 8 * cap - (sampling ? 24ull * sample_cap : 0), &srows));
             hipLaunchKernelGGL(hist_scan_kernel, dim3(1), dim3(256), 0, c->stream, ghist, plan.passes, (int)C::RADIX, d_n);
@@ -2116,10 +2116,10 @@ struct Sorter {
                                            sampling ? src.sample->shift : 0, sampling ? src.sample->value : 0));
         }
         // the number of live keys decides the grids of the array passes: one small readback
-        ZK_HIP(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, sizeof(u64) * 24, hipMemcpyDeviceToHost, c->stream));
-        ZK_HIP(c, hipStreamSynchronize(c->stream));
-        const uint64_t n = c->h_scalars[8];
-        if (acgt) for (int b = 0; b < 4; b++) acgt[b] = c->h_scalars[b];
+        ZK_TRY(fetch_span(c, c->h_scalars->acgt, ZK_SPAN(acgt, sample_n)));
+        ZK_TRY(stream_sync(c));
+        const uint64_t n = c->h_scalars->n_keys;
+        if (acgt) for (int b = 0; b < 4; b++) acgt[b] = c->h_scalars->acgt[b];
 #ifdef ZK_PHASES
         // measurement of the histogram kernel with fewer LDS adds than it needs (tools/p0_phases.py): its counts are wrong, nothing
         // may be sorted by them
@@ -2129,7 +2129,7 @@ struct Sorter {
         if (n > cap) return fail(c, ZK_ENOSPC, "sort buffers hold %llu keys, the stream has %llu", (unsigned long long)cap, (unsigned long long)n);
         if (n == 0) return ZK_OK;
         if (sampling) {
-            uint64_t sn = c->h_scalars[23] & 0xffffffffull;
+            uint64_t sn = c->h_scalars->sample_n & 0xffffffffull;
             if (sn > sample_cap) sn = sample_cap;
             src.sample->seen = sn;
             if (sn >= 4096) {          // enough to judge
@@ -2145,7 +2145,7 @@ struct Sorter {
         a.kout = buf_a; a.shift = plan.shift[0]; a.bits = plan.bits[0]; a.ghist = ghist;
         a.n = n;
         if (ranged) {
-            const uint64_t first_nl = c->h_scalars[20], nl = c->h_scalars[21], bad = c->h_scalars[22];
+            const uint64_t first_nl = c->h_scalars->rec_info[0], nl = c->h_scalars->rec_info[1], bad = c->h_scalars->rec_info[2];
             const bool uniform = first_nl < 0x7fffffffull && src.n_bytes % (first_nl + 1) == 0 && bad == 0 && nl == src.n_bytes / (first_nl + 1);
             // The usual plan (two passes over the top bits, tags for the block dedupe): pass 0 leaves the keys as two arrays, low words and
             // next digits, 6 bytes a key, and the second pass is tag_pass.hip's count / scan / scatter over static segments -- done here.
@@ -2174,7 +2174,7 @@ struct Sorter {
             // Uniform records (checked by the histogram kernel: the only newlines are one every `rec` bytes): tiles follow
             // the records, so that no key slot is spent on the windows that run into a separator (17 % of the
             // positions for 150-base reads and K = 25).  Any other stream: tiles of TILE positions.
-            const uint64_t first_nl = c->h_scalars[20], nl = c->h_scalars[21], bad = c->h_scalars[22];
+            const uint64_t first_nl = c->h_scalars->rec_info[0], nl = c->h_scalars->rec_info[1], bad = c->h_scalars->rec_info[2];
             if (src.mode != ZK_KEYS_BOTH && first_nl < 0x7fffffffull) {
                 const uint64_t rec = first_nl + 1;
                 const int64_t W = (int64_t)first_nl - src.K + 1;
@@ -2380,8 +2380,7 @@ __global__ void expand_tags_kernel(const u32* __restrict__ tags, const u64* __re
 
 int expand_tags(zk_ctx* c, const u32* tags, const u64* cuts, uint32_t blocks, int tag_bits, u64* keys_out, uint64_t first_block, uint64_t n_blocks) {
     if (n_blocks == 0) { first_block = 0; n_blocks = blocks; }
-    const uint64_t mx = (uint64_t)c->num_cus * 16;
-    hipLaunchKernelGGL(expand_tags_kernel, dim3((u32)(n_blocks < mx ? n_blocks : mx)), dim3(256), 0, c->stream, tags, cuts, (u64)first_block, (u64)n_blocks,
+    hipLaunchKernelGGL(expand_tags_kernel, dim3(grid_cap(c, n_blocks, 16)), dim3(256), 0, c->stream, tags, cuts, (u64)first_block, (u64)n_blocks,
                        tag_bits, keys_out);
     ZK_HIP(c, hipGetLastError());
     return ZK_OK;
@@ -2410,14 +2409,14 @@ int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int
     if (!tags) hipLaunchKernelGGL(dedupe_cuts_kernel, dim3((u32)div_up(chunks + 1, 256)), dim3(256), 0, c->stream, keys, (u64)n, a.tag_bits, (u32)chunks, cuts);
     a.kin = keys; a.tin = tags; a.n = n; a.cuts = cuts; a.out = work; a.nwords = nwords; a.pack = pack;
     a.chunks = (u32)chunks;
-    a.flags = (u32*)(c->d_scalars + 27);
-    a.counter = (u32*)(c->d_scalars + 29);
-    a.n_big = (u32*)(c->d_scalars + 30);
+    a.flags = (u32*)&c->d_scalars->dedupe_flags;
+    a.counter = (u32*)&c->d_scalars->dedupe_counter;
+    a.n_big = (u32*)&c->d_scalars->dedupe_n_big;
     a.big = big; a.big_cap = big_cap;
     const u32 bad_cap = 64;
     ZK_TRY(arena_alloc(c, sizeof(u32) * bad_cap, (void**)&a.bad));
     a.bad_cap = bad_cap;
-    a.n_bad = (u32*)(c->d_scalars + 31);
+    a.n_bad = (u32*)&c->d_scalars->dedupe_n_bad;
     a.dbg = c->dbg ? c->dbg + 8192 : nullptr;
     // the mirror sort can group by 6 more bits if the blocks say how their entries split on them: 64 counts per block, when the
     // workspace has the room (and the finer grouping's tables after it: dedupe_finish)
@@ -2426,7 +2425,7 @@ int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int
     unsorted = unsorted && two_per_cu;          // (dedupe_kernel's blocks leave it sorted)
     if (!max_chunks && !unsorted && a.tag_bits >= 14 && c->arena_size - c->arena_off > 64ull * chunks * (4 + 8 + 8) + (32ull << 20) + n / 16)
         ZK_TRY(arena_alloc(c, sizeof(u32) * 64 * chunks, (void**)&a.sub));
-    ZK_HIP(c, hipMemsetAsync(c->d_scalars + 27, 0, 5 * sizeof(u64), c->stream));
+    ZK_HIP(c, hipMemsetAsync(&c->d_scalars->dedupe_flags, 0, ZK_SPAN(dedupe_flags, dedupe_n_bad), c->stream));
     // algorithmic bytes: every key read once (a 32-bit tag, or the whole key), one word written per distinct key (added below, once
     // the launch has said how many)
     prof_begin(c, ZK_PROF_RLE, (tags ? 4 : 8) * n);
@@ -2438,30 +2437,30 @@ int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int
     };
     if (two_per_cu) {
         ZK_TRY(arena_alloc(c, sizeof(u32) * chunks, (void**)&a.retry));
-        a.n_retry = (u32*)(c->d_scalars + 28);
+        a.n_retry = (u32*)&c->d_scalars->dedupe_n_retry;
         a.limit = (u32)c->dedupe_limit;
         ZK_TRY(launch_dedupe2(c, a, tags != nullptr, c->dedupe_variant, unsorted));
     } else launch_one_per_cu(a);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 27, c->d_scalars + 27, 5 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 32, cuts + chunks, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    ZK_TRY(fetch_span(c, &c->h_scalars->dedupe_flags, ZK_SPAN(dedupe_flags, dedupe_n_bad)));
+    ZK_TRY(fetch(c, &c->h_scalars->dedupe_n_in, cuts + chunks));
     ZK_TRY(check_device_error(c));
-    if (two_per_cu && (uint32_t)c->h_scalars[28]) {
+    if (two_per_cu && (uint32_t)c->h_scalars->dedupe_n_retry) {
         // the blocks dedupe2_kernel declined (65 536 keys or more; a table that filled up): dedupe_kernel's table is larger and its
         // counts are 32 bits wide -- what it declines too goes on the list the host counts by sorting
         DedupeArgs d = a;
-        d.list = a.retry; d.chunks = (uint32_t)c->h_scalars[28]; d.retry = nullptr; d.n_retry = nullptr;
+        d.list = a.retry; d.chunks = (uint32_t)c->h_scalars->dedupe_n_retry; d.retry = nullptr; d.n_retry = nullptr;
         ZK_HIP(c, hipMemsetAsync(a.counter, 0, sizeof(u32), c->stream));
         launch_one_per_cu(d);
         ZK_HIP(c, hipGetLastError());
-        ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 27, c->d_scalars + 27, 5 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        ZK_TRY(fetch_span(c, &c->h_scalars->dedupe_flags, ZK_SPAN(dedupe_flags, dedupe_n_bad)));
         ZK_TRY(check_device_error(c));
     }
-    r->flags = (uint32_t)c->h_scalars[27];
-    r->n_big = (uint32_t)c->h_scalars[30];
+    r->flags = (uint32_t)c->h_scalars->dedupe_flags;
+    r->n_big = (uint32_t)c->h_scalars->dedupe_n_big;
     if (r->n_big > big_cap) r->flags |= 1;          // more counts beyond the field than the side list holds: the long way
-    const uint32_t n_bad = (uint32_t)c->h_scalars[31];
+    const uint32_t n_bad = (uint32_t)c->h_scalars->dedupe_n_bad;
     if (n_bad && n_bad <= bad_cap && !(r->flags & 1) && !max_chunks) {
         // The few blocks whose table filled up (a stretch of the key space with more distinct k-mers than a table holds) are
         // counted the plain way, one by one: their keys sorted by the bits below the block bits (the block's own place in `work`
@@ -2491,13 +2490,13 @@ int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int
     } else if (n_bad > bad_cap) r->flags |= 1;
     ZK_HIP(c, hipMemcpyAsync(incl, nwords, sizeof(u64) * chunks, hipMemcpyDeviceToDevice, c->stream));
     ZK_TRY(scan64_inclusive(c, incl, chunks));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, incl + chunks - 1, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    r->n_out = c->h_scalars[9];
+    ZK_TRY(fetch(c, &c->h_scalars->dedupe_n_out, incl + chunks - 1));
+    ZK_TRY(stream_sync(c));
+    r->n_out = c->h_scalars->dedupe_n_out;
     prof_add_bytes(c, ZK_PROF_RLE, 8 * r->n_out);          // one word written per distinct key
     r->cuts = cuts; r->nwords = nwords; r->incl = incl; r->big = big; r->chunks = (uint32_t)chunks; r->pack = pack; r->work = work; r->sub = a.sub;
     r->tag_bits = a.tag_bits; r->unsorted = unsorted;
-    if (n_in) *n_in = c->h_scalars[32];          // keys covered by the blocks that were counted
+    if (n_in) *n_in = c->h_scalars->dedupe_n_in;          // keys covered by the blocks that were counted
     return ZK_OK;
 }
 
@@ -2567,15 +2566,15 @@ int collapse_pass(zk_ctx* c, const u64* keys, uint64_t n, int shift, int bits, i
     a.split = (1u << pack) <= (u32)TILE;
     a.tiles = (u32)tiles;
     ZK_TRY(lookback_begin(c, tiles, (u32)tiles, &a.epoch, &a.ticket_base));
-    a.status = c->status; a.ticket = c->d_ticket; a.err = c->d_err; a.d_total = c->d_scalars + 9;
+    a.status = c->status; a.ticket = c->d_ticket; a.err = c->d_err; a.d_total = &c->d_scalars->total;
     prof_begin(c, ZK_PROF_RLE, 8 * n);
     if (bits <= 8) hipLaunchKernelGGL(collapse_kernel<8>, dim3((u32)tiles), dim3(512), 0, c->stream, a);
     else hipLaunchKernelGGL(collapse_kernel<9>, dim3((u32)tiles), dim3(512), 0, c->stream, a);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    ZK_TRY(fetch(c, &c->h_scalars->total));
     ZK_TRY(check_device_error(c));
-    *n_out = c->h_scalars[9];
+    *n_out = c->h_scalars->total;
     return ZK_OK;
 }
 

@@ -353,18 +353,18 @@ int rle_prefix(zk_ctx* c, const u64* sorted, uint64_t n, int pshift, u64* uniq, 
     SelState st;
     st.tiles = (u32)div_up(n, RLE_TILE);
     ZK_TRY(lookback_begin(c, st.tiles, st.tiles, &st.epoch, &st.ticket_base));
-    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = c->d_scalars + 9;
-    u64* d_side = c->d_scalars + 10;
+    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = &c->d_scalars->total;
+    u64* d_side = &c->d_scalars->rle_side;
     ZK_HIP(c, hipMemsetAsync(d_side, 0, sizeof(u64), c->stream));
     prof_begin(c, ZK_PROF_RLE, 8 * n);
     hipLaunchKernelGGL(rle_prefix_kernel, dim3(st.tiles), dim3(RLE_BLOCK), 0, c->stream, sorted, (u64)n, pshift, uniq, counts, (u64)cap,
                        side_k, side_c, (u64)side_cap, d_side, st);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *n_main = c->h_scalars[9];
-    *n_side = c->h_scalars[10];
+    ZK_TRY(fetch_span(c, &c->h_scalars->rle_side, ZK_SPAN(rle_side, total)));
+    ZK_TRY(stream_sync(c));
+    *n_main = c->h_scalars->total;
+    *n_side = c->h_scalars->rle_side;
     return check_device_error(c);
 }
 
@@ -481,14 +481,14 @@ int reduce_by_key(zk_ctx* c, const u64* sorted, const u32* w, uint64_t n, u64* u
     *n_out = 0;
     if (max_sum) *max_sum = 0;
     if (n == 0) return ZK_OK;
-    u32* d_max = max_sum ? (u32*)(c->d_scalars + 25) : nullptr;
+    u32* d_max = max_sum ? (u32*)&c->d_scalars->reduce_max : nullptr;
     if (d_max) ZK_HIP(c, hipMemsetAsync(d_max, 0, sizeof(u64), c->stream));
     SelState st;
     st.tiles = (u32)div_up(n, RLE_TILE);
     u32* lead;
     ZK_TRY(arena_alloc(c, sizeof(u32) * st.tiles, (void**)&lead));
     ZK_TRY(lookback_begin(c, st.tiles, st.tiles, &st.epoch, &st.ticket_base));
-    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = c->d_scalars + 9;
+    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = &c->d_scalars->total;
     prof_begin(c, ZK_PROF_SELECT, (pack ? 8 : 12) * n);
     hipLaunchKernelGGL(reduce_by_key_kernel, dim3(st.tiles), dim3(RLE_BLOCK), 0, c->stream, sorted, w, (u64)n, uniq, sums, (u64)cap, lead, st,
                        pack, d_max);
@@ -497,11 +497,11 @@ int reduce_by_key(zk_ctx* c, const u64* sorted, const u32* w, uint64_t n, u64* u
     hipLaunchKernelGGL(reduce_fixup_kernel, dim3((u32)div_up(st.tiles, 256)), dim3(256), 0, c->stream, lead, c->status, st.tiles, sums,
                        (u64)cap, c->d_err, d_max);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    if (d_max) ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 25, c->d_scalars + 25, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *n_out = c->h_scalars[9];
-    if (max_sum) *max_sum = c->h_scalars[25] & 0xffffffffull;
+    ZK_TRY(fetch(c, &c->h_scalars->total));
+    if (d_max) ZK_TRY(fetch(c, &c->h_scalars->reduce_max));
+    ZK_TRY(stream_sync(c));
+    *n_out = c->h_scalars->total;
+    if (max_sum) *max_sum = c->h_scalars->reduce_max & 0xffffffffull;
     return check_device_error(c);
 }
 
@@ -520,13 +520,13 @@ int sample_heads(zk_ctx* c, const u64* keys, uint64_t n, uint64_t* sampled, uint
     const uint64_t m = n < (1ull << 18) ? n : (1ull << 18);
     *sampled = m; *heads = m;
     if (m == 0) return ZK_OK;
-    u64* d = c->d_scalars + 23;
+    u64* d = &c->d_scalars->sample_heads;
     ZK_HIP(c, hipMemsetAsync(d, 0, sizeof(u64), c->stream));
     hipLaunchKernelGGL(sample_heads_kernel, dim3(64), dim3(256), 0, c->stream, keys, (u64)m, d);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 23, d, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *heads = c->h_scalars[23];
+    ZK_TRY(fetch(c, &c->h_scalars->sample_heads));
+    ZK_TRY(stream_sync(c));
+    *heads = c->h_scalars->sample_heads;
     return ZK_OK;
 }
 
@@ -562,14 +562,14 @@ int rle(zk_ctx* c, const u64* sorted, uint64_t n, u64* uniq, u32* counts, uint64
     *n_unique = 0;
     if (overflow) *overflow = false;
     if (n == 0) return ZK_OK;
-    u32* d_ovf = (u32*)(c->d_scalars + 24);
+    u32* d_ovf = (u32*)&c->d_scalars->rle_overflow;
     if (pack) ZK_HIP(c, hipMemsetAsync(d_ovf, 0, sizeof(u64), c->stream));
     SelState st;
     st.tiles = (u32)div_up(n, RLE_TILE);
     u32* lead;
     ZK_TRY(arena_alloc(c, sizeof(u32) * st.tiles, (void**)&lead));
     ZK_TRY(lookback_begin(c, st.tiles, st.tiles, &st.epoch, &st.ticket_base));
-    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = c->d_scalars + 9;
+    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = &c->d_scalars->total;
     prof_begin(c, ZK_PROF_RLE, 8 * n);
     hipLaunchKernelGGL(rle_kernel, dim3(st.tiles), dim3(RLE_BLOCK), 0, c->stream, sorted, (u64)n, uniq, counts, (u64)cap, lead, st, pack, d_ovf);
     prof_end(c);
@@ -577,11 +577,11 @@ int rle(zk_ctx* c, const u64* sorted, uint64_t n, u64* uniq, u32* counts, uint64
     hipLaunchKernelGGL(rle_fixup_kernel, dim3((u32)div_up(st.tiles, 256)), dim3(256), 0, c->stream, lead, c->status, st.tiles,
                        counts, (u64)cap, c->d_err, uniq, pack, d_ovf);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    if (pack) ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 24, c->d_scalars + 24, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *n_unique = c->h_scalars[9];
-    if (pack && overflow) *overflow = (c->h_scalars[24] & 0xffffffffull) != 0;
+    ZK_TRY(fetch(c, &c->h_scalars->total));
+    if (pack) ZK_TRY(fetch(c, &c->h_scalars->rle_overflow));
+    ZK_TRY(stream_sync(c));
+    *n_unique = c->h_scalars->total;
+    if (pack && overflow) *overflow = (c->h_scalars->rle_overflow & 0xffffffffull) != 0;
     ZK_TRY(check_device_error(c));
     return ZK_OK;
 }
@@ -683,14 +683,14 @@ static int run_select(zk_ctx* c, const Op& op, uint64_t n, uint64_t cap, uint64_
     SelState st;
     st.tiles = (u32)div_up(n, SEL_TILE);
     ZK_TRY(lookback_begin(c, st.tiles, st.tiles, &st.epoch, &st.ticket_base));
-    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = c->d_scalars + 9;
+    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = &c->d_scalars->total;
     prof_begin(c, ZK_PROF_SELECT, sizeof(typename Op::R) * n);
     hipLaunchKernelGGL((select_kernel<Op>), dim3(st.tiles), dim3(SEL_BLOCK), 0, c->stream, op, (u64)n, (u64)cap, st);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *n_out = c->h_scalars[9];
+    ZK_TRY(fetch(c, &c->h_scalars->total));
+    ZK_TRY(stream_sync(c));
+    *n_out = c->h_scalars->total;
     return check_device_error(c);
 }
 
@@ -774,17 +774,17 @@ int encode_list(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, int both, 
     SelState st;
     st.tiles = (u32)div_up(n_bytes, SEL_TILE);
     ZK_TRY(lookback_begin(c, st.tiles, st.tiles, &st.epoch, &st.ticket_base));
-    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = c->d_scalars + 9;
+    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = &c->d_scalars->total;
     u64* d_rows;
     ZK_TRY(arena_alloc(c, 32ull * st.tiles, (void**)&d_rows));
     hipLaunchKernelGGL(encode_list_kernel, dim3(st.tiles), dim3(SEL_BLOCK), 0, c->stream, stream, (u64)n_bytes, K, both, out,
                        (u64)cap, d_rows, st);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(column_sum(c, d_rows, st.tiles, 4, c->d_scalars + 0));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, sizeof(u64) * 16, hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *n_out = c->h_scalars[9] * (both ? 2 : 1);
-    if (acgt) for (int b = 0; b < 4; b++) acgt[b] = c->h_scalars[b];
+    ZK_TRY(column_sum(c, d_rows, st.tiles, 4, c->d_scalars->acgt));
+    ZK_TRY(fetch_span(c, &c->h_scalars->total, ZK_SPAN(total, acgt)));
+    ZK_TRY(stream_sync(c));
+    *n_out = c->h_scalars->total * (both ? 2 : 1);
+    if (acgt) for (int b = 0; b < 4; b++) acgt[b] = c->h_scalars->acgt[b];
     return check_device_error(c);
 }
 
@@ -854,7 +854,7 @@ int capture_filter(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, const u
     ZK_TRY(arena_alloc(c, n_bytes, (void**)&hit));
     ZK_TRY(arena_alloc(c, 8 * n_bytes, (void**)&ends));
     const u32 tiles = (u32)div_up(n_bytes, CAP_TILE);
-    const u32 grid = tiles < (u32)c->num_cus * 8 ? tiles : (u32)c->num_cus * 8;
+    const u32 grid = grid_cap(c, tiles, 8);
     hipLaunchKernelGGL(bait_hit_kernel, dim3(grid), dim3(SEL_BLOCK), 0, c->stream, stream, (u64)n_bytes, K, baits, (u64)n_baits, hit, tiles);
     ZK_HIP(c, hipGetLastError());
     NewlineOp op{stream, ends};
@@ -863,17 +863,15 @@ int capture_filter(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, const u
     *n_reads = nr;
     // bytes after the last terminator (a stream that does not end in '\n') belong to no read: copy them
     ZK_HIP(c, hipMemcpyAsync(out, stream, n_bytes, hipMemcpyDeviceToDevice, c->stream));
-    u64* d_kept = c->d_scalars + 11;
+    u64* d_kept = &c->d_scalars->capture_kept;
     ZK_HIP(c, hipMemsetAsync(d_kept, 0, sizeof(u64), c->stream));
     if (nr) {
-        u64 g = div_up(nr, 4);
-        if (g > (u64)c->num_cus * 16) g = (u64)c->num_cus * 16;
-        hipLaunchKernelGGL(capture_apply_kernel, dim3((u32)g), dim3(256), 0, c->stream, stream, hit, ends, (u64)nr, out, d_kept);
+        hipLaunchKernelGGL(capture_apply_kernel, dim3(grid_cap(c, div_up(nr, 4), 16)), dim3(256), 0, c->stream, stream, hit, ends, (u64)nr, out, d_kept);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 11, d_kept, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *n_kept = c->h_scalars[11];
+    ZK_TRY(fetch(c, &c->h_scalars->capture_kept));
+    ZK_TRY(stream_sync(c));
+    *n_kept = c->h_scalars->capture_kept;
     return check_device_error(c);
 }
 
@@ -947,7 +945,7 @@ int count_hist(zk_ctx* c, const void* counts, int count_bits, uint64_t n, uint64
     // launch with the exact size finishes the histogram (zk_hist resets the arena per call: count_hist may start it over).
     uint64_t big_cap = n < (1ull << 22) ? n : (1ull << 22);
     u64 *dense = nullptr, *big = nullptr;
-    u64* big_n = c->d_scalars + 10;
+    u64* big_n = &c->d_scalars->hist_big_n;
     std::vector<u64> hd(HIST_DENSE);
     u64* h_dense = hd.data();
     uint64_t nb = 0;
@@ -958,7 +956,7 @@ int count_hist(zk_ctx* c, const void* counts, int count_bits, uint64_t n, uint64
         ZK_TRY(arena_alloc(c, sizeof(u64) * big_cap, (void**)&big));
         ZK_HIP(c, hipMemsetAsync(dense, 0, sizeof(u64) * HIST_DENSE, c->stream));
         ZK_HIP(c, hipMemsetAsync(big_n, 0, sizeof(u64), c->stream));
-        u32 grid = (u32)(div_up(n, 256 * 16) < (uint64_t)c->num_cus * 8 ? div_up(n, 256 * 16) : (uint64_t)c->num_cus * 8);
+        const u32 grid = grid_cap(c, div_up(n, 256 * 16), 8);
         prof_begin(c, ZK_PROF_COUNT_HIST, (count_bits / 8) * n);
         if (count_bits == 32)
             hipLaunchKernelGGL((count_hist_kernel<u32>), dim3(grid), dim3(256), 0, c->stream, (const u32*)counts, (u64)n, dense, big, (u64)big_cap, big_n);
@@ -967,9 +965,9 @@ int count_hist(zk_ctx* c, const void* counts, int count_bits, uint64_t n, uint64
         prof_end(c);
         ZK_HIP(c, hipGetLastError());
         ZK_HIP(c, hipMemcpyAsync(h_dense, dense, sizeof(u64) * HIST_DENSE, hipMemcpyDeviceToHost, c->stream));
-        ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 10, big_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-        ZK_HIP(c, hipStreamSynchronize(c->stream));
-        nb = c->h_scalars[10];
+        ZK_TRY(fetch(c, &c->h_scalars->hist_big_n));
+        ZK_TRY(stream_sync(c));
+        nb = c->h_scalars->hist_big_n;
         if (nb <= big_cap) break;
         big_cap = nb;          // (nb <= n: the second launch cannot overflow)
     }

@@ -338,7 +338,7 @@ static int union_sum_t(zk_ctx* c, const u64* A, const CT* cA, u64 nA, const u64*
     st.packa = packa;
     st.disjoint = disjoint ? 1 : 0;
     ZK_TRY(lookback_begin(c, tiles, tiles, &st.epoch, &st.ticket_base));
-    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = c->d_scalars + 9;
+    st.status = c->status; st.ticket = c->d_ticket; st.err = c->d_err; st.d_total = &c->d_scalars->total;
     u64* d_rows = nullptr;
     if (acgt_w) ZK_TRY(arena_alloc(c, 32ull * tiles, (void**)&d_rows));
     prof_begin(c, ZK_PROF_UNION, (packa ? 8 : 8 + sizeof(CT)) * nA + (packb ? 8 : 8 + sizeof(CT)) * nB);
@@ -347,13 +347,13 @@ static int union_sum_t(zk_ctx* c, const u64* A, const CT* cA, u64 nA, const u64*
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     if (acgt_w) {
-        ZK_TRY(column_sum(c, d_rows, tiles, 4, c->d_scalars + 0));
+        ZK_TRY(column_sum(c, d_rows, tiles, 4, c->d_scalars->acgt));
     }
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, sizeof(u64) * 16, hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *n_out = c->h_scalars[9];
+    ZK_TRY(fetch_span(c, &c->h_scalars->total, ZK_SPAN(total, acgt)));
+    ZK_TRY(stream_sync(c));
+    *n_out = c->h_scalars->total;
     prof_add_bytes(c, ZK_PROF_UNION, (8 + sizeof(CT)) * *n_out);          // the entries written (the launch was opened with the bytes read)
-    if (acgt_w) for (int b = 0; b < 4; b++) acgt_w[b] = c->h_scalars[b];
+    if (acgt_w) for (int b = 0; b < 4; b++) acgt_w[b] = c->h_scalars->acgt[b];
     return check_device_error(c);
 }
 
@@ -386,16 +386,16 @@ int intersect_count(zk_ctx* c, const u64* A, u64 nA, const u64* B, u64 nB, uint6
     if (nA == 0 || nB == 0) return ZK_OK;
     u64* part; u32 tiles;
     ZK_TRY(make_partition(c, A, nA, B, nB, &part, &tiles));
-    u64* d_n = c->d_scalars + 11;
+    u64* d_n = &c->d_scalars->intersect_n;
     ZK_HIP(c, hipMemsetAsync(d_n, 0, sizeof(u64), c->stream));
     prof_begin(c, ZK_PROF_INTERSECT, 8 * (nA + nB));
-    const u32 grid = tiles < (u32)c->num_cus * 8 ? tiles : (u32)c->num_cus * 8;
+    const u32 grid = grid_cap(c, tiles, 8);
     hipLaunchKernelGGL(intersect_kernel, dim3(grid), dim3(MRG_BLOCK), 0, c->stream, A, nA, B, nB, part, tiles, d_n);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 11, d_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    const uint64_t a = c->h_scalars[11];
+    ZK_TRY(fetch(c, &c->h_scalars->intersect_n));
+    ZK_TRY(stream_sync(c));
+    const uint64_t a = c->h_scalars->intersect_n;
     abc[0] = a; abc[1] = nA - a; abc[2] = nB - a;
     return ZK_OK;
 }

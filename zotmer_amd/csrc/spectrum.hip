@@ -139,10 +139,10 @@ int project_sum(zk_ctx* c, const u64* keys, const void* cnts, int count_bits, ui
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(scan64_inclusive(c, heads, tiles));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 20, heads + tiles - 1, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    ZK_TRY(fetch(c, &c->h_scalars->project_heads, heads + tiles - 1));
+    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
-    const uint64_t m = c->h_scalars[20];
+    const uint64_t m = c->h_scalars->project_heads;
     *n_out = m;
     if (m > cap) return fail(c, ZK_ENOSPC, "zk_project_sum: %llu distinct prefixes, room for %llu", (unsigned long long)m, (unsigned long long)cap);
     ZK_HIP(c, hipMemsetAsync(out_s, 0, 8 * m, c->stream));
@@ -155,10 +155,10 @@ int project_sum(zk_ctx* c, const u64* keys, const void* cnts, int count_bits, ui
                            heads, out_k, out_s, tot);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(column_sum(c, tot, tiles, 1, c->d_scalars + 21));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 21, c->d_scalars + 21, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *total = c->h_scalars[21];
+    ZK_TRY(column_sum(c, tot, tiles, 1, &c->d_scalars->project_total));
+    ZK_TRY(fetch(c, &c->h_scalars->project_total));
+    ZK_TRY(stream_sync(c));
+    *total = c->h_scalars->project_total;
     return ZK_OK;
 }
 
@@ -322,7 +322,7 @@ int spectrum_sums(zk_ctx* c, const u64* A, const u64* sA, u64 nA, const u64* B, 
     if (nA == 0 || nB == 0) return ZK_OK;
     u64* part; u32 tiles;
     ZK_TRY(make_partition(c, A, nA, B, nB, &part, &tiles));
-    const u32 grid = tiles < (u32)c->num_cus * 8 ? tiles : (u32)c->num_cus * 8;
+    const u32 grid = grid_cap(c, tiles, 8);
     u64* res; double* partial;
     ZK_TRY(arena_alloc(c, sizeof(u64) * SP_WORDS, (void**)&res));
     ZK_TRY(arena_alloc(c, 2 * sizeof(double) * grid, (void**)&partial));
@@ -333,9 +333,10 @@ int spectrum_sums(zk_ctx* c, const u64* A, const u64* sA, u64 nA, const u64* B, 
     ZK_HIP(c, hipGetLastError());
     hipLaunchKernelGGL(spectrum_combine_kernel, dim3(1), dim3(64), 0, c->stream, partial, grid, res);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 24, res, sizeof(u64) * SP_WORDS, hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    const u64* h = c->h_scalars + 24;
+    static_assert(sizeof(zk_scalars::spectrum) == sizeof(u64) * SP_WORDS, "the landing holds every word of res");
+    ZK_TRY(fetch(c, &c->h_scalars->spectrum, res));
+    ZK_TRY(stream_sync(c));
+    const u64* h = c->h_scalars->spectrum;
     out->n_shared = h[0]; out->s_min = h[1]; out->x_shared = h[2]; out->y_shared = h[3]; out->s_xy_lo = h[4]; out->s_xy_hi = h[5];
     memcpy(&out->s_sqrt, &h[6], sizeof(double));
     memcpy(&out->s_js, &h[7], sizeof(double));

@@ -51,20 +51,18 @@ static int strand_keys(zk_ctx* c, const u8* text, const u64* lines, uint64_t n_r
                        uint64_t cap, uint64_t* n_keys) {
     *n_keys = 0;
     if (n_reads == 0) return ZK_OK;
-    u64* d_cur = c->d_scalars + 50;
+    u64* d_cur = &c->d_scalars->strand_cursor;
     ZK_HIP(c, hipMemsetAsync(d_cur, 0, sizeof(u64), c->stream));
-    u64 g = div_up(n_reads, 4);
-    if (g > (u64)c->num_cus * 16) g = (u64)c->num_cus * 16;
     const u64 M = (1ull << (2 * K)) - 1;
     prof_begin(c, ZK_PROF_STRAND_KEYS, 0);
-    hipLaunchKernelGGL(strand_keys_kernel, dim3((u32)g), dim3(256), 0, c->stream, text, lines, (u64)n_reads, K, reverse, seed, M, T, keys,
-                       (u64)cap, d_cur);
+    hipLaunchKernelGGL(strand_keys_kernel, dim3(grid_cap(c, div_up(n_reads, 4), 16)), dim3(256), 0, c->stream, text, lines, (u64)n_reads, K, reverse,
+                       seed, M, T, keys, (u64)cap, d_cur);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 50, d_cur, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    ZK_TRY(fetch(c, &c->h_scalars->strand_cursor));
+    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
-    *n_keys = c->h_scalars[50];
+    *n_keys = c->h_scalars->strand_cursor;
     prof_add_bytes(c, ZK_PROF_STRAND_KEYS, 8 * (*n_keys < cap ? *n_keys : cap));
     if (*n_keys > cap)
         return fail(c, ZK_ENOSPC, "zk_strand_keys: %llu keys, room for %llu", (unsigned long long)*n_keys, (unsigned long long)cap);
@@ -134,20 +132,20 @@ static int strand_pairs(zk_ctx* c, const u64* keys, const void* cnts, int count_
     const u64 tiles = div_up(n, CP_TILE);
     u64* cnt;
     ZK_TRY(arena_alloc(c, 8 * tiles, (void**)&cnt));
-    u64* d_sums = c->d_scalars + 51;
+    u64* d_sums = c->d_scalars->strand_sums;
     ZK_HIP(c, hipMemsetAsync(d_sums, 0, 2 * sizeof(u64), c->stream));
     prof_begin(c, ZK_PROF_STRAND_PAIRS, 8 * n);
     hipLaunchKernelGGL(strand_count_kernel, dim3((u32)tiles), dim3(CP_BLOCK), 0, c->stream, keys, (u64)n, K, (int)orphans, cnt, d_sums);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(scan64_inclusive(c, cnt, tiles));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 51, d_sums, 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 53, cnt + tiles - 1, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    ZK_TRY(fetch(c, &c->h_scalars->strand_sums));
+    ZK_TRY(fetch(c, &c->h_scalars->strand_n_pairs, cnt + tiles - 1));
+    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
-    st->n_orphans = c->h_scalars[51];
-    st->n_palindromes = c->h_scalars[52];
-    st->n_pairs = c->h_scalars[53];
+    st->n_orphans = c->h_scalars->strand_sums[0];
+    st->n_palindromes = c->h_scalars->strand_sums[1];
+    st->n_pairs = c->h_scalars->strand_n_pairs;
     if (st->n_pairs > cap)
         return fail(c, ZK_ENOSPC, "zk_strand_pairs: %llu lines, room for %llu", (unsigned long long)st->n_pairs, (unsigned long long)cap);
     prof_begin(c, ZK_PROF_STRAND_PAIRS, (8 + count_bits / 8) * n + 16 * st->n_pairs);
@@ -159,7 +157,7 @@ static int strand_pairs(zk_ctx* c, const u64* keys, const void* cnts, int count_
         ZK_TRY(compact_write(c, p, n, cnt));
     }
     prof_end(c);
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 
@@ -200,21 +198,20 @@ static int format_pairs(zk_ctx* c, const u64* a, const u64* b, uint64_t n, u8* o
     ZK_TRY(arena_require(c, 8 * n + n / 32 + (1 << 20), 8 * n + n / 32 + (1 << 20)));
     u64* len;
     ZK_TRY(arena_alloc(c, 8 * n, (void**)&len));
-    u64 g = div_up(n, 256);
-    if (g > (u64)c->num_cus * 16) g = (u64)c->num_cus * 16;
+    const u32 g = grid_cap(c, div_up(n, 256), 16);
     prof_begin(c, ZK_PROF_FORMAT_PAIRS, 24 * n);
-    hipLaunchKernelGGL(line_len_kernel, dim3((u32)g), dim3(256), 0, c->stream, a, b, (u64)n, len);
+    hipLaunchKernelGGL(line_len_kernel, dim3(g), dim3(256), 0, c->stream, a, b, (u64)n, len);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(scan64_inclusive(c, len, n));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 53, len + n - 1, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    ZK_TRY(fetch(c, &c->h_scalars->format_bytes, len + n - 1));
+    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
-    *n_bytes = c->h_scalars[53];
+    *n_bytes = c->h_scalars->format_bytes;
     if (*n_bytes > cap)
         return fail(c, ZK_ENOSPC, "zk_format_pairs: %llu bytes of lines, room for %llu", (unsigned long long)*n_bytes, (unsigned long long)cap);
     prof_begin(c, ZK_PROF_FORMAT_PAIRS, 24 * n + *n_bytes);
-    hipLaunchKernelGGL(line_write_kernel, dim3((u32)g), dim3(256), 0, c->stream, a, b, (u64)n, len, out);
+    hipLaunchKernelGGL(line_write_kernel, dim3(g), dim3(256), 0, c->stream, a, b, (u64)n, len, out);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     ZK_HIP(c, hipStreamSynchronize(c->stream));
@@ -224,8 +221,6 @@ static int format_pairs(zk_ctx* c, const u64* a, const u64* b, uint64_t n, u8* o
 }  // namespace zk
 
 using namespace zk;
-
-#define ZK_ARGS(c, cond) do { if (!(c)) return ZK_EINVAL; zk::enter(c); if (!(cond)) return zk::fail((c), ZK_EINVAL, "bad argument: %s", #cond); } while (0)
 
 extern "C" {
 

@@ -352,20 +352,20 @@ int strand_blocks(zk_ctx* c, const DedupeResult& r, u64* keys_buf, uint64_t buf_
     StrandArgs a = {};
     a.cw = r.work; a.cuts = r.cuts; a.nwords = r.nwords; a.incl = r.incl; a.m = sk; a.mstart = mstart;
     a.ok = out_k; a.oc = out_c; a.pack = pk; a.pshift = lo_bit;
-    a.n_declined = (u32*)(c->d_scalars + 9);
+    a.n_declined = &c->d_scalars->strand.n_declined;
     a.declined = declined;
-    u32* fail = (u32*)(c->d_scalars + 9) + 1;
+    u32* fail = &c->d_scalars->strand.fail;
     prof_begin(c, ZK_PROF_UNION, 8 * 2 * uc + 12 * 2 * uc);
     hipLaunchKernelGGL(strand_starts_kernel, dim3(((1u << SB_BLOCK_BITS) + 256) / 256), dim3(256), 0, c->stream, sk, (u64)uc, lo_bit, mstart);
-    ZK_HIP(c, hipMemsetAsync(c->d_scalars + 9, 0, sizeof(u64), c->stream));
+    ZK_HIP(c, hipMemsetAsync(&c->d_scalars->strand, 0, sizeof(zk_strand_counters), c->stream));
     hipLaunchKernelGGL(strand_block_union_kernel, dim3(r.chunks), dim3(TS_BLOCK), 0, c->stream, a);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    ZK_TRY(fetch(c, &c->h_scalars->strand));
     ZK_TRY(check_device_error(c));
-    const uint32_t n_declined = (uint32_t)c->h_scalars[9];
-    if (n_declined && c->strand_blocks == 3) c->h_scalars[9] |= 1ull << 32;          // (tests: the declined blocks the other way)
-    else if (n_declined) {
+    const uint32_t n_declined = c->h_scalars->strand.n_declined;
+    bool other_way = n_declined && c->strand_blocks == 3;          // (tests: the declined blocks the other way)
+    if (n_declined && !other_way) {
         // the declined blocks alone, cut by value into sub-tiles (their bytes: booked as the blocks' share of the union above)
         const uint32_t grid = n_declined < 2u * (uint32_t)c->num_cus ? n_declined : 2u * (uint32_t)c->num_cus;
         u64* scratch;
@@ -374,10 +374,11 @@ int strand_blocks(zk_ctx* c, const DedupeResult& r, u64* keys_buf, uint64_t buf_
         hipLaunchKernelGGL(strand_big_block_kernel, dim3(grid), dim3(TS_BLOCK), 0, c->stream, a, n_declined, scratch, fail);
         prof_end(c);
         ZK_HIP(c, hipGetLastError());
-        ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        ZK_TRY(fetch(c, &c->h_scalars->strand));
         ZK_TRY(check_device_error(c));
+        other_way = c->h_scalars->strand.fail != 0;
     }
-    if ((uint32_t)(c->h_scalars[9] >> 32) == 0) {
+    if (!other_way) {
         *n_out = 2 * uc;
         return ZK_OK;
     }

@@ -357,7 +357,7 @@ int stream_pass1(zk_ctx* c, const u32* tags, const u16* dig, uint64_t n, const u
     ZK_TRY(arena_alloc(c, sizeof(u32) * ((uint64_t)T1_RADIX + 1), (void**)&sg.first));
     ZK_TRY(arena_alloc(c, sizeof(u32) * (uint64_t)sg.max_segs * T1_RADIX, (void**)&rows));
     ZK_TRY(arena_alloc(c, sizeof(u64) * ((uint64_t)sg.max_segs + 1) * T1_RADIX, (void**)&offs));
-    sg.nseg = (u32*)(c->d_scalars + 33);
+    sg.nseg = (u32*)&c->d_scalars->tag_nseg;
     hipLaunchKernelGGL(tagpass_plan_kernel, dim3(1), dim3(T1_RADIX), 0, c->stream, ghist0, (u64)n, radix0, sg);
     prof_begin(c, ZK_PROF_HIST_ARRAY, 2 * n);
     hipLaunchKernelGGL(tagpass_count_kernel, dim3(sg.max_segs), dim3(T1_BLOCK), 0, c->stream, dig, sg, rows);

@@ -267,7 +267,7 @@ int tile_sort(zk_ctx* c, u64* keys, u32* vals, uint64_t n, int key_bits, int top
     const u32 tiles = (u32)tiles64;
     u64* bounds;
     ZK_TRY(arena_alloc(c, sizeof(u64) * ((uint64_t)tiles + 1), (void**)&bounds));
-    u32* flag = (u32*)(c->d_scalars + 40);
+    u32* flag = (u32*)&c->d_scalars->tile_declined;
     ZK_HIP(c, hipMemsetAsync(flag, 0, sizeof(u64), c->stream));
     const int pshift = key_bits - top;
     hipLaunchKernelGGL(tile_bounds_kernel, dim3(tiles / 256 + 1), dim3(256), 0, c->stream, (const u64*)keys, (u64)n, pshift, T, TS_SLACK, tiles, bounds, flag);
@@ -280,9 +280,9 @@ int tile_sort(zk_ctx* c, u64* keys, u32* vals, uint64_t n, int key_bits, int top
     else hipLaunchKernelGGL((tile_sort_kernel<14, 4096, false>), dim3(grid), dim3(TS_BLOCK), 0, c->stream, a);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 40, flag, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *declined = (c->h_scalars[40] & 1ull) != 0;
+    ZK_TRY(fetch(c, &c->h_scalars->tile_declined));
+    ZK_TRY(stream_sync(c));
+    *declined = (c->h_scalars->tile_declined & 1ull) != 0;
     return ZK_OK;
 }
 
@@ -300,7 +300,7 @@ int tile_sort_count(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int to
     const u32 tiles = (u32)tiles64;
     u64* bounds;
     ZK_TRY(arena_alloc(c, sizeof(u64) * ((uint64_t)tiles + 1), (void**)&bounds));
-    u32* flag = (u32*)(c->d_scalars + 40);
+    u32* flag = (u32*)&c->d_scalars->tile_declined;
     ZK_HIP(c, hipMemsetAsync(flag, 0, sizeof(u64), c->stream));
     const int pshift = key_bits - top;
     hipLaunchKernelGGL(tile_bounds_kernel, dim3(tiles / 256 + 1), dim3(256), 0, c->stream, keys, (u64)n, pshift, T, TS_SLACK, tiles, bounds, flag);
@@ -311,18 +311,18 @@ int tile_sort_count(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int to
     a.kin = keys; a.bounds = bounds; a.tiles = tiles; a.pshift = pshift; a.uniq = uniq; a.counts = counts; a.cap = cap; a.flag = flag;
     // every workgroup draws tiles until the ticket says there are none left: tiles + grid tickets in all
     ZK_TRY(lookback_begin(c, tiles, tiles + grid, &a.epoch, &a.ticket_base));
-    a.status = c->status; a.ticket = c->d_ticket; a.err = c->d_err; a.d_total = c->d_scalars + 9;
+    a.status = c->status; a.ticket = c->d_ticket; a.err = c->d_err; a.d_total = &c->d_scalars->total;
     a.dbg = c->dbg;
     prof_begin(c, ZK_PROF_TILE_SORT, 8 * n);
     hipLaunchKernelGGL((tile_sort_count_kernel<TS_COUNT_ITEMS, 4096>), dim3(grid), dim3(TS_BLOCK), 0, c->stream, a);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 40, flag, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *declined = (c->h_scalars[40] & 1ull) != 0;
+    ZK_TRY(fetch(c, &c->h_scalars->tile_declined));
+    ZK_TRY(fetch(c, &c->h_scalars->total));
+    ZK_TRY(stream_sync(c));
+    *declined = (c->h_scalars->tile_declined & 1ull) != 0;
     if (*declined) return ZK_OK;
-    *n_unique = c->h_scalars[9];
+    *n_unique = c->h_scalars->total;
     prof_add_bytes(c, ZK_PROF_TILE_SORT, 12 * *n_unique);
     ZK_TRY(check_device_error(c));
     return ZK_OK;

@@ -373,50 +373,18 @@ class Context:
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
                  "probe_scan": 21}
 
-    def tune(self, sort_variant=None, pairs_variant=None, short_sort=None, side_div=None, xcd_group=None, comm_chunk=None,
-             early_collapse=None, packed_pairs=None, wide_tiles=None, stream_pass=None, stream_ranges=None, tag_words=None,
-             dedupe_variant=None, dedupe_limit=None, dedupe_bits=None, comm_self_loop=None, tag_pass=None, kway=None, tile_sort=None,
-             strand_blocks=None):
-        if strand_blocks is not None:
-            self._check(self.lib.zk_tune(self.h, 20, int(strand_blocks)))
-        if tile_sort is not None:
-            self._check(self.lib.zk_tune(self.h, 19, int(tile_sort)))
-        if kway is not None:
-            self._check(self.lib.zk_tune(self.h, 18, int(kway)))
-        if tag_pass is not None:
-            self._check(self.lib.zk_tune(self.h, 17, int(tag_pass)))
-        if comm_self_loop is not None:
-            self._check(self.lib.zk_tune(self.h, 16, int(comm_self_loop)))
-        if dedupe_bits is not None:
-            self._check(self.lib.zk_tune(self.h, 15, int(dedupe_bits)))
-        if dedupe_variant is not None:
-            self._check(self.lib.zk_tune(self.h, 13, int(dedupe_variant)))
-        if dedupe_limit is not None:
-            self._check(self.lib.zk_tune(self.h, 14, int(dedupe_limit)))
-        if tag_words is not None:
-            self._check(self.lib.zk_tune(self.h, 12, int(tag_words)))
-        if stream_pass is not None:
-            self._check(self.lib.zk_tune(self.h, 10, int(stream_pass)))
-        if stream_ranges is not None:
-            self._check(self.lib.zk_tune(self.h, 11, int(stream_ranges)))
-        if wide_tiles is not None:
-            self._check(self.lib.zk_tune(self.h, 9, int(wide_tiles)))
-        if packed_pairs is not None:
-            self._check(self.lib.zk_tune(self.h, 8, int(packed_pairs)))
-        if early_collapse is not None:
-            self._check(self.lib.zk_tune(self.h, 7, int(early_collapse)))
-        if comm_chunk is not None:
-            self._check(self.lib.zk_tune(self.h, 6, int(comm_chunk)))
-        if xcd_group is not None:
-            self._check(self.lib.zk_tune(self.h, 5, int(xcd_group)))
-        if short_sort is not None:
-            self._check(self.lib.zk_tune(self.h, 3, int(short_sort)))
-        if side_div is not None:
-            self._check(self.lib.zk_tune(self.h, 4, int(side_div)))
-        if sort_variant is not None:
-            self._check(self.lib.zk_tune(self.h, 1, int(sort_variant)))
-        if pairs_variant is not None:
-            self._check(self.lib.zk_tune(self.h, 2, int(pairs_variant)))
+    # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
+    TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
+                    packed_pairs=8, wide_tiles=9, stream_pass=10, stream_ranges=11, tag_words=12, dedupe_variant=13, dedupe_limit=14,
+                    dedupe_bits=15, comm_self_loop=16, tag_pass=17, kway=18, tile_sort=19, strand_blocks=20)
+
+    def tune(self, **knobs):
+        for name in knobs:
+            if name not in self.TUNE_IDS:
+                raise TypeError("tune() got an unexpected keyword argument %r" % name)
+        for name, value in knobs.items():
+            if value is not None:
+                self._check(self.lib.zk_tune(self.h, self.TUNE_IDS[name], int(value)))
 
     def profile(self, enable=True):
         self._check(self.lib.zk_profile(self.h, int(enable)))
