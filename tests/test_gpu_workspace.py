@@ -58,6 +58,17 @@ def n_canonical_of(kmers, K):
     return (len(k) + pal) // 2
 
 
+def canonical_of(kmers, counts, K):
+    """the counted canonical list of a both-strand table: the entries with x <= rc x, a palindrome's count halved (it was counted
+    twice per window)"""
+    k = np.asarray(kmers, dtype=np.uint64)
+    rc = revcomp_np(k, K)
+    keep = k <= rc
+    c = np.asarray(counts)[keep].astype(np.uint32)
+    c[k[keep] == rc[keep]] //= 2
+    return k[keep], c
+
+
 def stream_of(reads):
     return ("".join(r + "\n" for r in reads)).encode()
 
@@ -485,6 +496,7 @@ def test_kmerize_stats_every_plan(ctx, K):
         for name, reads in (("deep", deep), ("flat", flat)):
             want = zo.kmerize(K, reads)
             n_can = n_canonical_of(want["kmers"], K)
+            can_k, can_c = canonical_of(want["kmers"], want["counts"], K)
             data = stream_of(reads)
             if name == "flat":
                 assert len(data) >= 4 * MiB
@@ -510,5 +522,10 @@ def test_kmerize_stats_every_plan(ctx, K):
                     sub_ref = sub
                     assert sts.n_canonical == n_can and sts.n_unique < len(want["kmers"])
                 assert np.array_equal(sub[0], sub_ref[0]) and np.array_equal(sub[1], sub_ref[1]) and sub[2] == sub_ref[2], (name, K, plan)
+                # the counted canonical list itself: every counting route has an exit of its own for it (counted straight into the
+                # caller's arrays, or copied out of the aux region or a sort buffer)
+                ck, cc, stc = ctx.kmerize(d, K, native.KMERIZE_CANONICAL_ONLY)
+                assert np.array_equal(ck.to_host(), can_k) and np.array_equal(cc.to_host(), can_c), (name, K, plan)
+                assert stc.n_canonical == stc.n_unique == len(can_k) and list(stc.acgt) == want["acgt"], (name, K, plan)
     finally:
         ctx.tune(**DEFAULTS)
