@@ -553,6 +553,76 @@ def test_kmerize_stream_ranges_pass(ctx, shape):
         ctx.tune(stream_pass=1, stream_ranges=0, early_collapse=1)
 
 
+# launches per profiling tag of one kmerize, by (input, knobs): recorded from the library before sort_stream was cut into stages
+SORT_STREAM_ROUTE_LAUNCHES = {
+    'u150 stream_pass=0': dict(hist_array=1, hist_stream=1, mirror=1, pass_keys=5, pass_packed=4, pass_stream=1, rle=2, union_sum=1),
+    'u150 stream_pass=1': dict(hist_array=1, hist_stream=1, mirror=1, pass_keys=5, pass_packed=4, pass_stream=1, rle=2, union_sum=1),
+    'u150 stream_pass=3': dict(hist_array=1, hist_stream=1, mirror=1, pass_keys=5, pass_packed=4, pass_stream=1, rle=2, union_sum=1),
+    'alt_149_151 stream_pass=0': dict(hist_array=1, hist_stream=1, mirror=1, pass_keys=5, pass_packed=4, pass_stream=1, rle=2, union_sum=1),
+    'alt_149_151 stream_pass=1': dict(hist_array=1, hist_stream=1, mirror=1, pass_keys=5, pass_packed=4, pass_stream=1, rle=2, union_sum=1),
+    'alt_149_151 stream_pass=3': dict(hist_array=1, hist_stream=1, mirror=1, pass_keys=5, pass_packed=4, pass_stream=1, rle=2, union_sum=1),
+    'deep K=25 tag_words=1 tag_pass=1 wide_tiles=1': dict(hist_array=1, hist_stream=1, pass_keys=1, pass_packed=2, pass_stream=1, rle=2, select=1, union_sum=1),
+    'deep K=25 tag_words=1 tag_pass=0 wide_tiles=1': dict(hist_stream=1, pass_keys=1, pass_packed=2, pass_stream=1, rle=2, select=1, union_sum=1),
+    'deep K=25 tag_words=0 tag_pass=0 wide_tiles=0': dict(hist_stream=1, pass_keys=1, pass_packed=2, pass_stream=1, rle=2, select=1, union_sum=1),
+    'deep K=25 tag_words=2 tag_pass=0 wide_tiles=1': dict(hist_stream=1, pass_keys=1, pass_packed=2, pass_stream=1, rle=2, select=1, union_sum=1),
+    'deep K=27 tag_words=1 tag_pass=1 wide_tiles=1': dict(hist_stream=1, pass_keys=1, pass_packed=2, pass_stream=1, rle=2, select=1, union_sum=1),
+    'deep K=27 tag_words=1 tag_pass=0 wide_tiles=1': dict(hist_stream=1, pass_keys=1, pass_packed=2, pass_stream=1, rle=2, select=1, union_sum=1),
+    'deep K=27 tag_words=0 tag_pass=0 wide_tiles=0': dict(hist_stream=1, pass_keys=1, pass_packed=2, pass_stream=1, rle=2, select=1, union_sum=1),
+    'deep K=27 tag_words=2 tag_pass=0 wide_tiles=1': dict(hist_stream=1, pass_keys=1, pass_packed=2, pass_stream=1, rle=2, select=1, union_sum=1),
+}
+
+
+def _sort_stream_route_launches(ctx):
+    """{case: {profiling tag: launches}} of one kmerize per case, each one checked against the oracle."""
+    def rnd(rng, n, p_n=0.002):
+        a = rng.choice(list("ACGT"), size=n)
+        a[rng.random(n) < p_n] = "N"
+        return "".join(a)
+    # the inputs of test_kmerize_record_aligned_tiles_and_fallbacks (u150, alt_149_151) and test_kmerize_forced_block_dedupe (deep)
+    rng = np.random.default_rng(len("u150"))
+    u150 = [rnd(rng, 150) for _ in range(1333)]
+    rng = np.random.default_rng(len("alt_149_151"))
+    alt = [rnd(rng, 149 if i % 2 == 0 else 151) for i in range(1500)]
+    deep = synth.read_strings(31, 0, 6000, 150, genome=12000, sub_thr=synth.frac32(0.004), n_thr=synth.frac32(0.001))
+    got = {}
+
+    def run(case, d, K, want, **knobs):
+        ctx.tune(**knobs)
+        ctx.profile(True)
+        k, c, st = ctx.kmerize(d, K)
+        got[case] = {tag: rec["launches"] for tag, rec in ctx.profile_read().items()}
+        assert np.array_equal(k.to_host(), want["kmers"]) and np.array_equal(c.to_host(), want["counts"]), case
+        assert list(st.acgt) == want["acgt"] and st.n_unique == len(want["kmers"]), case
+    try:
+        for name, reads in (("u150", u150), ("alt_149_151", alt)):
+            want = zo.kmerize(25, reads)
+            d = ctx.upload_stream(stream_of(reads))
+            for stream_pass in (0, 1, 3):
+                run("%s stream_pass=%d" % (name, stream_pass), d, 25, want, stream_pass=stream_pass)
+        ctx.tune(stream_pass=1)
+        d = ctx.upload_stream(stream_of(deep))
+        for K in (25, 27):          # K = 27: 36 key bits below the 18 block bits, tags no longer fit
+            want = zo.kmerize(K, deep)
+            for tag_words, tag_pass, wide in ((1, 1, 1), (1, 0, 1), (0, 0, 0), (2, 0, 1)):
+                run("deep K=%d tag_words=%d tag_pass=%d wide_tiles=%d" % (K, tag_words, tag_pass, wide), d, K, want,
+                    dedupe_bits=18, tag_words=tag_words, tag_pass=tag_pass, wide_tiles=wide)
+    finally:
+        ctx.profile(False)
+        ctx.tune(stream_pass=1, stream_ranges=0, dedupe_bits=0, tag_words=native.DEFAULT_TAG_WORDS, tag_pass=0, wide_tiles=1)
+    return got
+
+
+def test_sort_stream_routes_by_launches(ctx):
+    """Which first-pass route and which tag route sort_stream takes, pinned by what it launches: the arrays of two routes are the same
+    by construction, so only the launches per profiling tag tell a route from its neighbour.  stream_pass 0 / 1 / 3 on a uniform and a
+    never-uniform stream (record-aligned pipeline tiles, tiles of positions, the ranged pass), and under the forced block dedupe the
+    tag settings at K = 25 (tags fit 32 bits) and K = 27 (they do not)."""
+    got = _sort_stream_route_launches(ctx)
+    assert sorted(got) == sorted(SORT_STREAM_ROUTE_LAUNCHES)
+    for case in got:
+        assert got[case] == SORT_STREAM_ROUTE_LAUNCHES[case], case
+
+
 @pytest.mark.parametrize("K", [4, 24, 32])
 def test_kmerize_even_K_palindromes_vs_oracle(ctx, K):
     # even K: x == rc(x) exists; the mirrored path must count such a window twice, like two emissions

@@ -70,6 +70,25 @@ __device__ __forceinline__ u64 wave_incl_scan_u64(u64 v) {
     return v;
 }
 
+// match-any over the digit bits: on return (plo, phi) = the live lanes of the wave that hold the same digit as this lane.
+// All RBITS bits are always tested (bits above the pass's width are zero in every lane, so they change nothing) -- no
+// data- or pass-dependent branch.  Four vector instructions per bit: the bit as 0 / ~0 (v_bfe_i32, kept opaque: left to
+// itself the compiler rebuilds it from a shift, a sign compare and an arithmetic shift), its ballot, and per half ONE
+// three-input boolean op  peers &= ~(ballot ^ bit)  (v_bitop3_b32, truth table 0x90 for a & ~(b ^ c)).
+// (the sort passes of radix_sort.hip and collapse.hip's collapse_kernel rank their tiles with it)
+template <int RBITS>
+__device__ __forceinline__ void match_digit(u32 d, u64 live_mask, u32& plo, u32& phi) {
+    plo = (u32)live_mask; phi = (u32)(live_mask >> 32);
+#pragma unroll
+    for (int b = 0; b < RBITS; b++) {
+        int B;
+        asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(B) : "v"(d), "n"(b));
+        const u64 m = __ballot(B != 0);
+        plo = __builtin_amdgcn_bitop3_b32(plo, (u32)m, (u32)B, 0x90);
+        phi = __builtin_amdgcn_bitop3_b32(phi, (u32)(m >> 32), (u32)B, 0x90);
+    }
+}
+
 __device__ __forceinline__ u64 ld_agent(const u64* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

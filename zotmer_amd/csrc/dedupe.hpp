@@ -1,4 +1,4 @@
-// dedupe.hpp -- what the two block-dedupe kernels share (radix_sort.hip::dedupe_kernel, dedupe2.hip::dedupe2_kernel).
+// dedupe.hpp -- what the two block-dedupe kernels share (dedupe_blocks.hip::dedupe_kernel, dedupe2.hip::dedupe2_kernel).
 //
 // K4 of DESIGN.md: replaces the run-length half of kmerize.merge (zotmer/commands/kmerize.py:41-132) -- the keys of one block (equal
 // top bits, every copy of a k-mer inside) are counted in an LDS hash table and leave the kernel sorted, as words (key << pack | count).

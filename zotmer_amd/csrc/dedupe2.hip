@@ -1,6 +1,6 @@
 // dedupe2.hip -- K4, the block dedupe with TWO workgroups per CU (32-bit tags only).
 //
-// Replaces the run-length half of kmerize.merge (zotmer/commands/kmerize.py:41-132) exactly as radix_sort.hip::dedupe_kernel does;
+// Replaces the run-length half of kmerize.merge (zotmer/commands/kmerize.py:41-132) exactly as dedupe_blocks.hip::dedupe_kernel does;
 // same inputs, same words out.  What is different is how a CU is used.  dedupe_kernel's table (12 K entries of 4 + 4 bytes, 142 KB
 // with its lists) leaves room for one workgroup per CU, and a block's phases -- clear, insert, drain, group, rank, write -- run one
 // after the other with a barrier between them: tools/lds_atomic_bench.hip measures the two LDS atomics of an insert at 10.3 ns per

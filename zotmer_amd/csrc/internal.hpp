@@ -20,7 +20,7 @@ struct zk_scalars {
     // -- adjacent: rle_prefix reads back [rle_side .. total], the merges [total .. acgt], sort_stream [acgt .. sample_n] --
     u64 rle_side;            // rle_prefix: entries on the side list
     u64 total;               // SHARED BY DESIGN: the look-back total of the launch in flight, written by every SelState / MergeState / KwayState /
-                             // tile-sort-count / collapse kernel (select, setops, kway, codec, tilesort, radix_sort) and read back right after it
+                             // tile-sort-count / collapse kernel (select, setops, kway, codec, tilesort, collapse) and read back right after it
     u64 acgt[4];             // base totals: column_sum of encode_list / union_sum / kway_union_sum, the stream histogram
     u64 n_keys;              // hist_scan_kernel: live keys of a sort
     u64 rec_info[3];         // first_newline_kernel + the stream histogram: first newline, newlines, bad bytes (one pointer)
@@ -90,7 +90,7 @@ struct zk_ctx {
                                // per CU writing whole 128-byte units from LDS, 2 = two 512-thread workgroups per CU writing 64-byte units,
                                // 3 = as 2 with a tile's units leaving in two bursts (measurements); 0 = the look-back pipeline
     int tag_words = 2;         // zk_kmerize, block dedupe after two passes with at most 32 key bits below the blocks: the second pass writes
-                               // only those bits, as 32-bit tags (radix_sort.hip); 2 (default) = ... and takes a key's place in its digit's run
+                               // only those bits, as 32-bit tags (radix_sort.hip's sort_stream); 2 (default) = ... and takes a key's place in its digit's run
                                // from a returning LDS add wherever a tile holds keys of one bucket of the pass before (pass_pipe_kernel VAR 3:
                                // 23.6-24.0 against 24.7 ms); 1 = tags, every tile ranked by ballots; 0 = whole keys
     int dedupe_variant = 0;    // block dedupe at <= 32 tag bits: dedupe2_kernel's variant (dedupe2.hip), -1 = dedupe_kernel alone
@@ -211,7 +211,21 @@ struct PassPlan {          // the digits of an LSD sort: pass p takes bits [shif
     int shift[MAX_PASSES];
     int bits[MAX_PASSES];
 };
-int sort_workspace_bytes(uint64_t n, bool pairs, uint64_t* bytes);
+// the bits [lo, lo + key_bits) in digits of at most rbits, as even as they come
+static inline PassPlan make_plan(int key_bits, int rbits, int lo = 0) {
+    PassPlan p;
+    if (key_bits < 1) key_bits = 1;
+    if (key_bits > 64) key_bits = 64;
+    p.passes = (key_bits + rbits - 1) / rbits;
+    int base = key_bits / p.passes, rem = key_bits % p.passes, s = lo;
+    for (int i = 0; i < MAX_PASSES; i++) { p.shift[i] = 0; p.bits[i] = 0; }
+    for (int i = 0; i < p.passes; i++) {
+        p.bits[i] = base + (i < rem ? 1 : 0);
+        p.shift[i] = s;
+        s += p.bits[i];
+    }
+    return p;
+}
 int sort_keys(zk_ctx* c, u64* keys, u64* alt, uint64_t n, int key_bits, u64** result);
 int sort_pairs(zk_ctx* c, u64* keys, u64* alt, u32* vals, u32* valt, uint64_t n, int key_bits, u64** rk, u32** rv);
 int sort_keys_upper(zk_ctx* c, u64* keys, u64* alt, uint64_t n, int key_bits, int lo_bit, u64** result, int prof_tag = ZK_PROF_PASS_PACKED);
@@ -219,7 +233,7 @@ int sort_pairs_upper(zk_ctx* c, u64* keys, u64* alt, u32* vals, u32* valt, uint6
 int sort_pairs_mirrored(zk_ctx* c, const u64* src_k, const u32* src_v, u64* keys, u64* alt, u32* vals, u32* valt, uint64_t n, int K,
                         u64** rk, u32** rv, int lo_bit = 0);
 int sort_pairs_rbits(zk_ctx* c);
-// sort whose first pass generates the keys from a base stream (encode.hip + radix_sort.hip)
+// sort whose first pass generates the keys from a base stream (encode_tile.hpp + radix_sort.hip)
 // Ask sort_stream to look before it sorts: the histogram kernel sets aside the keys whose bits from `shift` up equal `value` (a
 // few whole blocks of the block dedupe: every copy of their k-mers), and if more than max_ratio of them are distinct the sort is
 // declined (return 1, nothing sorted) -- the caller then plans for an input that does not repeat its k-mers.
@@ -230,11 +244,17 @@ struct StreamSample { int shift; uint64_t value; double max_ratio; uint64_t seen
 struct StreamTags { bool written = false; u64* cuts = nullptr; uint32_t blocks = 0; };
 struct StreamSrc { const u8* stream; uint64_t n_bytes; int K; int mode; int lo_bit; int hi_bit = 0; StreamSample* sample = nullptr;
                    StreamTags* tags = nullptr; };   // mode: ZK_KEYS_*; sort bits [lo_bit, hi_bit) (hi_bit 0 = 2K)
+int sort_stream(zk_ctx* c, const StreamSrc& src, u64* buf_a, u64* buf_b, uint64_t cap, uint64_t* n_keys,
+                uint64_t acgt[4], u64** result);
 int sort_rbits(zk_ctx* c);
 PassPlan sort_plan_upper(zk_ctx* c, int key_bits, int lo_bit);   // the digits sort_keys_upper(_counted) takes for the bits [lo_bit, key_bits)
-// digit counts of the passes to come, taken by the kernel that writes the words they will sort (no histogram pass of its own then)
-struct MirrorHist { int passes; int shift[4]; int bits[4]; u64* raw; };          // raw: [MAX_PASSES][512], += by the producer
 int sort_first_bits(zk_ctx* c, int key_bits, int lo_bit);
+// digit counts of the passes to come, taken by the kernel that writes the words they will sort (no histogram pass of its own then)
+constexpr int MIRROR_RBITS = 9, MIRROR_RADIX = 1 << MIRROR_RBITS;          // the default geometry's digits (radix_sort.hip asserts it)
+struct MirrorHist { int passes; int shift[4]; int bits[4]; u64* raw; };          // raw: [MAX_PASSES][MIRROR_RADIX], += by the producer
+// ... and the sort that takes them (dedupe_finish; default geometry only)
+int sort_keys_upper_counted(zk_ctx* c, u64* keys, u64* alt, uint64_t n, int key_bits, int lo_bit, u64* counted, u64** result);
+// dedupe_blocks.hip
 struct DedupeResult {
     uint64_t n_out = 0;          // distinct keys
     uint32_t flags = 0;          // bit 0: a table filled up (unusable), bit 1: counts beyond the packed field exist (patched by dedupe_finish)
@@ -250,21 +270,20 @@ struct DedupeResult {
 int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int pack, u64* work, uint64_t cap, DedupeResult* r,
                 uint64_t* n_in = nullptr, uint64_t max_chunks = 0, const u32* tags = nullptr, const u64* tag_cuts = nullptr,
                 bool unsorted = false);
-// r.unsorted: every block of at most a dedupe2_kernel table's entries sorted in place (strand_blocks.hip); r.unsorted is false after
-int dedupe_sort_blocks(zk_ctx* c, DedupeResult& r);
 // the keys back from their tags: key = (block number << tag_bits) | tag
 int expand_tags(zk_ctx* c, const u32* tags, const u64* cuts, uint32_t blocks, int tag_bits, u64* keys_out, uint64_t first_block = 0, uint64_t n_blocks = 0);
 // packed_out: out_k takes the words themselves, (key << pack) | count, and out_c is not written (the caller merges them as they are)
 int dedupe_finish(zk_ctx* c, const DedupeResult& r, u64* out_k, u32* out_c, u64* out_m = nullptr, int K = 0, int gbases = 0,
                   u64** mirror_hist = nullptr, int* mirror_group_bits = nullptr, bool packed_out = false);
-int sort_keys_upper_counted(zk_ctx* c, u64* keys, u64* alt, uint64_t n, int key_bits, int lo_bit, u64* counted, u64** result);
-// strand_blocks.hip: both strands of the block dedupe's counted list at odd K, block by block (keys_buf: buf_words free words)
+// strand_blocks.hip
+// r.unsorted: every block of at most a dedupe2_kernel table's entries sorted in place; r.unsorted is false after
+int dedupe_sort_blocks(zk_ctx* c, DedupeResult& r);
+// both strands of the block dedupe's counted list at odd K, block by block (keys_buf: buf_words free words)
 int strand_blocks(zk_ctx* c, const DedupeResult& r, u64* keys_buf, uint64_t buf_words, int K, u64* out_k, u32* out_c, uint64_t cap,
                   uint64_t* n_out);
+// collapse.hip
 int collapse_pass(zk_ctx* c, const u64* keys, uint64_t n, int shift, int bits, int pack, u64* out, uint64_t cap, uint64_t* n_out,
                   uint64_t max_tiles = 0);
-int sort_stream(zk_ctx* c, const StreamSrc& src, u64* buf_a, u64* buf_b, uint64_t cap, uint64_t* n_keys,
-                uint64_t acgt[4], u64** result);
 // stream_pass.hip: histogram + first pass over static stream ranges
 struct StreamRows { u32* rows = nullptr; u64* offs = nullptr; u32 ranges = 0, radix = 0; u32* gcodes = nullptr; u16* gvalid = nullptr;
                     u32 strands = 1;             // 2 (ZK_KEYS_BOTH): rows [ranges + w] are the reverse strand of range w

@@ -299,7 +299,7 @@ int mirror_expand(zk_ctx* c, const u64* ck, const u32* cc, uint64_t n, int K, u6
 // Canonical mode counts the copies of a k-mer BEFORE the sort is finished -- three ways, tried in this order (zk_tune
 // ZK_TUNE_EARLY_COLLAPSE picks one for tests):
 //   (1) block dedupe: LSD passes over the TOP bits until the blocks of equal top bits are small, then an LDS hash table per
-//       block counts the copies and leaves the block sorted (radix_sort.hip::dedupe_kernel) -- two full-size passes on a
+//       block counts the copies and leaves the block sorted (dedupe_blocks.hip::dedupe_kernel) -- two full-size passes on a
 //       50 M-read batch, and the counted list is finished; dedupe_finish also prepares the mirror sort;
 //   (2) collapse_kernel: LSD passes over the low bits until the copies are within a tile of each other, the next digit ranked
 //       tile by tile with the run lengths counted in LDS, words sorted from that bit up;
@@ -568,7 +568,7 @@ static int count_blocks(zk_ctx* c, const KmerizePlan& p, const SortBufs& b, cons
 }
 
 // COUNT_FUSED: the keys are sorted by their low fused_bit bits.  Runs are counted inside the tile-local ranking of the next digit
-// (radix_sort.hip::collapse_kernel): that pass writes one word per run instead of every key, into the other buffer, and no pass
+// (collapse.hip::collapse_kernel): that pass writes one word per run instead of every key, into the other buffer, and no pass
 // of its own reads the keys again to count.  Its output is tile-major, so the passes over the words start at fused_bit.  Whether
 // it pays: the same kernel over the first tiles (low bits ascending: a random subset of the k-mers with all their copies).  The
 // list lands in the aux region; little duplication: every key to the end.

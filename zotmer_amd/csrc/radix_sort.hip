@@ -25,7 +25,6 @@
 #include <stdlib.h>
 #include "internal.hpp"
 #include "encode_tile.hpp"
-#include "dedupe.hpp"
 
 namespace zk {
 
@@ -50,21 +49,6 @@ struct Cfg {
     static_assert(64 * ITEMS < 65536, "per-wave ranks are 16-bit");
     static_assert(RADIX <= MAX_RADIX && RBITS * MAX_PASSES >= 64, "RBITS");
 };
-
-static PassPlan make_plan(int key_bits, int rbits, int lo = 0) {
-    PassPlan p;
-    if (key_bits < 1) key_bits = 1;
-    if (key_bits > 64) key_bits = 64;
-    p.passes = (key_bits + rbits - 1) / rbits;
-    int base = key_bits / p.passes, rem = key_bits % p.passes, s = lo;
-    for (int i = 0; i < MAX_PASSES; i++) { p.shift[i] = 0; p.bits[i] = 0; }
-    for (int i = 0; i < p.passes; i++) {
-        p.bits[i] = base + (i < rem ? 1 : 0);
-        p.shift[i] = s;
-        s += p.bits[i];
-    }
-    return p;
-}
 
 struct SortArgs {
     // array source
@@ -570,24 +554,6 @@ __device__ __forceinline__ u64 lookback_segmented(const SortArgs& a, u32 tile, i
     return base + sum;
 }
 
-// match-any over the digit bits: on return (plo, phi) = the live lanes of the wave that hold the same digit as this lane.
-// All RBITS bits are always tested (bits above the pass's width are zero in every lane, so they change nothing) -- no
-// data- or pass-dependent branch.  Four vector instructions per bit: the bit as 0 / ~0 (v_bfe_i32, kept opaque: left to
-// itself the compiler rebuilds it from a shift, a sign compare and an arithmetic shift), its ballot, and per half ONE
-// three-input boolean op  peers &= ~(ballot ^ bit)  (v_bitop3_b32, truth table 0x90 for a & ~(b ^ c)).
-template <int RBITS>
-__device__ __forceinline__ void match_digit(u32 d, u64 live_mask, u32& plo, u32& phi) {
-    plo = (u32)live_mask; phi = (u32)(live_mask >> 32);
-#pragma unroll
-    for (int b = 0; b < RBITS; b++) {
-        int B;
-        asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(B) : "v"(d), "n"(b));
-        const u64 m = __ballot(B != 0);
-        plo = __builtin_amdgcn_bitop3_b32(plo, (u32)m, (u32)B, 0x90);
-        phi = __builtin_amdgcn_bitop3_b32(phi, (u32)(m >> 32), (u32)B, 0x90);
-    }
-}
-
 template <class C, int SRC, bool PAIRS>
 __global__ __launch_bounds__(C::BLOCK, C::WPE) void pass_kernel(SortArgs a) {
     constexpr int BLOCK = C::BLOCK, ITEMS = C::ITEMS, RADIX = C::RADIX, NW = C::NW, DPT = C::DPT;
@@ -745,590 +711,6 @@ __global__ __launch_bounds__(C::BLOCK, C::WPE) void pass_kernel(SortArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ZK_STAMP(7);         // keys stored
 #endif
-}
-
-// ---------------------------------------------------------------------------------------
-// Collapse pass (zk_kmerize, canonical keys; see pipeline.hip::kmerize_full).
-//
-// Input: the keys ordered by their low `shift` bits, where 2^shift is within a factor of a tile of the number of keys -- so
-// all copies of a k-mer (they share every bit) sit within a few dozen slots of each other, i.e. nearly always in ONE tile,
-// interleaved with the few other k-mers that share their low bits.  The tile is ranked by the NEXT digit exactly as a sort
-// pass would and parked in LDS grouped by that digit: inside a digit group the keys are still in input order, hence ordered
-// by shift + bits low bits, hence equal keys are neighbours.  Instead of scattering the 8192 keys to the digit's global
-// place, the runs are counted right there and the tile writes one word (key << pack | run length) per run, tiles one after
-// the other (a one-word look-back per tile; no global histogram of this digit is needed at all).
-//
-// The output is NOT ordered by the digit across tiles -- it is tile-major -- so the upper-bit passes that follow start at
-// bit `shift`, not shift + bits: inside (tile, digit group) the words ascend by their low `shift` bits and the tiles
-// partition the range of those bits in ascending order, so for any digit value the stable pass collects tile 0's group,
-// tile 1's group, ... = ascending low bits.  This needs the FIRST of those passes to use exactly this digit (a narrower one
-// would concatenate two groups of one tile, whose low bits overlap): the caller takes `bits` from sort_first_bits.
-// LSD invariant kept; a run cut by a tile edge (or a k-mer whose copies were not neighbours) yields two words with the
-// same key, which reduce_by_key adds up after the sort, as before.
-// `split`: runs are also cut every 512 slots so that a length always fits `pack` < 14 bits.
-//
-// Measured alternatives (config 2, 6.2 G keys; this version 21 ms): a persistent variant that prefetches the next tile's keys
-// -- with the one-word look-back all resident workgroups fall into lock step (2.5x slower); with per-workgroup output
-// regions and a compacting copy instead of the look-back no faster (the kernel is bound by its ~1800 vector instructions
-// per thread, not by the loads); counting in an LDS hash table (compare-and-swap claims, adds count; output in input
-// order, no ranking at all) 30-35 ms: the copies of a k-mer sit in the same 64 lanes, so every atomic instruction carries
-// several same-address conflicts (SQ_LDS_BANK_CONFLICT 43 % of the kernel's cycles).
-// ---------------------------------------------------------------------------------------
-template <int RBITS>
-struct CollapseSmem {
-    static constexpr int BLOCK = 512, ITEMS = 16, TILE = BLOCK * ITEMS, RADIX = 1 << RBITS, NW = BLOCK / 64, CHUNKS = TILE / 64;
-    u64 exch[TILE];
-    u16 cnt[NW][RADIX];
-    u32 digit_off[RADIX];
-    u64 mask[CHUNKS];           // head flags of slots [64 q, 64 q + 64)
-    u32 hbase[CHUNKS];          // heads before chunk q
-    u32 nexth[CHUNKS];          // first head at or after slot 64 (q + 1)
-    u32 wsum[NW];
-    u32 ticket;
-    u32 total_live;
-    u32 heads;
-    u64 gbase;
-};
-
-struct CollapseArgs {
-    const u64* kin;
-    u64 n;
-    u64* out;
-    u64 cap;
-    int shift, bits, pack, split;
-    u64* status;
-    u32* ticket;
-    u32 ticket_base;
-    u32 epoch;
-    u32* err;
-    u64* d_total;
-    u32 tiles;
-};
-
-template <int RBITS>
-__global__ __launch_bounds__(512, 4) void collapse_kernel(CollapseArgs a) {
-    using S = CollapseSmem<RBITS>;
-    constexpr int BLOCK = S::BLOCK, ITEMS = S::ITEMS, TILE = S::TILE, RADIX = S::RADIX, NW = S::NW, CHUNKS = S::CHUNKS;
-    static_assert(RADIX <= BLOCK, "one digit per thread");
-    __shared__ S sm;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const u32 tile = take_ticket(a.ticket, &sm.ticket) - a.ticket_base;
-    // as load_tile: a wave takes 64 * ITEMS consecutive keys (the ranks below number them wave by wave, row by row)
-    const u64 base = (u64)tile * TILE + (u64)wave * (64 * ITEMS) + lane;
-    const u32 dmask = (1u << a.bits) - 1u;
-
-    u64 key[ITEMS];
-    u32 live = 0;
-    if ((u64)(tile + 1) * TILE <= a.n) {
-        const u64* p = a.kin + base;
-#pragma unroll
-        for (int i = 0; i < ITEMS; i++) key[i] = p[i * 64];
-        live = (1u << ITEMS) - 1u;
-    } else {
-#pragma unroll
-        for (int i = 0; i < ITEMS; i++) {
-            const u64 g = base + (u64)i * 64;
-            key[i] = 0;
-            if (g < a.n) { key[i] = a.kin[g]; live |= 1u << i; }
-        }
-    }
-    u16* mycnt = sm.cnt[wave];
-    for (int q = lane; q < RADIX / 8; q += 64) reinterpret_cast<uint4*>(mycnt)[q] = make_uint4(0, 0, 0, 0);
-
-    // ---- rank inside the wave (see pass_kernel) -------------------------------------------------
-    u32 rank2[ITEMS / 2];
-#pragma unroll
-    for (int i = 0; i < ITEMS; i++) {
-        const bool lv = (live >> i) & 1u;
-        const u32 d = (u32)(key[i] >> a.shift) & dmask;
-        u32 plo, phi;
-        match_digit<RBITS>(d, __ballot(lv), plo, phi);
-        const u32 below = __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u));
-        const u32 npeer = (u32)__popc(plo) + (u32)__popc(phi);
-        const u32 pre = lv ? (u32)mycnt[d] : 0u;
-        if (i & 1) rank2[i / 2] |= (pre + below) << 16; else rank2[i / 2] = pre + below;
-        if (lv && below == npeer - 1) mycnt[d] = (u16)(pre + npeer);
-    }
-    __syncthreads();
-    // ---- per digit: exclusive scan over the waves, then over the digits ----------------------------
-    u32 acc = 0;
-    if (tid < RADIX) {
-#pragma unroll
-        for (int w = 0; w < NW; w++) {
-            const u32 t = sm.cnt[w][tid];
-            sm.cnt[w][tid] = (u16)acc;
-            acc += t;
-        }
-    }
-    const u32 inc = wave_incl_scan_u32(acc);
-    if (lane == 63) sm.wsum[wave] = inc;
-    __syncthreads();
-    {
-        u32 woff = 0;
-        for (int w = 0; w < wave; w++) woff += sm.wsum[w];
-        if (tid < RADIX) sm.digit_off[tid] = woff + inc - acc;
-        if (tid == BLOCK - 1) sm.total_live = woff + inc;
-    }
-    __syncthreads();
-    // ---- park, grouped by digit ------------------------------------------------------------------
-#pragma unroll
-    for (int i = 0; i < ITEMS; i++) {
-        const u32 d = (u32)(key[i] >> a.shift) & dmask;
-        if ((live >> i) & 1u) sm.exch[sm.digit_off[d] + sm.cnt[wave][d] + ((rank2[i / 2] >> (16 * (i & 1))) & 0xffffu)] = key[i];
-    }
-    __syncthreads();
-    const u32 total = sm.total_live;
-    // ---- heads of the runs: slot s = 512 i + tid, chunk q = 8 i + wave --------------------------------
-    u32 headbits = 0;
-#pragma unroll
-    for (int i = 0; i < ITEMS; i++) {
-        const u32 s = (u32)i * BLOCK + tid;
-        const u64 k = sm.exch[s];
-        const u64 prev = sm.exch[s ? s - 1 : 0];
-        key[i] = k;
-        const bool head = s < total && (s == 0 || k != prev || (a.split && tid == 0));
-        const u64 m = __ballot(head);
-        if (lane == 0) sm.mask[i * NW + wave] = m;
-        headbits |= (head ? 1u : 0u) << i;
-    }
-    __syncthreads();
-    // ---- heads before every chunk, first head after it; the tile's place in the output -----------------------
-    if (wave == 0) {
-        static_assert(CHUNKS == 128, "two chunks per lane");
-        const u64 m0 = sm.mask[2 * lane], m1 = sm.mask[2 * lane + 1];
-        const u32 p0 = (u32)__popcll(m0), p1 = (u32)__popcll(m1);
-        const u32 in2 = wave_incl_scan_u32(p0 + p1);
-        sm.hbase[2 * lane] = in2 - p0 - p1;
-        sm.hbase[2 * lane + 1] = in2 - p1;
-        // first head in the chunks AFTER q (suffix minimum over the chunks' first heads; `total` if there is none)
-        const u32 f0 = m0 ? (u32)(2 * lane) * 64 + (u32)__builtin_ctzll(m0) : 0xffffffffu;
-        const u32 f1 = m1 ? (u32)(2 * lane + 1) * 64 + (u32)__builtin_ctzll(m1) : 0xffffffffu;
-        u32 suf = f0 < f1 ? f0 : f1;          // inclusive suffix minimum over the lanes' pairs
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 t = (u32)__shfl_down((int)suf, o, 64);
-            if (lane + o < 64 && t < suf) suf = t;
-        }
-        u32 after = (u32)__shfl_down((int)suf, 1, 64);          // over the pairs after this lane's
-        if (lane == 63) after = 0xffffffffu;
-        const u32 a1 = after < total ? after : total;
-        sm.nexth[2 * lane + 1] = a1;
-        sm.nexth[2 * lane] = f1 < a1 ? f1 : a1;
-        const u32 m = (u32)__builtin_amdgcn_readlane((int)in2, 63);
-        const u64 excl = lookback_exclusive(a.status, tile, (u64)m, a.epoch, a.err);
-        if (lane == 0) {
-            sm.heads = m;
-            sm.gbase = excl;
-            if (tile == a.tiles - 1) *a.d_total = excl + m;
-            if (excl + m > a.cap) atomicOr(a.err, ZK_DERR_CAPACITY);
-        }
-    }
-    __syncthreads();
-    const u64 gbase = sm.gbase;
-    if (gbase + sm.heads > a.cap) return;
-    // ---- one word per run ---------------------------------------------------------------------------------
-#pragma unroll
-    for (int i = 0; i < ITEMS; i++) {
-        const u32 s = (u32)i * BLOCK + tid;
-        const u32 q = (u32)i * NW + wave;
-        const u64 m = sm.mask[q];
-        const u64 rest = (lane < 63) ? (m >> (lane + 1)) : 0ull;
-        const u32 nx = rest ? s + 1 + (u32)__builtin_ctzll(rest) : sm.nexth[q];
-        const u32 j = sm.hbase[q] + __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
-        if ((headbits >> i) & 1u) a.out[gbase + j] = (key[i] << a.pack) | (u64)(nx - s);
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// Block dedupe (zk_kmerize, canonical keys; see pipeline.hip::kmerize_full): counting AND finishing the sort in LDS.
-//
-// After LSD passes over the TOP b bits of the keys, the keys that share those bits form a block -- and all copies of a k-mer
-// lie in one block (they share every bit).  While a block is small (n / 2^b keys; 23.7 K after two passes on config 2) one
-// workgroup counts it in an LDS hash table: a compare-and-swap claims an entry for a key's remaining bits (its tag), an add
-// counts the copy.  The block's entries (~3 K distinct tags) are then sorted right there: a counting sort on the tag's top byte
-// (LDS counters), and inside each byte's group of a dozen entries the place is the number of smaller tags.  The block's
-// distinct k-mers therefore leave the kernel SORTED, and the blocks are in the order of their top bits: the counted list
-// needs no further sort pass at all.
-// The copies of a k-mer are spread over the whole block (unlike in the tile-local table variant that was measured for
-// collapse_kernel, where they sit in the same 64 lanes), so the atomics rarely collide.
-// Words (key << pack | count) go to the block's own place in `out` (its input offset: never more words than keys);
-// dedupe_unpack_kernel moves them together and splits them into keys and counts.  A count beyond the field leaves the field 0
-// and goes to a side list that patches the count afterwards.  A table that fills up (more than ~6 K distinct keys in a block:
-// little duplication) raises a flag and the caller sorts the keys the long way -- the result never depends on the table.
-// ---------------------------------------------------------------------------------------
-// TAG32: a tag fits 32 bits: entries of 4 + 4 bytes.  The blocks are not of one size -- a canonical k-mer more often starts with
-// A than with T (it is the smaller strand), so the sizes spread from ~0 to 2 x the mean with the first bases; the table is sized
-// for the big ones: one 1024-thread workgroup per CU.
-template <bool TAG32>
-struct DedupeSmem {
-    static constexpr int BLOCK = 1024, ITEMS = 8, TILE = BLOCK * ITEMS, NW = BLOCK / 64, ALL = TAG32 ? 12288 : 6144, SPT = ALL / BLOCK, NB = 256;
-    // a wave's side list: what one tile can add at worst (64 * ITEMS) on top of what is left standing after a tile (SIDE_KEEP)
-    static constexpr int SIDE_KEEP = 128, SIDE = SIDE_KEEP + 64 * ITEMS;
-    typedef typename std::conditional<TAG32, u32, u64>::type E;
-    E keys[ALL];             // tags (after the count: the entries again, grouped by their top byte)
-    u32 cnt[ALL];
-    E side[NW][SIDE];
-    u32 bc[NB];              // entries per top byte of the tag
-    u32 bbase[NB + 1];       // ... before it
-    u32 bfill[NB];
-    u32 ticket;
-};
-
-// cuts[v] = first index whose key >> tag_bits is >= v, v = 0 .. blocks
-__global__ void dedupe_cuts_kernel(const u64* __restrict__ k, u64 n, int tag_bits, u32 blocks, u64* __restrict__ cuts) {
-    const u32 v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v > blocks) return;
-    u64 lo = 0, hi = n;
-    while (lo < hi) {
-        const u64 mid = (lo + hi) >> 1;
-        if ((k[mid] >> tag_bits) < (u64)v) lo = mid + 1; else hi = mid;
-    }
-    cuts[v] = lo;
-}
-
-// ticket -> block: the blocks in order, or (second chance of the blocks dedupe2_kernel declined) the ones on a list
-__device__ __forceinline__ u32 dedupe_block_of(const DedupeArgs& a, u32 ticket) { return a.list ? a.list[ticket] : ticket; }
-
-// what a workgroup carries from one block to the next: the block it is about to count (its ticket), with the first tile of its keys
-// already asked for -- the ticket, the bounds and those keys travel while the previous block is being sorted and written
-template <int ITEMS>
-struct DedupeNext {
-    u32 chunk;
-    u64 lo, hi;
-    u64 key[ITEMS];
-};
-
-template <bool TAG32, bool TAGIN>
-__device__ __forceinline__ void dedupe_block(const DedupeArgs& a, DedupeSmem<TAG32>& sm, DedupeNext<DedupeSmem<TAG32>::ITEMS>& st, u32 (&ph)[8], u32& tlast) {
-    using S = DedupeSmem<TAG32>;
-    using E = typename S::E;
-    constexpr int BLOCK = S::BLOCK, ITEMS = S::ITEMS, TILE = S::TILE, ALL = S::ALL, SPT = S::SPT, NB = S::NB;
-    constexpr E EMPTY = (E)~(E)0;            // no entry.  A 64-bit tag never has all its bits set; a 32-bit one may: see `home`
-    constexpr u32 HS = TAG32 ? ALL - 1 : ALL;          // ... then the last entry belongs to the all-ones tag alone
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const u32 chunk = dedupe_block_of(a, st.chunk);
-    const u64 lo = st.lo, hi = st.hi;
-    const u32 maxc = (1u << a.pack) - 1u;
-    // whole tiles: one address, constant offsets; the cut last tile: per-key bounds
-    auto load = [&](u64 base, u64 end, u64 (&k)[ITEMS]) {
-        if constexpr (TAGIN) {
-            // (a tag is a whole key as far as the table goes: the block's bits are added when the words are written)
-            if (base + TILE <= end) {
-                // four tags per load (16 bytes a lane, a kilobyte a wave instruction; which thread takes which key is the table's
-                // business alone); a block starts wherever it starts: the loads are 4-byte aligned, no more
-                struct __attribute__((packed, aligned(4))) Tag4 { u32 a, b, c, d; };
-                static_assert(ITEMS % 4 == 0, "whole quads");
-#pragma unroll
-                for (int i = 0; i < ITEMS / 4; i++) {
-                    const Tag4 q = *reinterpret_cast<const Tag4*>(a.tin + base + (u64)i * (4 * BLOCK) + 4 * tid);
-                    k[4 * i] = q.a; k[4 * i + 1] = q.b; k[4 * i + 2] = q.c; k[4 * i + 3] = q.d;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < ITEMS; i++) {
-                    const u64 g = base + (u64)i * BLOCK + tid;
-                    k[i] = g < end ? (u64)a.tin[g] : ~0ull;
-                }
-            }
-        } else if (base + TILE <= end) {
-            const u64* p = a.kin + base + tid;
-#pragma unroll
-            for (int i = 0; i < ITEMS; i++) k[i] = p[i * BLOCK];
-        } else {
-#pragma unroll
-            for (int i = 0; i < ITEMS; i++) {
-                const u64 g = base + (u64)i * BLOCK + tid;
-                k[i] = g < end ? a.kin[g] : ~0ull;
-            }
-        }
-    };
-    if (tid == 0) sm.ticket = atomicAdd(a.counter, 1u);          // the block after this one: read after the next barrier
-    if (hi <= lo) {
-        if (tid == 0) a.nwords[chunk] = 0;
-        if (a.sub && tid < 64) a.sub[(u64)chunk * 64 + tid] = 0;
-        __syncthreads();
-        st.chunk = (u32)__builtin_amdgcn_readfirstlane((int)sm.ticket);
-        st.lo = st.hi = 0;
-        if (st.chunk < a.chunks) { const u32 nb = dedupe_block_of(a, st.chunk); st.lo = a.cuts[nb]; st.hi = a.cuts[nb + 1]; }
-        if (st.hi > st.lo) load(st.lo, st.hi, st.key);
-        return;
-    }
-    for (int q = tid; q < ALL * (int)sizeof(E) / 16; q += BLOCK) reinterpret_cast<uint4*>(sm.keys)[q] = make_uint4(~0u, ~0u, ~0u, ~0u);
-    for (int q = tid; q < ALL / 4; q += BLOCK) reinterpret_cast<uint4*>(sm.cnt)[q] = make_uint4(0, 0, 0, 0);
-    if (tid < NB) { sm.bc[tid] = 0; sm.bfill[tid] = 0; }
-    __syncthreads();
-    DD_PHASE(0);          // table cleared
-    const u32 nchunk = (u32)__builtin_amdgcn_readfirstlane((int)sm.ticket);
-    u64 nlo = 0, nhi = 0;
-    if (nchunk < a.chunks) { const u32 nb = dedupe_block_of(a, nchunk); nlo = a.cuts[nb]; nhi = a.cuts[nb + 1]; }
-    u32 bad = 0;
-    // The kernel is bound by its instruction count (188 per key with several keys probing at once, 88 with one tight probing
-    // loop per key -- a loop runs as long as the unluckiest of its 64 lanes).  So the common case has NO loop and no branch:
-    // one compare-and-swap at the key's home entry, the count added as 1 or 0 (adding 0 to another key's entry harms nobody);
-    // a key that finds another key at home goes to the wave's side list (its place from a ballot, no atomic), and the lists --
-    // about a tenth of the distinct keys with all their copies -- are inserted by linear probing afterwards, full wavefronts.
-    // (An order-preserving "hash" -- the tag scaled to the table -- would leave the table sorted, but the error variants of a
-    // k-mer differ from it in a few low bits and all want the same entry: 45 ms instead of 17.)
-    const u64 tmask = (1ull << a.tag_bits) - 1;
-    u32 nside = 0;          // entries in this wave's side list (the same in every lane)
-    auto home = [&](E e) -> u32 {
-        // the all-ones 32-bit tag (= the empty marker) has the last entry to itself: there the swap of "empty" for "empty"
-        // succeeds and leaves the word as it is; no other key is ever sent there
-        u32 x;
-        if constexpr (TAG32) x = (u32)e * 0x9E3779B1u; else x = ((u32)((u64)e >> 24) ^ ((u32)e * 0x85EBCA6Bu)) * 0x9E3779B1u;
-        if (TAG32 && e == EMPTY) return HS;
-        return (u32)(((u64)x * HS) >> 32);
-    };
-    auto cas = [&](u32 h, E e) -> E {
-        if constexpr (TAG32) return atomicCAS(&sm.keys[h], EMPTY, e);
-        else return (E)atomicCAS(reinterpret_cast<unsigned long long*>(&sm.keys[h]), (unsigned long long)EMPTY, (unsigned long long)e);
-    };
-    auto drain = [&]() {          // the wave's side list into the table by linear probing, 64 entries at a time
-        for (u32 i = (u32)lane; i < nside; i += 64) {
-            const E e = sm.side[wave][i];
-            u32 h = home(e) + 1;          // its home entry is taken: that is why it is here
-            h = h == HS ? 0u : h;
-            int p = 0;
-            for (; p < ALL; p++) {
-                const E old = cas(h, e);
-                if (old == EMPTY || old == e) break;
-                h = h + 1 == HS ? 0u : h + 1;
-            }
-            if (p < ALL) atomicAdd(&sm.cnt[h], 1u); else bad = 1;
-        }
-        nside = 0;
-    };
-    // (Measured: the eight compare-and-swaps of a tile issued back to back before any answer is used -- 24.6 ms against 21.3: the
-    // insert is bound by the LDS atomic unit's throughput (two atomics per key, ~47 K per block), not by the round trips.)
-    auto insert = [&](u64 k, bool valid) {
-        const E e = (E)(k & tmask);
-        const u32 h = home(e);
-        const E old = valid ? cas(h, e) : e;          // (a plain read first, the swap only for the lanes that see "empty": no faster)
-        const bool ok = old == EMPTY || old == e;
-        atomicAdd(&sm.cnt[h], (ok && valid) ? 1u : 0u);
-        const u64 m = __ballot(!ok);
-        if (m) {
-            if (!ok) sm.side[wave][nside + popc_below(m)] = e;
-            nside += (u32)__popcll(m);
-        }
-    };
-    u64 key[ITEMS], nk[ITEMS];
-#pragma unroll
-    for (int i = 0; i < ITEMS; i++) key[i] = st.key[i];          // the first tile was asked for during the previous block
-    for (u64 base = lo; base < hi; base += TILE) {
-        if (base + TILE < hi) load(base + TILE, hi, nk);
-        if (base + TILE <= hi) {
-#pragma unroll
-            for (int i = 0; i < ITEMS; i++) insert(key[i], true);
-        } else {
-#pragma unroll
-            for (int i = 0; i < ITEMS; i++) insert(key[i], key[i] != ~0ull);
-        }
-#pragma unroll
-        for (int i = 0; i < ITEMS; i++) key[i] = nk[i];
-        if (nside > (u32)S::SIDE_KEEP || base + TILE >= hi) drain();
-    }
-    DD_PHASE(1);          // keys inserted
-    st.chunk = nchunk; st.lo = nlo; st.hi = nhi;
-    if (nhi > nlo) load(nlo, nhi, st.key);          // the next block's first tile travels while this one is sorted and written
-    const int any_bad = __syncthreads_or((int)bad);
-    DD_PHASE(2);          // ... every wave done
-    if (any_bad) {
-        // the table filled up (a block with more distinct keys than it holds): the block goes on the list of those the host
-        // counts by sorting; only when that list is full is the whole run given up
-        if (tid == 0) {
-            const u32 at = atomicAdd(a.n_bad, 1u);
-            if (at < a.bad_cap) a.bad[at] = chunk; else atomicOr(a.flags, 1u);
-            a.nwords[chunk] = 0;
-        }
-        if (a.sub && tid < 64) a.sub[(u64)chunk * 64 + tid] = 0;
-        return;
-    }
-    // ---- the block's entries, sorted: a counting sort on the tag's top byte, then ranks inside each byte's group ---------
-    // thread t takes the entries t, t + BLOCK, ... into registers; the table's memory then takes them back grouped
-    E et[SPT];
-    u32 ec[SPT];
-    const int bsh = a.tag_bits > 8 ? a.tag_bits - 8 : 0;
-#pragma unroll
-    for (int j = 0; j < SPT; j++) {
-        et[j] = sm.keys[tid + j * BLOCK];
-        ec[j] = sm.cnt[tid + j * BLOCK];
-        if (ec[j]) atomicAdd(&sm.bc[(u32)((u64)et[j] >> bsh) & (NB - 1)], 1u);
-    }
-    __syncthreads();
-    DD_PHASE(3);          // entries read, byte groups counted
-    if (wave == 0) {
-        u32 c4[4], sum = 0;
-#pragma unroll
-        for (int r = 0; r < 4; r++) { c4[r] = sm.bc[4 * lane + r]; sum += c4[r]; }
-        const u32 inc = wave_incl_scan_u32(sum);
-        u32 run = inc - sum;
-#pragma unroll
-        for (int r = 0; r < 4; r++) { sm.bbase[4 * lane + r] = run; run += c4[r]; }
-        if (lane == 63) sm.bbase[NB] = inc;
-    }
-    __syncthreads();
-    const u32 total = sm.bbase[NB];
-    if (tid == 0) a.nwords[chunk] = total;
-    if (a.sub && tid < 64) a.sub[(u64)chunk * 64 + tid] = sm.bbase[4 * tid + 4] - sm.bbase[4 * tid];          // four top bytes = one 6-bit start
-#pragma unroll
-    for (int j = 0; j < SPT; j++) {
-        if (ec[j]) {
-            const u32 b = (u32)((u64)et[j] >> bsh) & (NB - 1);
-            const u32 p = sm.bbase[b] + atomicAdd(&sm.bfill[b], 1u);
-            sm.keys[p] = et[j];
-            sm.cnt[p] = ec[j];
-        }
-    }
-    __syncthreads();
-    DD_PHASE(4);          // grouped by top byte
-    const u64 hi_part = (u64)chunk << a.tag_bits;          // the bits every key of the block has above its tag
-    for (u32 i = (u32)tid; i < total; i += BLOCK) {
-        const E mine = sm.keys[i];
-        const u32 b = (u32)((u64)mine >> bsh) & (NB - 1);
-        const u32 g0 = sm.bbase[b], g1 = sm.bbase[b + 1];
-        u32 rank = 0;
-        for (u32 q = g0; q < g1; q++) rank += sm.keys[q] < mine ? 1u : 0u;
-        const u32 c = sm.cnt[i];
-        const u64 k = hi_part | (u64)mine;
-        if (c > maxc) {
-            const u32 at = atomicAdd(a.n_big, 1u);
-            if (at < a.big_cap) { a.big[2 * (u64)at] = k; a.big[2 * (u64)at + 1] = c; }
-            atomicOr(a.flags, 2u);
-        }
-        a.out[lo + g0 + rank] = (k << a.pack) | (u64)(c > maxc ? 0u : c);
-    }
-    DD_PHASE(5);          // ranked and written
-}
-
-// Persistent: one workgroup per CU (the table takes most of its LDS) draws the blocks from a counter -- in order, not strided:
-// the sizes go with the first bases, a stride of the grid would give one workgroup all the big ones.
-template <bool TAG32, bool TAGIN = false>
-__global__ __launch_bounds__(1024, 4) void dedupe_kernel(DedupeArgs a) {
-    using S = DedupeSmem<TAG32>;
-    static_assert(TAG32 || !TAGIN, "32-bit tags in, 32-bit tags in the table");
-    __shared__ S sm;
-    DedupeNext<S::ITEMS> st;
-    if (threadIdx.x == 0) sm.ticket = atomicAdd(a.counter, 1u);
-    __syncthreads();
-    st.chunk = (u32)__builtin_amdgcn_readfirstlane((int)sm.ticket);
-    st.lo = st.hi = 0;
-    if (st.chunk < a.chunks) { const u32 nb = dedupe_block_of(a, st.chunk); st.lo = a.cuts[nb]; st.hi = a.cuts[nb + 1]; }
-#pragma unroll
-    for (int i = 0; i < S::ITEMS; i++) {
-        const u64 g = st.lo + (u64)i * S::BLOCK + threadIdx.x;
-        if constexpr (TAGIN) st.key[i] = g < st.hi ? (u64)a.tin[g] : ~0ull;
-        else st.key[i] = g < st.hi ? a.kin[g] : ~0ull;
-    }
-    __syncthreads();          // the ticket word is free again
-    u32 ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    u32 tlast = a.dbg ? (u32)__builtin_amdgcn_s_memtime() : 0u;
-    (void)tlast;
-    u32 nblk = 0;
-    while (st.chunk < a.chunks) {
-        dedupe_block<TAG32, TAGIN>(a, sm, st, ph, tlast);          // leaves the next block in st
-        __syncthreads();          // the table and the ticket word are free again
-        DD_PHASE(6);
-        nblk++;
-    }
-    if (a.dbg && threadIdx.x == 0) {
-        for (int k = 0; k < 8; k++) a.dbg[(u64)blockIdx.x * 16 + k] = ph[k];
-        a.dbg[(u64)blockIdx.x * 16 + 8] = nblk;
-    }
-}
-
-// the words of the blocks, moved together and taken apart: block v's words -> keys / counts [incl[v] - nwords[v], incl[v])
-// out_m (or null): beside them the mirrored words (rc(key) << pack | count), already grouped by their low block bits -- block v of
-// the list IS group rc(v) of the mirror list (the first bases of a k-mer are the last of its reverse complement), and minc holds
-// the groups' inclusive ends: the first stage of the mirror sort comes for free with the copy that is made anyway.
-
-__global__ __launch_bounds__(256) void dedupe_unpack_kernel(const u64* __restrict__ in, const u64* __restrict__ cuts, const u64* __restrict__ incl,
-                                                            const u64* __restrict__ nwords, u32 chunks, int pack, u64* __restrict__ out_k,
-                                                            u32* __restrict__ out_c, u64* __restrict__ out_m, const u64* __restrict__ minc,
-                                                            int K, int gbases, MirrorHist mh, const u64* __restrict__ place24, int packed_out) {
-    __shared__ u32 bins[4 * 512];          // the digit histograms of the mirror sort's passes: it reads every word anyway
-    const bool hist = out_m && mh.passes > 0;
-    if (hist) {
-        for (int q = threadIdx.x; q < 4 * 512; q += blockDim.x) bins[q] = 0;
-        __syncthreads();
-    }
-    const u64 maxc = (1ull << pack) - 1;
-    for (u32 v = blockIdx.x; v < chunks; v += gridDim.x) {
-        const u64 cnt = nwords[v];
-        const u64 dst0 = incl[v] - cnt;
-        const u64* src = in + cuts[v];
-        const u64 mdst = (out_m && !place24) ? minc[(u32)revcomp(gbases, (u64)v)] - cnt : 0;
-        const int t6 = 2 * K - 2 * gbases - 6;          // where the 6 bits after the block bits sit in a key
-        // four words of a thread in flight at a time (a block is ~3 K words: twelve rounds of one load each otherwise)
-        for (u64 i0 = threadIdx.x; i0 < cnt; i0 += 4ull * blockDim.x) {
-            u64 w4[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const u64 i = i0 + (u64)q * blockDim.x;
-                w4[q] = i < cnt ? src[i] : 0;
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const u64 i = i0 + (u64)q * blockDim.x;
-                if (i >= cnt) break;
-                const u64 w = w4[q];
-                if (packed_out) out_k[dst0 + i] = w;          // (the union reads the words as they are: 12 bytes less moved per entry)
-                else { out_k[dst0 + i] = w >> pack; out_c[dst0 + i] = (u32)(w & maxc); }
-                if (out_m) {
-                    const u64 mw = (revcomp(K, w >> pack) << pack) | (w & maxc);
-                    // place24: grouped by 6 more bits -- the block is sorted, so the words that share their next three bases are
-                    // a run of it, and place24[v][those 6 bits] + i is the run's place in the group of the mirrored words
-                    const u64 at = place24 ? place24[(u64)v * 64 + ((u32)(w >> (pack + t6)) & 63u)] + i : mdst + i;
-                    out_m[at] = mw;
-                    if (hist) {
-#pragma unroll
-                        for (int p = 0; p < 4; p++)
-                            if (p < mh.passes) atomicAdd(&bins[p * 512 + ((u32)(mw >> mh.shift[p]) & ((1u << mh.bits[p]) - 1u))], 1u);
-                    }
-                }
-            }
-        }
-    }
-    if (hist) {
-        __syncthreads();
-        for (int q = threadIdx.x; q < mh.passes * 512; q += blockDim.x)
-            if (bins[q]) atomicAdd(&mh.raw[q], (u64)bins[q]);
-    }
-}
-
-// msz24[g] = words of the run (block v, 6-bit start j) whose mirror image is group g = rc3(j) << (2 gbases) | rc(v)
-__global__ void dedupe_mirror_sizes24_kernel(const u32* __restrict__ sub, u32 chunks, int gbases, u64* __restrict__ msz) {
-    const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= (u64)chunks * 64) return;
-    const u32 v = (u32)revcomp(gbases, g & ((u64)chunks - 1)), j = (u32)revcomp(3, g >> (2 * gbases));
-    msz[g] = sub[(u64)v * 64 + j];
-}
-// place24[v][j] = (start of group g(v, j) in the mirror list) - (start of the run inside block v): add the word's index in the block
-__global__ void dedupe_mirror_place24_kernel(const u32* __restrict__ sub, const u64* __restrict__ minc24, u32 chunks, int gbases,
-                                             u64* __restrict__ place) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;          // one wavefront per block: lane = j
-    const u32 v = (u32)(t >> 6), j = (u32)(t & 63);
-    if (v >= chunks) return;
-    const u32 x = sub[(u64)v * 64 + j];
-    const u32 before = wave_incl_scan_u32(x) - x;
-    const u64 g = ((u64)revcomp(3, (u64)j) << (2 * gbases)) | revcomp(gbases, (u64)v);
-    place[(u64)v * 64 + j] = minc24[g] - x - before;
-}
-
-// msz[g] = words of the block whose mirror image is group g
-__global__ void dedupe_mirror_sizes_kernel(const u64* __restrict__ nwords, u32 chunks, int gbases, u64* __restrict__ msz) {
-    const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < chunks) msz[g] = nwords[(u32)revcomp(gbases, (u64)g)];
-}
-
-// the counts that did not fit a word: found again by key in the sorted list
-__global__ void dedupe_big_kernel(const u64* __restrict__ big, u32 n_big, const u64* __restrict__ k, u64 n, u32* __restrict__ c, u32* err) {
-    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_big) return;
-    const u64 key = big[2 * (u64)t], cnt = big[2 * (u64)t + 1];
-    u64 lo = 0, hi = n;
-    while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (k[mid] < key) lo = mid + 1; else hi = mid; }
-    if (lo < n && k[lo] == key) c[lo] = (u32)cnt; else atomicOr(err, ZK_DERR_CAPACITY);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1862,10 +1244,80 @@ __global__ __launch_bounds__(512) void tag_cuts_kernel(const u64* __restrict__ k
 // host side
 // ---------------------------------------------------------------------------------------
 int launch_wide_pass(zk_ctx* c, const SortArgs& a);
-constexpr u64 WIDE_TILES_MAX_KEYS = ~0ull;          // (round 4: no limit any more, see V6)
+
+// One bit per tile of `tile` keys of a pass's input, set where a bucket of the pass before begins inside the tile (starts[b]: where
+// bucket b begins; null: the pass before had no buckets, every bit stays clear).  See pass_pipe_kernel, VAR 3.
+static int straddle_bitmap(zk_ctx* c, uint64_t n, u32 tile, const u64* starts, u32 buckets, u32 radix, const u32** bitmap) {
+    const u32 tiles = (u32)div_up(n, tile);
+    u32* bm;
+    ZK_TRY(arena_alloc(c, sizeof(u32) * (tiles / 32 + 1), (void**)&bm));
+    ZK_HIP(c, hipMemsetAsync(bm, 0, sizeof(u32) * (tiles / 32 + 1), c->stream));
+    if (starts) {
+        hipLaunchKernelGGL(straddle_kernel, dim3((radix + 255) / 256), dim3(256), 0, c->stream, starts, buckets, tile, bm);
+        ZK_HIP(c, hipGetLastError());
+    }
+    *bitmap = bm;
+    return ZK_OK;
+}
+
+// What the stream histogram left in h_scalars->rec_info: are the records uniform -- every (first_nl + 1)-th byte a newline, and no other?
+struct RecInfo { uint64_t first_nl; bool uniform; };
+static RecInfo uniform_records(const zk_ctx* c, uint64_t n_bytes) {
+    const uint64_t first_nl = c->h_scalars->rec_info[0], nl = c->h_scalars->rec_info[1], bad = c->h_scalars->rec_info[2];
+    return {first_nl, first_nl < 0x7fffffffull && n_bytes % (first_nl + 1) == 0 && bad == 0 && nl == n_bytes / (first_nl + 1)};
+}
+
+static void publish_tags(StreamTags* t, u64* cuts, uint64_t blocks) { t->cuts = cuts; t->blocks = (uint32_t)blocks; t->written = true; }
+
+// ---- the plan of sort_stream: a pure function of the knobs, the source, the buffers' size and (once counted; 0 before) the keys ----
+constexpr u32 SAMPLE_CAP = 1u << 20;          // keys the look before the sort sets aside at most
+struct StreamPlan {
+    int top;            // the bits [src.lo_bit, top) are sorted
+    PassPlan plan;
+    bool sampling;      // the look before the sort (StreamSample): the histogram sets keys aside
+    bool ranged;        // pass 0 over static stream ranges (stream_pass.hip) with its own histogram; else a look-back pass of this file
+    bool planes;        // ... leaving two arrays (low words, next digits), and tag_pass.hip's pass over them writes the tags.  Needs n
+    bool tags;          // the last of two look-back passes writes the keys' low 32 bits only, for the block dedupe
+    bool straddle;      // the pass after the stream's, and the one that writes tags, take places from LDS adds inside one bucket
+};
+static StreamPlan stream_plan(const zk_ctx* c, const StreamSrc& src, uint64_t cap, int rbits, bool pipe, uint64_t n) {
+    StreamPlan s;
+    s.top = (src.hi_bit > 0 && src.hi_bit < 2 * src.K) ? src.hi_bit : 2 * src.K;
+    s.plan = make_plan(s.top - src.lo_bit, rbits, src.lo_bit);
+    s.sampling = src.sample && cap >= 4ull * SAMPLE_CAP && src.mode == ZK_KEYS_CANONICAL;
+    s.ranged = c->stream_pass != 0;          // (ZK_KEYS_BOTH: the two strands of a range as two ranges)
+    // The usual plan (two passes over the top bits, tags for the block dedupe): pass 0 leaves the keys as two arrays, low words and
+    // next digits, 6 bytes a key, and the second pass is tag_pass.hip's count / scan / scatter over static segments.
+    const uint64_t n_pad = ((n + 63) & ~63ull) + 64;
+    s.planes = s.ranged && c->tag_pass && src.tags && s.plan.passes == 2 && s.plan.shift[0] == 32 && s.plan.bits[0] == 9 && s.plan.bits[1] == 9 &&
+               src.mode == ZK_KEYS_CANONICAL && 2 * src.K > 32 && n >= 4096 && 4 * n_pad + 2 * n + 64 <= 8 * cap;
+    // the block dedupe comes next and a key's low 32 bits are all it needs: the last of two passes writes those only
+    s.tags = src.tags && pipe && s.plan.passes == 2 && s.plan.shift[0] <= 32 && src.mode == ZK_KEYS_CANONICAL;
+    s.straddle = c->tag_words >= 2 && pipe;
+    return s;
+}
+
+// Record-aligned tiles of the pipeline's pass 0, for uniform records of first_nl bases + the separator: a workgroup of `block` threads
+// takes rpt records, a thread one of the cpr 16-window chunks of a record.  False (rec = 0: tiles of `tile` positions) where a
+// record is too short, the tile's bytes do not fit the image (img_words), or the records would fill the key slots no better (1.02).
+struct RecordTiles { u32 rec = 0, rpt = 0, cpr = 0, wpr = 0, cpr_inv = 0; };
+static bool record_tiles(uint64_t first_nl, int K, int block, int tile, int img_words, RecordTiles* t) {
+    const uint64_t rec = first_nl + 1;
+    const int64_t W = (int64_t)first_nl - K + 1;
+    if (rec < 16 || W < 1) return false;
+    const uint32_t cpr = (uint32_t)((W + 15) / 16);
+    const uint32_t rpt = (block / cpr) / 16 * 16;
+    if (!(rpt >= 16 && (uint64_t)rpt * rec / 16 + 3 <= (uint64_t)img_words && (double)rpt * (double)W > 1.02 * (double)tile * (double)W / (double)rec))
+        return false;
+    t->rec = (u32)rec; t->rpt = rpt; t->cpr = cpr; t->wpr = (u32)W;
+    t->cpr_inv = (u32)(((1ull << 32) + cpr - 1) / cpr);
+    return true;
+}
+// ---- end of the plan ----
 
 template <class C>
 struct Sorter {
+    static int rbits() { return C::RBITS; }
     static u32 tiles_for(const SortArgs& a, int src) {
         if (src == SRC_ARRAY) return (u32)div_up(a.n, C::TILE);
         if (a.rec) return (u32)div_up(a.n_bytes / a.rec, a.rpt);           // record-aligned tiles (pipeline pass 0 only)
@@ -1873,21 +1325,40 @@ struct Sorter {
         return (u32)div_up(a.n_bytes, pos);
     }
 
+    // Begin the look-back of one pass and fill what every pass kernel takes from the context.  pipe: the pipeline (a status word per
+    // tile and digit); else pass_kernel, whose look-back is segmented where the geometry says so.  stamps: the diagnostic buffers
+    static int begin_pass(zk_ctx* c, SortArgs& a, u32 tiles, u32 tickets, bool pipe, bool stamps = true) {
+        const bool seg = !pipe && C::SEG > 0;
+        ZK_TRY(lookback_begin(c, seg ? ((uint64_t)tiles / (C::SEG > 0 ? C::SEG : 1) + 2) * C::RADIX : (uint64_t)tiles * C::RADIX, tickets,
+                              &a.epoch, &a.ticket_base));
+        if (pipe || seg) ZK_TRY(part16_begin(c, (uint64_t)tiles * C::RADIX, &a.part));
+        a.status = c->status;
+        a.ticket = c->d_ticket;
+        a.err = c->d_err;
+        a.dbg = stamps ? c->dbg : nullptr;
+        a.dbg2 = (stamps && c->dbg) ? c->dbg + 8ull * tiles : nullptr;
+        return ZK_OK;
+    }
+    // ... of the pipeline: its grid (what fits a CU's 160 KB of LDS, and the scanner workgroups; one role ticket per workgroup) and tile counters
+    template <bool PAIRS>
+    static int begin_pipe(zk_ctx* c, SortArgs& a, u32 tiles, u32* grid, bool stamps) {
+        u32 g = (u32)c->num_cus * (sizeof(PipeSmem<C, PAIRS>) > 80 * 1024 ? 1 : 2);
+        if (g > tiles) g = tiles;
+        g += C::RADIX / 64;
+        ZK_TRY(begin_pass(c, a, tiles, g, true, stamps));
+        ZK_HIP(c, hipMemsetAsync(c->d_xticket, 0, 8 * 32 * sizeof(u32), c->stream));
+        a.xticket = c->d_xticket;
+        a.nx = 1u;
+        a.glog = 0;
+        *grid = g;
+        return ZK_OK;
+    }
+
     template <int SRC, bool PAIRS>
     static int launch_pass(zk_ctx* c, SortArgs a) {
         const u32 tiles = tiles_for(a, SRC);
         if (tiles == 0) return ZK_OK;
-        if (C::SEG > 0) {
-            ZK_TRY(lookback_begin(c, ((uint64_t)tiles / C::SEG + 2) * C::RADIX, tiles, &a.epoch, &a.ticket_base));
-            ZK_TRY(part16_begin(c, (uint64_t)tiles * C::RADIX, &a.part));
-        } else {
-            ZK_TRY(lookback_begin(c, (uint64_t)tiles * C::RADIX, tiles, &a.epoch, &a.ticket_base));
-        }
-        a.status = c->status;
-        a.ticket = c->d_ticket;
-        a.err = c->d_err;
-        a.dbg = c->dbg;
-        a.dbg2 = c->dbg ? c->dbg + 8ull * tiles : nullptr;
+        ZK_TRY(begin_pass(c, a, tiles, tiles, false));
         prof_begin(c, SRC == SRC_STREAM ? ZK_PROF_PASS_STREAM : (PAIRS ? ZK_PROF_PASS_PAIRS : ZK_PROF_PASS_KEYS),
                    SRC == SRC_STREAM ? a.n_bytes + 8 * a.n : (PAIRS ? 24 : 16) * a.n);
         hipLaunchKernelGGL((pass_kernel<C, SRC, PAIRS>), dim3(tiles), dim3(C::BLOCK), 0, c->stream, a);
@@ -1902,21 +1373,10 @@ struct Sorter {
       if constexpr (C::PIPE) {
         const u32 tiles = tiles_for(a, SRC);
         if (tiles == 0) return ZK_OK;
-        u32 grid = (u32)c->num_cus * (sizeof(PipeSmem<C>) > 80 * 1024 ? 1 : 2);          // what fits a CU's 160 KB of LDS
-        if (grid > tiles) grid = tiles;
-        grid += C::RADIX / 64;          // the scanner workgroups
-        ZK_TRY(lookback_begin(c, (uint64_t)tiles * C::RADIX, grid, &a.epoch, &a.ticket_base));   // one role ticket per workgroup
-        ZK_TRY(part16_begin(c, (uint64_t)tiles * C::RADIX, &a.part));
-        ZK_HIP(c, hipMemsetAsync(c->d_xticket, 0, 8 * 32 * sizeof(u32), c->stream));
-        a.xticket = c->d_xticket;
+        u32 grid;
+        ZK_TRY(begin_pipe<false>(c, a, tiles, &grid, true));
         a.nx = (c->xcd_group > 0 && c->num_xcd == 8) ? 8u : 1u;
-        a.glog = 0;
         while ((1 << (a.glog + 1)) <= c->xcd_group) a.glog++;
-        a.status = c->status;
-        a.ticket = c->d_ticket;
-        a.err = c->d_err;
-        a.dbg = c->dbg;
-        a.dbg2 = c->dbg ? c->dbg + 8ull * tiles : nullptr;
         prof_begin(c, SRC == SRC_STREAM ? ZK_PROF_PASS_STREAM : (a.prof_tag ? a.prof_tag : ZK_PROF_PASS_KEYS),
                    SRC == SRC_STREAM ? a.n_bytes + 8 * a.n : (a.tags_out ? 12 : 16) * a.n);
         if (SRC == SRC_ARRAY && a.tags_out && a.straddle)
@@ -1934,25 +1394,14 @@ struct Sorter {
       }
       return ZK_OK;
     }
-    // the same pipeline with a 32-bit payload (VAR 5; 6 = places from LDS adds where a.straddle allows)
+    // the same pipeline with a 32-bit payload (VAR 5; 6 = places from LDS adds where a.straddle allows): one global tile order, no stamps
     static constexpr bool PIPE_PAIRS = C::PIPE && C::ITEMS <= 8;          // (a tile of pairs is 12 bytes an entry: 8 K of them)
     static int launch_pipe_pairs(zk_ctx* c, SortArgs a) {
       if constexpr (PIPE_PAIRS) {
         const u32 tiles = (u32)div_up(a.n, C::TILE);
         if (tiles == 0) return ZK_OK;
-        u32 grid = (u32)c->num_cus * (sizeof(PipeSmem<C, true>) > 80 * 1024 ? 1 : 2);
-        if (grid > tiles) grid = tiles;
-        grid += C::RADIX / 64;          // the scanner workgroups
-        ZK_TRY(lookback_begin(c, (uint64_t)tiles * C::RADIX, grid, &a.epoch, &a.ticket_base));
-        ZK_TRY(part16_begin(c, (uint64_t)tiles * C::RADIX, &a.part));
-        ZK_HIP(c, hipMemsetAsync(c->d_xticket, 0, 8 * 32 * sizeof(u32), c->stream));
-        a.xticket = c->d_xticket;
-        a.nx = 1u;
-        a.glog = 0;
-        a.status = c->status;
-        a.ticket = c->d_ticket;
-        a.err = c->d_err;
-        a.dbg = nullptr; a.dbg2 = nullptr;
+        u32 grid;
+        ZK_TRY(begin_pipe<true>(c, a, tiles, &grid, false));
         prof_begin(c, ZK_PROF_PASS_PAIRS, 24 * a.n);
         if (a.straddle) hipLaunchKernelGGL((pass_pipe_kernel<C, SRC_ARRAY, 6>), dim3(grid), dim3(C::BLOCK), 0, c->stream, a, tiles);
         else hipLaunchKernelGGL((pass_pipe_kernel<C, SRC_ARRAY, 5>), dim3(grid), dim3(C::BLOCK), 0, c->stream, a, tiles);
@@ -1961,15 +1410,12 @@ struct Sorter {
       }
       return ZK_OK;
     }
-    // keys per tile of the geometry launch_keys_pass uses for this many keys
-    static u32 keys_pass_tile(zk_ctx* c, uint64_t n) {
-        if constexpr (C::PIPE && C::RBITS == 9 && C::BLOCK == 512) { if (c->wide_tiles && n <= WIDE_TILES_MAX_KEYS) return 16384u; }
-        return (u32)C::TILE;
-    }
+    // The default geometry hands its array passes to the 16 K-key tiles (same digits, same histograms): see V6
+    static constexpr bool WIDE = C::PIPE && C::RBITS == 9 && C::BLOCK == 512;
+    // keys per tile of the geometry launch_keys_pass uses
+    static u32 keys_pass_tile(zk_ctx* c) { return (WIDE && c->wide_tiles) ? 16384u : (u32)C::TILE; }
     static int launch_keys_pass(zk_ctx* c, const SortArgs& a) {
-        // the default geometry hands its array passes to the 16 K-key tiles (same digits, same histograms) while the array is
-        // not too big for them: see V6
-        if constexpr (C::PIPE && C::RBITS == 9 && C::BLOCK == 512) { if (c->wide_tiles && a.n <= WIDE_TILES_MAX_KEYS) return launch_wide_pass(c, a); }
+        if (WIDE && c->wide_tiles) return launch_wide_pass(c, a);
         if (C::PIPE) return launch_pipe<SRC_ARRAY>(c, a);
         return launch_pass<SRC_ARRAY, false>(c, a);
     }
@@ -2042,7 +1488,7 @@ struct Sorter {
     // lo_bit > 0: only the bits [lo_bit, key_bits) are sorted (the input is already ordered by the bits below)
     // unordered: nobody needs pairs of equal keys to stay in their order (the mirrored keys of the strand rebuild are all different) and
     // the order the keys arrive in means nothing: the first pass takes its places from LDS adds in every tile, the second wherever a
-    // tile lies inside one bucket of the first (pipeline geometries only)
+    // tile lies inside one bucket of the first (pipeline geometries only: it is read under PIPE_PAIRS alone)
     static int sort_pairs(zk_ctx* c, u64* keys, u64* alt, u32* vals, u32* valt, uint64_t n, int key_bits, u64** rk, u32** rv,
                           const u64* src_k = nullptr, const u32* src_v = nullptr, int mirror_K = 0, int lo_bit = 0, bool unordered = false) {
         PassPlan plan = make_plan(key_bits - lo_bit, C::RBITS, lo_bit);
@@ -2059,18 +1505,8 @@ struct Sorter {
             a.mirror_K = (p == 0) ? mirror_K : 0;
             if constexpr (PIPE_PAIRS) {
                 a.straddle = nullptr;
-                if (unordered && p <= 1) {
-                    const u32 tiles = (u32)div_up(n, C::TILE);
-                    u32* bm;
-                    ZK_TRY(arena_alloc(c, sizeof(u32) * (tiles / 32 + 1), (void**)&bm));
-                    ZK_HIP(c, hipMemsetAsync(bm, 0, sizeof(u32) * (tiles / 32 + 1), c->stream));
-                    if (p == 1) {
-                        hipLaunchKernelGGL(straddle_kernel, dim3((C::RADIX + 255) / 256), dim3(256), 0, c->stream, (const u64*)(ghist + (p - 1) * C::RADIX),
-                                           1u << plan.bits[p - 1], (u32)C::TILE, bm);
-                        ZK_HIP(c, hipGetLastError());
-                    }
-                    a.straddle = bm;
-                }
+                if (unordered && p <= 1)          // (p == 0: no bucket begins anywhere)
+                    ZK_TRY(straddle_bitmap(c, n, (u32)C::TILE, p == 1 ? ghist : nullptr, 1u << plan.bits[0], (u32)C::RADIX, &a.straddle));
                 ZK_TRY(launch_pipe_pairs(c, a));
             } else
             ZK_TRY((launch_pass<SRC_ARRAY, true>(c, a)));
@@ -2082,138 +1518,117 @@ struct Sorter {
         return ZK_OK;
     }
 
-    // Sort the k-mers of a base stream without ever storing them unsorted: histogram and first
-    // pass read the stream, the remaining passes ping-pong between buf_a and buf_b.
-    static int sort_stream(zk_ctx* c, const StreamSrc& src, u64* buf_a, u64* buf_b, uint64_t cap, uint64_t* n_keys,
-                           uint64_t acgt[4], u64** result) {
-        const int top = (src.hi_bit > 0 && src.hi_bit < 2 * src.K) ? src.hi_bit : 2 * src.K;     // sort the bits [lo_bit, top)
-        PassPlan plan = make_plan(top - src.lo_bit, C::RBITS, src.lo_bit);
-        u64* ghist;
-        ZK_TRY(arena_alloc(c, sizeof(u64) * MAX_PASSES * C::RADIX, (void**)&ghist));
-        SortArgs a = {};
-        a.stream = src.stream; a.n_bytes = src.n_bytes; a.K = src.K; a.mode = src.mode;
+    // ---- sort_stream, stage 1: count.  The digits of every pass, the base totals and the live keys, from one read of the stream
+    // (stream_pass.hip's histogram for the ranged pass 0, which needs the counts per range; else this file's); the look's keys are
+    // set aside in the second sort buffer, which is idle until pass 1.  *n and acgt are read back: n decides the grids to come.
+    static int stream_count(zk_ctx* c, const StreamSrc& src, const StreamPlan& sp, const SortArgs& a, u64* ghist, u64* buf_b, uint64_t cap,
+                            StreamRows* srows, uint64_t* n, uint64_t acgt[4]) {
         u64* d_acgt = c->d_scalars->acgt;
         u64* d_n = &c->d_scalars->n_keys;
-        // the look before the sort (StreamSample): the set-aside keys go to the second sort buffer, which is idle until pass 1
-        const u32 sample_cap = 1u << 20;
-        const bool sampling = src.sample && cap >= 4ull * sample_cap && src.mode == ZK_KEYS_CANONICAL;
-        // stream_pass.hip: the pass over static stream ranges needs the digit counts of pass 0 per range, from its own histogram kernel
-        const bool ranged = c->stream_pass != 0;          // (ZK_KEYS_BOTH: the two strands of a range as two ranges)
-        StreamRows srows;
-        if (ranged) {
+        u64* sample = sp.sampling ? buf_b : nullptr;
+        const int sample_shift = sp.sampling ? src.sample->shift : 0;
+        const u64 sample_value = sp.sampling ? src.sample->value : 0;
+        if (sp.ranged) {
             u64* rec_info = c->d_scalars->rec_info;
             ZK_HIP(c, hipMemsetAsync(rec_info, 0, ZK_SPAN(rec_info, sample_n), c->stream));          // the records and the sample counter
             hipLaunchKernelGGL(first_newline_kernel, dim3(1), dim3(256), 0, c->stream, src.stream, (u64)src.n_bytes, rec_info);
-            ZK_TRY(stream_hist(c, src.stream, src.n_bytes, src.K, src.mode, plan, ghist, (u32)C::RADIX, d_acgt, d_n, rec_info,
-                               sampling ? buf_b : nullptr, sample_cap, sampling ? src.sample->shift : 0, sampling ? src.sample->value : 0,
-                               (u32*)&c->d_scalars->sample_n,
+            ZK_TRY(stream_hist(c, src.stream, src.n_bytes, src.K, src.mode, sp.plan, ghist, (u32)C::RADIX, d_acgt, d_n, rec_info,
+                               sample, SAMPLE_CAP, sample_shift, sample_value, (u32*)&c->d_scalars->sample_n,
                                // the stream's image goes behind the set-aside keys in the second sort buffer (idle until pass 1)
-                               (char*)buf_b + (sampling ? 24ull * sample_cap : 0), 8 * cap - (sampling ? 24ull * sample_cap : 0), &srows));
-            hipLaunchKernelGGL(hist_scan_kernel, dim3(1), dim3(256), 0, c->stream, ghist, plan.passes, (int)C::RADIX, d_n);
+                               (char*)buf_b + (sp.sampling ? 24ull * SAMPLE_CAP : 0), 8 * cap - (sp.sampling ? 24ull * SAMPLE_CAP : 0), srows));
+            hipLaunchKernelGGL(hist_scan_kernel, dim3(1), dim3(256), 0, c->stream, ghist, sp.plan.passes, (int)C::RADIX, d_n);
             ZK_HIP(c, hipGetLastError());
         } else {
-            ZK_TRY(launch_hist<SRC_STREAM>(c, a, plan, ghist, d_acgt, d_n, sampling ? buf_b : nullptr, sample_cap,
-                                           sampling ? src.sample->shift : 0, sampling ? src.sample->value : 0));
+            ZK_TRY(launch_hist<SRC_STREAM>(c, a, sp.plan, ghist, d_acgt, d_n, sample, SAMPLE_CAP, sample_shift, sample_value));
         }
-        // the number of live keys decides the grids of the array passes: one small readback
         ZK_TRY(fetch_span(c, c->h_scalars->acgt, ZK_SPAN(acgt, sample_n)));
         ZK_TRY(stream_sync(c));
-        const uint64_t n = c->h_scalars->n_keys;
+        *n = c->h_scalars->n_keys;
         if (acgt) for (int b = 0; b < 4; b++) acgt[b] = c->h_scalars->acgt[b];
-#ifdef ZK_PHASES
-        // measurement of the histogram kernel with fewer LDS adds than it needs (tools/p0_phases.py): its counts are wrong, nothing
-        // may be sorted by them
-        if (const char* e = getenv("ZK_HIST_ATOMICS")) if (atoi(e) != 2) { *n_keys = 0; return ZK_OK; }
-#endif
-        *n_keys = n;
-        if (n > cap) return fail(c, ZK_ENOSPC, "sort buffers hold %llu keys, the stream has %llu", (unsigned long long)cap, (unsigned long long)n);
-        if (n == 0) return ZK_OK;
-        if (sampling) {
-            uint64_t sn = c->h_scalars->sample_n & 0xffffffffull;
-            if (sn > sample_cap) sn = sample_cap;
-            src.sample->seen = sn;
-            if (sn >= 4096) {          // enough to judge
-                u64* res = nullptr;
-                uint64_t distinct = 0;
-                ZK_TRY(sort_keys(c, buf_b, buf_b + sample_cap, sn, 2 * src.K, &res, 0, ZK_PROF_SAMPLE));
-                ZK_TRY(rle(c, res, sn, res, (u32*)(buf_b + 2ull * sample_cap), sn, &distinct));
-                src.sample->distinct = distinct;
-                const bool repeats = (double)distinct <= src.sample->max_ratio * (double)sn;
-                if (repeats == src.sample->want_distinct) return 1;          // declined: nothing sorted
-            }
-        }
-        a.kout = buf_a; a.shift = plan.shift[0]; a.bits = plan.bits[0]; a.ghist = ghist;
-        a.n = n;
-        if (ranged) {
-            const uint64_t first_nl = c->h_scalars->rec_info[0], nl = c->h_scalars->rec_info[1], bad = c->h_scalars->rec_info[2];
-            const bool uniform = first_nl < 0x7fffffffull && src.n_bytes % (first_nl + 1) == 0 && bad == 0 && nl == src.n_bytes / (first_nl + 1);
-            // The usual plan (two passes over the top bits, tags for the block dedupe): pass 0 leaves the keys as two arrays, low words and
-            // next digits, 6 bytes a key, and the second pass is tag_pass.hip's count / scan / scatter over static segments -- done here.
+        return ZK_OK;
+    }
+
+    // ---- stage 2: the look before the sort (StreamSample).  The set-aside keys are sorted and run-length counted; returns 1 -- as
+    // sort_stream then does -- when what they say is not what the caller wants: declined, nothing sorted.
+    static int stream_look(zk_ctx* c, const StreamSrc& src, u64* buf_b) {
+        uint64_t sn = c->h_scalars->sample_n & 0xffffffffull;
+        if (sn > SAMPLE_CAP) sn = SAMPLE_CAP;
+        src.sample->seen = sn;
+        if (sn < 4096) return ZK_OK;          // not enough to judge
+        u64* res = nullptr;
+        uint64_t distinct = 0;
+        ZK_TRY(sort_keys(c, buf_b, buf_b + SAMPLE_CAP, sn, 2 * src.K, &res, 0, ZK_PROF_SAMPLE));
+        ZK_TRY(rle(c, res, sn, res, (u32*)(buf_b + 2ull * SAMPLE_CAP), sn, &distinct));
+        src.sample->distinct = distinct;
+        const bool repeats = (double)distinct <= src.sample->max_ratio * (double)sn;
+        return repeats == src.sample->want_distinct ? 1 : ZK_OK;
+    }
+
+    // ---- stage 3: the first pass, from the stream to buf_a.  Five routes:
+    enum Route {
+        RANGED_PLANES,      // stream_pass.hip over static ranges, the keys left as two arrays; tag_pass.hip's stream_pass1 then writes the
+                            // tags to buf_b and the blocks' starts: the whole sort (*done)
+        RANGED,             // stream_pass.hip over static ranges, whole keys
+        RECORD_TILES,       // the pipeline, its tiles laid along uniform records (a.rec ...): no key slot is spent on the windows that
+                            // run into a separator (17 % of the positions for 150-base reads and K = 25)
+        POSITION_TILES,     // the pipeline, tiles of TILE stream positions: any other stream
+        PASS_KERNEL         // one workgroup per tile: both strands, and the geometries whose pipeline cannot take a stream
+    };
+    static constexpr bool PIPE_STREAM = C::PIPE && C::ITEMS == 16 && PipeSmem<C>::IMG_FITS && C::BLOCK <= 512;
+    static Route first_pass_route(const StreamSrc& src, const StreamPlan& sp, const RecInfo& ri, RecordTiles* rt) {
+        if (sp.ranged) return sp.planes ? RANGED_PLANES : RANGED;
+        if (!PIPE_STREAM || src.mode == ZK_KEYS_BOTH) return PASS_KERNEL;
+        // (uniform: checked by the histogram kernel -- the only newlines are one every `rec` bytes)
+        return (ri.uniform && record_tiles(ri.first_nl, src.K, C::BLOCK, C::TILE, PipeSmem<C>::IMG_WORDS, rt)) ? RECORD_TILES : POSITION_TILES;
+    }
+    static int stream_first_pass(zk_ctx* c, const StreamSrc& src, const StreamPlan& sp, SortArgs& a, u64* ghist, const StreamRows& srows,
+                                 u64* buf_a, u64* buf_b, uint64_t n, u64** result, bool* done) {
+        const RecInfo ri = uniform_records(c, src.n_bytes);
+        RecordTiles rt;
+        const Route route = first_pass_route(src, sp, ri, &rt);
+        const PassPlan& plan = sp.plan;
+        if (route == RANGED_PLANES) {
             const uint64_t n_pad = ((n + 63) & ~63ull) + 64;
-            const bool planes = c->tag_pass && src.tags && plan.passes == 2 && plan.shift[0] == 32 && plan.bits[0] == 9 && plan.bits[1] == 9 &&
-                                src.mode == ZK_KEYS_CANONICAL && 2 * src.K > 32 && n >= 4096 && 4 * n_pad + 2 * n + 64 <= 8 * cap;
-            if (planes) {
-                StreamPlanes pl{(u16*)((char*)buf_a + 4 * n_pad), plan.shift[1], plan.bits[1]};
-                ZK_TRY(stream_pass0(c, src.n_bytes, src.K, src.mode, plan.shift[0], plan.bits[0], ghist, srows, first_nl, uniform, buf_a, n,
-                                    c->stream_pass, &pl));
-                const uint64_t blocks = 1ull << (plan.bits[0] + plan.bits[1]);
-                u64* cuts;
-                ZK_TRY(arena_alloc(c, sizeof(u64) * (blocks + 1), (void**)&cuts));
-                ZK_TRY(stream_pass1(c, (const u32*)buf_a, pl.dig, n, ghist, 1u << plan.bits[0], plan.bits[1], (u32*)buf_b, cuts));
-                src.tags->cuts = cuts; src.tags->blocks = (uint32_t)blocks; src.tags->written = true;
-                *result = buf_b;
+            StreamPlanes pl{(u16*)((char*)buf_a + 4 * n_pad), plan.shift[1], plan.bits[1]};
+            ZK_TRY(stream_pass0(c, src.n_bytes, src.K, src.mode, plan.shift[0], plan.bits[0], ghist, srows, ri.first_nl, ri.uniform, buf_a, n,
+                                c->stream_pass, &pl));
+            const uint64_t blocks = 1ull << (plan.bits[0] + plan.bits[1]);
+            u64* cuts;
+            ZK_TRY(arena_alloc(c, sizeof(u64) * (blocks + 1), (void**)&cuts));
+            ZK_TRY(stream_pass1(c, (const u32*)buf_a, pl.dig, n, ghist, 1u << plan.bits[0], plan.bits[1], (u32*)buf_b, cuts));
+            publish_tags(src.tags, cuts, blocks);
+            *result = buf_b;
+            *done = true;
+            return ZK_OK;
+        }
+        if (route == RANGED)
+            return stream_pass0(c, src.n_bytes, src.K, src.mode, plan.shift[0], plan.bits[0], ghist, srows, ri.first_nl, ri.uniform, buf_a, n,
+                                c->stream_pass);
+        if constexpr (PIPE_STREAM) {
+            if (route == RECORD_TILES || route == POSITION_TILES) {
+                a.rec = rt.rec; a.rpt = rt.rpt; a.cpr = rt.cpr; a.wpr = rt.wpr; a.cpr_inv = rt.cpr_inv;          // (all 0: tiles of positions)
+                ZK_TRY(launch_pipe<SRC_STREAM>(c, a));
+                a.rec = 0;
                 return ZK_OK;
             }
-            ZK_TRY(stream_pass0(c, src.n_bytes, src.K, src.mode, plan.shift[0], plan.bits[0], ghist, srows, first_nl, uniform, buf_a, n,
-                                c->stream_pass));
-#ifdef ZK_PHASES
-            if (c->stream_pass >> 8) { *n_keys = 0; return ZK_OK; }          // measurement modes of the pass (diagnostic build, tools/p0_phases.py): nothing is counted
-#endif
-        } else
-        if constexpr (C::PIPE && C::ITEMS == 16 && PipeSmem<C>::IMG_FITS && C::BLOCK <= 512) {
-            // Uniform records (checked by the histogram kernel: the only newlines are one every `rec` bytes): tiles follow
-            // the records, so that no key slot is spent on the windows that run into a separator (17 % of the
-            // positions for 150-base reads and K = 25).  Any other stream: tiles of TILE positions.
-            const uint64_t first_nl = c->h_scalars->rec_info[0], nl = c->h_scalars->rec_info[1], bad = c->h_scalars->rec_info[2];
-            if (src.mode != ZK_KEYS_BOTH && first_nl < 0x7fffffffull) {
-                const uint64_t rec = first_nl + 1;
-                const int64_t W = (int64_t)first_nl - src.K + 1;
-                if (rec >= 16 && W >= 1 && src.n_bytes % rec == 0 && bad == 0 && nl == src.n_bytes / rec) {
-                    const uint32_t cpr = (uint32_t)((W + 15) / 16);
-                    const uint32_t rpt = (C::BLOCK / cpr) / 16 * 16;
-                    if (rpt >= 16 && (uint64_t)rpt * rec / 16 + 3 <= (uint64_t)PipeSmem<C>::IMG_WORDS &&
-                        (double)rpt * (double)W > 1.02 * (double)C::TILE * (double)W / (double)rec) {
-                        a.rec = (u32)rec; a.rpt = rpt; a.cpr = cpr; a.wpr = (u32)W;
-                        a.cpr_inv = (u32)(((1ull << 32) + cpr - 1) / cpr);
-                    }
-                }
-            }
-            if (src.mode != ZK_KEYS_BOTH) ZK_TRY(launch_pipe<SRC_STREAM>(c, a));
-            else ZK_TRY((launch_pass<SRC_STREAM, false>(c, a)));
-        } else {
-            ZK_TRY((launch_pass<SRC_STREAM, false>(c, a)));
         }
+        return launch_pass<SRC_STREAM, false>(c, a);
+    }
+
+    // ---- stage 4: the passes above, ping-pong between the buffers.  The last of two writes tags where the plan says so, and the
+    // blocks' starts with them (tag_cuts_kernel).
+    static int stream_upper_passes(zk_ctx* c, const StreamSrc& src, const StreamPlan& sp, SortArgs& a, u64* ghist, u64* buf_a, u64* buf_b,
+                                   uint64_t n, uint64_t* n_keys, u64** result) {
+        const PassPlan& plan = sp.plan;
         u64* in = buf_a; u64* out = buf_b;
-        a.rec = 0;
-        // the block dedupe comes next and a key's low 32 bits are all it needs: the last of two passes writes those only
-        const bool tags = src.tags && C::PIPE && plan.passes == 2 && plan.shift[0] <= 32 && src.mode == ZK_KEYS_CANONICAL;
         for (int p = 1; p < plan.passes; p++) {
             a.kin = in; a.kout = out; a.shift = plan.shift[p]; a.bits = plan.bits[p];
             a.ghist = ghist + p * C::RADIX;
-            a.tags_out = (tags && p == plan.passes - 1) ? 1 : 0;
+            a.tags_out = (sp.tags && p == plan.passes - 1) ? 1 : 0;
             a.straddle = nullptr;
             // (p == 1: the pass before came from the stream and had no order to keep)
-            if ((a.tags_out || p == 1) && c->tag_words >= 2 && C::PIPE) {
-                // the tiles in which a bucket of the pass before begins keep their order (see pass_pipe_kernel, VAR 3): one bit each
-                const u32 tile = keys_pass_tile(c, n), tiles = (u32)div_up(n, tile);
-                u32* bm;
-                ZK_TRY(arena_alloc(c, sizeof(u32) * (tiles / 32 + 1), (void**)&bm));
-                ZK_HIP(c, hipMemsetAsync(bm, 0, sizeof(u32) * (tiles / 32 + 1), c->stream));
-                hipLaunchKernelGGL(straddle_kernel, dim3((C::RADIX + 255) / 256), dim3(256), 0, c->stream, (const u64*)(ghist + (p - 1) * C::RADIX),
-                                   1u << plan.bits[p - 1], tile, bm);
-                ZK_HIP(c, hipGetLastError());
-                a.straddle = bm;
-            }
+            if ((a.tags_out || p == 1) && sp.straddle)
+                ZK_TRY(straddle_bitmap(c, n, keys_pass_tile(c), ghist + (p - 1) * C::RADIX, 1u << plan.bits[p - 1], (u32)C::RADIX, &a.straddle));
 #ifdef ZK_PHASES
             if (const char* e = getenv("ZK_LOCAL_PASS")) a.dbg_local = atoi(e);
 #endif
@@ -2222,7 +1637,7 @@ struct Sorter {
             if (a.dbg_local) { *n_keys = 0; return ZK_OK; }          // (nothing is where it belongs: nothing may be counted from it)
 #endif
             if (a.tags_out) {
-                const u32 tile = keys_pass_tile(c, n), tiles = (u32)div_up(n, tile);
+                const u32 tile = keys_pass_tile(c), tiles = (u32)div_up(n, tile);
                 const uint64_t blocks = 1ull << (plan.bits[0] + plan.bits[1]);
                 u64* cuts;
                 ZK_TRY(arena_alloc(c, sizeof(u64) * (blocks + 1), (void**)&cuts));
@@ -2230,12 +1645,45 @@ struct Sorter {
                                    (const u64*)(ghist + C::RADIX), (const u64*)c->status, (u32)C::RADIX, tile, tiles, plan.shift[1], plan.bits[1],
                                    plan.bits[0], cuts);
                 ZK_HIP(c, hipGetLastError());
-                src.tags->cuts = cuts; src.tags->blocks = (uint32_t)blocks; src.tags->written = true;
+                publish_tags(src.tags, cuts, blocks);
             }
             u64* t = in; in = out; out = t;
         }
         *result = in;
         return ZK_OK;
+    }
+
+    // Sort the k-mers of a base stream without ever storing them unsorted: histogram and first
+    // pass read the stream, the remaining passes ping-pong between buf_a and buf_b.
+    static int sort_stream(zk_ctx* c, const StreamSrc& src, u64* buf_a, u64* buf_b, uint64_t cap, uint64_t* n_keys,
+                           uint64_t acgt[4], u64** result) {
+        StreamPlan sp = stream_plan(c, src, cap, C::RBITS, C::PIPE, 0);
+        u64* ghist;
+        ZK_TRY(arena_alloc(c, sizeof(u64) * MAX_PASSES * C::RADIX, (void**)&ghist));
+        SortArgs a = {};
+        a.stream = src.stream; a.n_bytes = src.n_bytes; a.K = src.K; a.mode = src.mode;
+        StreamRows srows;
+        uint64_t n = 0;
+        ZK_TRY(stream_count(c, src, sp, a, ghist, buf_b, cap, &srows, &n, acgt));
+#ifdef ZK_PHASES
+        // measurement of the histogram kernel with fewer LDS adds than it needs (tools/p0_phases.py): its counts are wrong, nothing
+        // may be sorted by them
+        if (const char* e = getenv("ZK_HIST_ATOMICS")) if (atoi(e) != 2) { *n_keys = 0; return ZK_OK; }
+#endif
+        *n_keys = n;
+        if (n > cap) return fail(c, ZK_ENOSPC, "sort buffers hold %llu keys, the stream has %llu", (unsigned long long)cap, (unsigned long long)n);
+        if (n == 0) return ZK_OK;
+        if (sp.sampling) ZK_TRY(stream_look(c, src, buf_b));          // (1: declined)
+        sp = stream_plan(c, src, cap, C::RBITS, C::PIPE, n);          // n is known: `planes`
+        a.kout = buf_a; a.shift = sp.plan.shift[0]; a.bits = sp.plan.bits[0]; a.ghist = ghist;
+        a.n = n;
+        bool done = false;
+        ZK_TRY(stream_first_pass(c, src, sp, a, ghist, srows, buf_a, buf_b, n, result, &done));
+        if (done) return ZK_OK;
+#ifdef ZK_PHASES
+        if (sp.ranged && (c->stream_pass >> 8)) { *n_keys = 0; return ZK_OK; }          // measurement modes of the ranged pass (diagnostic build, tools/p0_phases.py): nothing is counted
+#endif
+        return stream_upper_passes(c, src, sp, a, ghist, buf_a, buf_b, n, n_keys, result);
     }
 };
 
@@ -2262,25 +1710,25 @@ typedef Cfg<512, 16, 8, 1, 4, 32, true> V5;      // the pipeline with 8-bit digi
 typedef Cfg<1024, 16, 9, 1, 4, 32, true> V6;
 // 7 (pairs only): the pipeline with a payload -- 1024 threads x 8 pairs, 8 K-pair tiles, 115 KB of LDS, one workgroup per CU
 typedef Cfg<1024, 8, 9, 1, 4, 32, true> V7;
+static_assert(V3::RBITS == MIRROR_RBITS && V3::RADIX == MIRROR_RADIX, "dedupe_finish counts the digits of the default geometry");
 int launch_wide_pass(zk_ctx* c, const SortArgs& a) { return Sorter<V6>::launch_pipe<SRC_ARRAY>(c, a); }
-#define ZK_SORT_DISPATCH(c, CALL) ZK_SORT_DISPATCH_V((c)->sort_variant, CALL)
-#define ZK_SORT_DISPATCH_V(v, CALL)                 \
-    switch (v) {                                    \
+#define ZK_SORT_CASES(CALL)                         \
         case 0: return Sorter<V0>::CALL;            \
         case 1: return Sorter<V1>::CALL;            \
         case 2: return Sorter<V2>::CALL;            \
         case 4: return Sorter<V4>::CALL;            \
         case 5: return Sorter<V5>::CALL;            \
         case 6: return Sorter<V6>::CALL;            \
-        default: return Sorter<V3>::CALL;           \
-    }
+        default: return Sorter<V3>::CALL;
+#define ZK_SORT_DISPATCH(c, CALL) switch ((c)->sort_variant) { ZK_SORT_CASES(CALL) }
+// pairs: geometry 7 as well
+#define ZK_PAIRS_DISPATCH(c, CALL) switch ((c)->pairs_variant) { case 7: return Sorter<V7>::CALL; ZK_SORT_CASES(CALL) }
 
 static int sort_keys_lsd(zk_ctx* c, u64* keys, u64* alt, uint64_t n, int key_bits, u64** result) {
     ZK_SORT_DISPATCH(c, sort_keys(c, keys, alt, n, key_bits, result));
 }
 static int sort_pairs_lsd(zk_ctx* c, u64* keys, u64* alt, u32* vals, u32* valt, uint64_t n, int key_bits, u64** rk, u32** rv) {
-    if (c->pairs_variant == 7) return Sorter<V7>::sort_pairs(c, keys, alt, vals, valt, n, key_bits, rk, rv);
-    ZK_SORT_DISPATCH_V(c->pairs_variant, sort_pairs(c, keys, alt, vals, valt, n, key_bits, rk, rv));
+    ZK_PAIRS_DISPATCH(c, sort_pairs(c, keys, alt, vals, valt, n, key_bits, rk, rv));
 }
 
 // Large arrays: LSD passes over the top bits only, then every tile sorted to the end in LDS (tilesort.hip) -- unless a block of equal
@@ -2335,8 +1783,7 @@ int sort_keys_upper_counted(zk_ctx* c, u64* keys, u64* alt, uint64_t n, int key_
 int sort_pairs_upper(zk_ctx* c, u64* keys, u64* alt, u32* vals, u32* valt, uint64_t n, int key_bits, int lo_bit, u64** rk, u32** rv) {
     *rk = keys; *rv = vals;
     if (n == 0) return ZK_OK;
-    if (c->pairs_variant == 7) return Sorter<V7>::sort_pairs(c, keys, alt, vals, valt, n, key_bits, rk, rv, nullptr, nullptr, 0, lo_bit);
-    ZK_SORT_DISPATCH_V(c->pairs_variant, sort_pairs(c, keys, alt, vals, valt, n, key_bits, rk, rv, nullptr, nullptr, 0, lo_bit));
+    ZK_PAIRS_DISPATCH(c, sort_pairs(c, keys, alt, vals, valt, n, key_bits, rk, rv, nullptr, nullptr, 0, lo_bit));
 }
 
 // (rc(src_k[i]), src_v[i]) sorted by key; keys/alt/vals/valt are work buffers, the source arrays are only read
@@ -2345,237 +1792,23 @@ int sort_pairs_mirrored(zk_ctx* c, const u64* src_k, const u32* src_v, u64* keys
                         u64** rk, u32** rv, int lo_bit) {
     *rk = keys; *rv = vals;
     if (n == 0) return ZK_OK;
-    // (mirrored keys are all different, and their order of arrival means nothing: `unordered`)
-    if (c->pairs_variant == 7) return Sorter<V7>::sort_pairs(c, keys, alt, vals, valt, n, 2 * K, rk, rv, src_k, src_v, K, lo_bit, true);
-    ZK_SORT_DISPATCH_V(c->pairs_variant, sort_pairs(c, keys, alt, vals, valt, n, 2 * K, rk, rv, src_k, src_v, K, lo_bit));
+    // Mirrored keys are all different, and their order of arrival means nothing: `unordered`.  Every geometry is told so, and it is
+    // inert in all but 7: Sorter::sort_pairs reads it only under `if constexpr (PIPE_PAIRS)`, i.e. PIPE && ITEMS <= 8, and of the
+    // geometries above only V7 has both (V3, V5 and V6 are pipelines of 16 keys a thread; V0, V1, V2 and V4 are no pipelines).
+    ZK_PAIRS_DISPATCH(c, sort_pairs(c, keys, alt, vals, valt, n, 2 * K, rk, rv, src_k, src_v, K, lo_bit, true));
 }
-int sort_pairs_rbits(zk_ctx* c) { return (c->pairs_variant == 0 || c->pairs_variant == 1 || c->pairs_variant == 5) ? 8 : 9; }
 
-// digit width of the geometry used for key arrays (the truncated sort sizes its bit range with it)
+// digit width of the geometry used for key arrays / for pairs (the truncated sort sizes its bit range with it)
+int sort_rbits(zk_ctx* c) { ZK_SORT_DISPATCH(c, rbits()); }
+int sort_pairs_rbits(zk_ctx* c) { ZK_PAIRS_DISPATCH(c, rbits()); }
+
 // the digits sort_keys_upper / sort_keys_upper_counted will use for the bits [lo_bit, key_bits)
 PassPlan sort_plan_upper(zk_ctx* c, int key_bits, int lo_bit) { return make_plan(key_bits - lo_bit, sort_rbits(c), lo_bit); }
-
-int sort_rbits(zk_ctx* c) {
-    switch (c->sort_variant) { case 0: case 1: case 5: return 8; default: return 9; }
-}
 
 // width of the first digit of sort_keys_upper(key_bits, lo_bit) -- collapse_pass must group by exactly that digit
 int sort_first_bits(zk_ctx* c, int key_bits, int lo_bit) {
     if (lo_bit >= key_bits) return 0;
     return make_plan(key_bits - lo_bit, sort_rbits(c), lo_bit).bits[0];
-}
-
-// keys[0..n) ordered by their TOP b bits (of key_bits) -> the distinct keys with their counts, SORTED.  Two steps, because the
-// caller can only size the result once the first is done:
-//   dedupe_pass   counts the blocks (dedupe_kernel): words in `work` (at least as many words as keys), block by block.
-//                 *flags: bit 0 = some table filled up (the words are not to be used), bit 1 = some counts went to the side list.
-//                 max_chunks > 0: only the leading blocks (the sample; *n_in = the keys they cover).
-//   dedupe_finish moves the words together and apart into out_k / out_c (r.n_out entries each).
-__global__ void expand_tags_kernel(const u32* __restrict__ tags, const u64* __restrict__ cuts, u64 first_block, u64 n_blocks, int tag_bits, u64* __restrict__ out) {
-    for (u64 v = first_block + blockIdx.x; v < first_block + n_blocks; v += gridDim.x) {
-        const u64 lo = cuts[v], hi = cuts[v + 1], top = v << tag_bits;
-        for (u64 i = lo + threadIdx.x; i < hi; i += blockDim.x) out[i] = top | (u64)tags[i];
-    }
-}
-
-int expand_tags(zk_ctx* c, const u32* tags, const u64* cuts, uint32_t blocks, int tag_bits, u64* keys_out, uint64_t first_block, uint64_t n_blocks) {
-    if (n_blocks == 0) { first_block = 0; n_blocks = blocks; }
-    hipLaunchKernelGGL(expand_tags_kernel, dim3(grid_cap(c, n_blocks, 16)), dim3(256), 0, c->stream, tags, cuts, (u64)first_block, (u64)n_blocks,
-                       tag_bits, keys_out);
-    ZK_HIP(c, hipGetLastError());
-    return ZK_OK;
-}
-
-int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int pack, u64* work, uint64_t cap, DedupeResult* r,
-                uint64_t* n_in, uint64_t max_chunks, const u32* tags, const u64* tag_cuts, bool unsorted) {
-    *r = DedupeResult();
-    if (n_in) *n_in = n;
-    if (n == 0) return ZK_OK;
-    if (b < 1 || b > 24 || b >= key_bits || pack < 10 || pack > 31) return fail(c, ZK_EINTERNAL, "dedupe_pass: %d block bits of %d, pack %d", b, key_bits, pack);
-    if (cap < n) return fail(c, ZK_ENOSPC, "dedupe_pass: work buffer of %llu words for %llu keys", (unsigned long long)cap, (unsigned long long)n);
-    DedupeArgs a = {};
-    uint64_t chunks = 1ull << b;          // one block per value of the top bits
-    if (max_chunks && chunks > max_chunks) chunks = max_chunks;
-    u64 *cuts, *nwords, *incl, *big;
-    const u32 big_cap = 1u << 16;
-    if (tags) {
-        if (!tag_cuts || key_bits - b > 32) return fail(c, ZK_EINTERNAL, "dedupe_pass: tags of %d bits", key_bits - b);
-        cuts = const_cast<u64*>(tag_cuts);
-    } else ZK_TRY(arena_alloc(c, sizeof(u64) * (chunks + 1), (void**)&cuts));
-    ZK_TRY(arena_alloc(c, sizeof(u64) * chunks, (void**)&nwords));
-    ZK_TRY(arena_alloc(c, sizeof(u64) * chunks, (void**)&incl));
-    ZK_TRY(arena_alloc(c, sizeof(u64) * 2 * big_cap, (void**)&big));
-    a.tag_bits = key_bits - b;
-    if (!tags) hipLaunchKernelGGL(dedupe_cuts_kernel, dim3((u32)div_up(chunks + 1, 256)), dim3(256), 0, c->stream, keys, (u64)n, a.tag_bits, (u32)chunks, cuts);
-    a.kin = keys; a.tin = tags; a.n = n; a.cuts = cuts; a.out = work; a.nwords = nwords; a.pack = pack;
-    a.chunks = (u32)chunks;
-    a.flags = (u32*)&c->d_scalars->dedupe_flags;
-    a.counter = (u32*)&c->d_scalars->dedupe_counter;
-    a.n_big = (u32*)&c->d_scalars->dedupe_n_big;
-    a.big = big; a.big_cap = big_cap;
-    const u32 bad_cap = 64;
-    ZK_TRY(arena_alloc(c, sizeof(u32) * bad_cap, (void**)&a.bad));
-    a.bad_cap = bad_cap;
-    a.n_bad = (u32*)&c->d_scalars->dedupe_n_bad;
-    a.dbg = c->dbg ? c->dbg + 8192 : nullptr;
-    // the mirror sort can group by 6 more bits if the blocks say how their entries split on them: 64 counts per block, when the
-    // workspace has the room (and the finer grouping's tables after it: dedupe_finish)
-    // ... leaving what the sorts and the union after it need (their tables are a few bytes per thousand keys)
-    const bool two_per_cu = a.tag_bits <= 32 && c->dedupe_variant >= 0;
-    unsorted = unsorted && two_per_cu;          // (dedupe_kernel's blocks leave it sorted)
-    if (!max_chunks && !unsorted && a.tag_bits >= 14 && c->arena_size - c->arena_off > 64ull * chunks * (4 + 8 + 8) + (32ull << 20) + n / 16)
-        ZK_TRY(arena_alloc(c, sizeof(u32) * 64 * chunks, (void**)&a.sub));
-    ZK_HIP(c, hipMemsetAsync(&c->d_scalars->dedupe_flags, 0, ZK_SPAN(dedupe_flags, dedupe_n_bad), c->stream));
-    // algorithmic bytes: every key read once (a 32-bit tag, or the whole key), one word written per distinct key (added below, once
-    // the launch has said how many)
-    prof_begin(c, ZK_PROF_RLE, (tags ? 4 : 8) * n);
-    auto launch_one_per_cu = [&](const DedupeArgs& d) {
-        const u32 grid = d.chunks < (u32)c->num_cus ? d.chunks : (u32)c->num_cus;
-        if (tags) hipLaunchKernelGGL((dedupe_kernel<true, true>), dim3(grid), dim3(1024), 0, c->stream, d);
-        else if (d.tag_bits <= 32) hipLaunchKernelGGL((dedupe_kernel<true, false>), dim3(grid), dim3(1024), 0, c->stream, d);
-        else hipLaunchKernelGGL((dedupe_kernel<false, false>), dim3(grid), dim3(1024), 0, c->stream, d);
-    };
-    if (two_per_cu) {
-        ZK_TRY(arena_alloc(c, sizeof(u32) * chunks, (void**)&a.retry));
-        a.n_retry = (u32*)&c->d_scalars->dedupe_n_retry;
-        a.limit = (u32)c->dedupe_limit;
-        ZK_TRY(launch_dedupe2(c, a, tags != nullptr, c->dedupe_variant, unsorted));
-    } else launch_one_per_cu(a);
-    prof_end(c);
-    ZK_HIP(c, hipGetLastError());
-    ZK_TRY(fetch_span(c, &c->h_scalars->dedupe_flags, ZK_SPAN(dedupe_flags, dedupe_n_bad)));
-    ZK_TRY(fetch(c, &c->h_scalars->dedupe_n_in, cuts + chunks));
-    ZK_TRY(check_device_error(c));
-    if (two_per_cu && (uint32_t)c->h_scalars->dedupe_n_retry) {
-        // the blocks dedupe2_kernel declined (65 536 keys or more; a table that filled up): dedupe_kernel's table is larger and its
-        // counts are 32 bits wide -- what it declines too goes on the list the host counts by sorting
-        DedupeArgs d = a;
-        d.list = a.retry; d.chunks = (uint32_t)c->h_scalars->dedupe_n_retry; d.retry = nullptr; d.n_retry = nullptr;
-        ZK_HIP(c, hipMemsetAsync(a.counter, 0, sizeof(u32), c->stream));
-        launch_one_per_cu(d);
-        ZK_HIP(c, hipGetLastError());
-        ZK_TRY(fetch_span(c, &c->h_scalars->dedupe_flags, ZK_SPAN(dedupe_flags, dedupe_n_bad)));
-        ZK_TRY(check_device_error(c));
-    }
-    r->flags = (uint32_t)c->h_scalars->dedupe_flags;
-    r->n_big = (uint32_t)c->h_scalars->dedupe_n_big;
-    if (r->n_big > big_cap) r->flags |= 1;          // more counts beyond the field than the side list holds: the long way
-    const uint32_t n_bad = (uint32_t)c->h_scalars->dedupe_n_bad;
-    if (n_bad && n_bad <= bad_cap && !(r->flags & 1) && !max_chunks) {
-        // The few blocks whose table filled up (a stretch of the key space with more distinct k-mers than a table holds) are
-        // counted the plain way, one by one: their keys sorted by the bits below the block bits (the block's own place in `work`
-        // is the second buffer), run lengths into words at that place, the block's word count patched in.
-        uint32_t list[64];
-        ZK_HIP(c, hipMemcpy(list, a.bad, sizeof(u32) * n_bad, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < n_bad && !(r->flags & 1); i++) {
-            u64 lohi[2];
-            ZK_HIP(c, hipMemcpy(lohi, cuts + list[i], 2 * sizeof(u64), hipMemcpyDeviceToHost));
-            const uint64_t m = lohi[1] - lohi[0];
-            u64* res = nullptr;
-            u64* bk = const_cast<u64*>(keys) + lohi[0];          // the block's keys, sorted in place
-            if (tags) {
-                // only tags were written: the block's keys are made again, beside the lists (a block is a few thousand keys)
-                ZK_TRY(arena_alloc(c, 8 * m, (void**)&bk));
-                ZK_TRY(expand_tags(c, tags, cuts, (uint32_t)chunks, a.tag_bits, bk - lohi[0], list[i], 1));
-            }
-            ZK_TRY(sort_keys(c, bk, work + lohi[0], m, a.tag_bits, &res));
-            if (res != bk) ZK_HIP(c, hipMemcpyAsync(bk, res, 8 * m, hipMemcpyDeviceToDevice, c->stream));
-            uint64_t u = 0;
-            bool ovf = false;
-            ZK_TRY(rle(c, bk, m, work + lohi[0], nullptr, m, &u, pack, &ovf));
-            if (ovf) { r->flags |= 1; break; }          // (a count beyond the field in such a block: the long way after all)
-            ZK_HIP(c, hipMemcpy(nwords + list[i], &u, sizeof(u64), hipMemcpyHostToDevice));
-        }
-        a.sub = nullptr;          // the runs of those blocks were not counted: the mirror sort groups by the block bits only
-    } else if (n_bad > bad_cap) r->flags |= 1;
-    ZK_HIP(c, hipMemcpyAsync(incl, nwords, sizeof(u64) * chunks, hipMemcpyDeviceToDevice, c->stream));
-    ZK_TRY(scan64_inclusive(c, incl, chunks));
-    ZK_TRY(fetch(c, &c->h_scalars->dedupe_n_out, incl + chunks - 1));
-    ZK_TRY(stream_sync(c));
-    r->n_out = c->h_scalars->dedupe_n_out;
-    prof_add_bytes(c, ZK_PROF_RLE, 8 * r->n_out);          // one word written per distinct key
-    r->cuts = cuts; r->nwords = nwords; r->incl = incl; r->big = big; r->chunks = (uint32_t)chunks; r->pack = pack; r->work = work; r->sub = a.sub;
-    r->tag_bits = a.tag_bits; r->unsorted = unsorted;
-    if (n_in) *n_in = c->h_scalars->dedupe_n_in;          // keys covered by the blocks that were counted
-    return ZK_OK;
-}
-
-// out_m (or null; K odd or even, 2 * gbases block bits = all 4^gbases blocks counted): the mirrored words, grouped by their low
-// 2 * gbases bits (dedupe_unpack_kernel) -- ready for the passes over the bits above
-int dedupe_finish(zk_ctx* c, const DedupeResult& r, u64* out_k, u32* out_c, u64* out_m, int K, int gbases, u64** mirror_hist,
-                  int* mirror_group_bits, bool packed_out) {
-    if (mirror_hist) *mirror_hist = nullptr;
-    int gbits = 2 * gbases;
-    if (mirror_group_bits) *mirror_group_bits = gbits;
-    if (r.n_out == 0) return ZK_OK;
-    u64 *minc = nullptr, *place24 = nullptr;
-    if (out_m && (1ull << (2 * gbases)) != r.chunks) return fail(c, ZK_EINTERNAL, "dedupe_finish: %u blocks are not 4^%d", r.chunks, gbases);
-    if (out_m && r.sub && mirror_group_bits && 2 * K - gbits - 6 >= 8) {
-        // 6 more group bits: one pass less for the mirror sort (26 bits above the groups instead of 32 at K = 25)
-        const uint64_t runs = 64ull * r.chunks;
-        u64* minc24;
-        ZK_TRY(arena_alloc(c, sizeof(u64) * runs, (void**)&minc24));
-        ZK_TRY(arena_alloc(c, sizeof(u64) * runs, (void**)&place24));
-        hipLaunchKernelGGL(dedupe_mirror_sizes24_kernel, dim3((u32)div_up(runs, 256)), dim3(256), 0, c->stream, r.sub, r.chunks, gbases, minc24);
-        ZK_TRY(scan64_inclusive(c, minc24, runs));
-        hipLaunchKernelGGL(dedupe_mirror_place24_kernel, dim3((u32)div_up(runs, 256)), dim3(256), 0, c->stream, r.sub, minc24, r.chunks, gbases, place24);
-        ZK_HIP(c, hipGetLastError());
-        gbits += 6;
-        *mirror_group_bits = gbits;
-    }
-    MirrorHist mh = {};
-    if (out_m && mirror_hist && c->sort_variant == 3) {
-        // the digit counts of the passes that will sort the mirrored words above their group bits (sort_keys_upper_counted)
-        const PassPlan plan = make_plan(2 * K - gbits, V3::RBITS, gbits + r.pack);
-        if (plan.passes <= 4) {
-            ZK_TRY(arena_alloc(c, sizeof(u64) * MAX_PASSES * V3::RADIX, (void**)&mh.raw));
-            ZK_HIP(c, hipMemsetAsync(mh.raw, 0, sizeof(u64) * MAX_PASSES * V3::RADIX, c->stream));
-            mh.passes = plan.passes;
-            for (int p = 0; p < plan.passes; p++) { mh.shift[p] = plan.shift[p]; mh.bits[p] = plan.bits[p]; }
-            *mirror_hist = mh.raw;
-        }
-    }
-    if (out_m && !place24) {
-        ZK_TRY(arena_alloc(c, sizeof(u64) * r.chunks, (void**)&minc));
-        hipLaunchKernelGGL(dedupe_mirror_sizes_kernel, dim3((r.chunks + 255) / 256), dim3(256), 0, c->stream, r.nwords, r.chunks, gbases, minc);
-        ZK_TRY(scan64_inclusive(c, minc, r.chunks));
-    }
-    if (packed_out && r.n_big) return fail(c, ZK_EINTERNAL, "dedupe_finish: packed words with %u counts beyond the field", r.n_big);
-    prof_begin(c, ZK_PROF_SELECT, ((out_m ? 28 : 20) - (packed_out ? 4 : 0)) * r.n_out);
-    hipLaunchKernelGGL(dedupe_unpack_kernel, dim3((u32)c->num_cus * 8), dim3(256), 0, c->stream, r.work, r.cuts, r.incl, r.nwords, r.chunks, r.pack, out_k, out_c,
-                       out_m, minc, K, gbases, mh, place24, packed_out ? 1 : 0);
-    if (r.n_big) hipLaunchKernelGGL(dedupe_big_kernel, dim3((r.n_big + 255) / 256), dim3(256), 0, c->stream, r.big, r.n_big, out_k, (u64)r.n_out, out_c, c->d_err);
-    prof_end(c);
-    ZK_HIP(c, hipGetLastError());
-    return ZK_OK;
-}
-
-// keys[0..n) ordered by their low `shift` bits -> out[0..*n_out): one word (key << pack | run length) per run of equal keys
-// inside a tile grouped by the digit [shift, shift + bits); max_tiles > 0: only the leading tiles, at most that many (the
-// sample).  2^pack must exceed 512 (run pieces are cut at 512 when 2^pack <= 8192).
-int collapse_pass(zk_ctx* c, const u64* keys, uint64_t n, int shift, int bits, int pack, u64* out, uint64_t cap, uint64_t* n_out,
-                  uint64_t max_tiles) {
-    *n_out = 0;
-    if (n == 0) return ZK_OK;
-    if (bits < 1 || bits > 9 || pack < 10 || pack > 31) return fail(c, ZK_EINTERNAL, "collapse_pass: bits %d, pack %d", bits, pack);
-    CollapseArgs a = {};
-    constexpr uint64_t TILE = CollapseSmem<9>::TILE;
-    uint64_t tiles = div_up(n, TILE);
-    if (max_tiles && tiles > max_tiles) { tiles = max_tiles; n = tiles * TILE; }
-    a.kin = keys; a.n = n; a.out = out; a.cap = cap; a.shift = shift; a.bits = bits; a.pack = pack;
-    a.split = (1u << pack) <= (u32)TILE;
-    a.tiles = (u32)tiles;
-    ZK_TRY(lookback_begin(c, tiles, (u32)tiles, &a.epoch, &a.ticket_base));
-    a.status = c->status; a.ticket = c->d_ticket; a.err = c->d_err; a.d_total = &c->d_scalars->total;
-    prof_begin(c, ZK_PROF_RLE, 8 * n);
-    if (bits <= 8) hipLaunchKernelGGL(collapse_kernel<8>, dim3((u32)tiles), dim3(512), 0, c->stream, a);
-    else hipLaunchKernelGGL(collapse_kernel<9>, dim3((u32)tiles), dim3(512), 0, c->stream, a);
-    prof_end(c);
-    ZK_HIP(c, hipGetLastError());
-    ZK_TRY(fetch(c, &c->h_scalars->total));
-    ZK_TRY(check_device_error(c));
-    *n_out = c->h_scalars->total;
-    return ZK_OK;
 }
 
 int sort_stream(zk_ctx* c, const StreamSrc& src, u64* buf_a, u64* buf_b, uint64_t cap, uint64_t* n_keys,
