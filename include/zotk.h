@@ -141,6 +141,7 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_FORMAT_PAIRS 20 /* zk_format_pairs: the length pass (16 B read, 8 written per pair) and the write pass (24 B read per
                                    pair + the text), one record each */
 #define ZK_PROF_PROBE_SCAN 21   /* zk_probe_scan: the one pass over the set (8 B read per entry, whatever the number of windows) */
+#define ZK_PROF_BAIT_TALLY 22   /* zk_bait_tally: the one pass over the set (8 B read per entry; the adds depend on the hits) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -205,6 +206,34 @@ int zk_capture_hits(zk_ctx* ctx, const zk_bait_table* baits, const zk_bait_table
  * spans[n_baits + 1 + b] = its first byte in d_out (b = n_baits: the ends).  Paired input: once per mate, with that mate's text. */
 int zk_capture_gather(zk_ctx* ctx, const uint64_t* d_pairs, uint64_t n_pairs, uint32_t n_baits, const uint8_t* d_text,
                       const uint64_t* d_lines, uint64_t n_lines, uint8_t* d_out, uint64_t cap, uint64_t* spans, uint64_t* n_bytes);
+
+/* ---- complete alleles of a k-mer index, `zot mlst` (commands/mlst.py, library/index.py) -----------------------------------
+ * The index of library/index.py:67-125 -- S, the sorted distinct K-mers of both strands of every FASTA record; T, CSR offsets;
+ * U, the ascending record numbers per k-mer -- is a bait table: zk_bait_table_build makes it from the records' base stream.
+ *
+ * zk_bait_table_arrays: borrowed device pointers to a table's arrays (keys[n_keys], offs[n_keys + 1], ids[n_ids]; the S, T and
+ * U that index.py:117-123 writes), valid until zk_bait_table_free. */
+int zk_bait_table_arrays(const zk_bait_table* table, const uint64_t** d_keys, const uint32_t** d_offs, const uint32_t** d_ids);
+
+/* A table from arrays (copied device to device), for an index read from a file (KmerIndex.__init__, index.py:37-47).  Checked
+ * ON THE DEVICE before the directory is built, so that a damaged file can never become an out-of-range add in zk_bait_tally:
+ * 1 <= K <= 32, keys strictly ascending and < 4^K, offs[0] == 0, offs strictly increasing, offs[n_keys] == n_ids,
+ * n_ids < 2^32 - 1, every id < n_records, ids strictly ascending within a key.  Anything else: ZK_EINVAL, a message that names
+ * the first rule broken, *table untouched, nothing leaked.  n_keys == 0 (then n_ids == 0) is the empty table. */
+int zk_bait_table_from_arrays(zk_ctx* ctx, int K, const uint64_t* d_keys, uint64_t n_keys, const uint32_t* d_offs,
+                              const uint32_t* d_ids, uint64_t n_ids, uint64_t n_records, zk_bait_table** table);
+
+/* index.py:91 (lens[i] = len(xs), the distinct K-mers of both strands of record i): d_sizes[r] = the number of keys that list
+ * record r (n_records words, overwritten). */
+int zk_bait_record_sizes(zk_ctx* ctx, const zk_bait_table* table, uint32_t* d_sizes);
+
+/* mlst.py:45-49 (for x in xs: for j in idx[x]: cs[j] -= 1) counted upwards: d_hits[r] = the number of entries of d_kmers
+ * (ascending K-mers; an entry equal to its predecessor counts once) that are keys listing record r.  n_records words,
+ * overwritten.  n == 0, or a table without keys, writes zeros.  Record r is complete (mlst.py:51-54) when d_hits[r] equals its
+ * zk_bait_record_sizes.  The hits are sums of integers: the same call returns the same bits.  ZK_TALLY_TILE = the entries a
+ * workgroup takes per step (tests place their sizes around it). */
+#define ZK_TALLY_TILE 2048
+int zk_bait_tally(zk_ctx* ctx, const zk_bait_table* table, const uint64_t* d_kmers, uint64_t n, uint32_t* d_hits);
 
 /* basics.can (library/basics.py:231-250; used by `zot vars`): per k-mer, whichever of x and rc(x) has the smaller
  * murmer(., 17) -- x on a tie.  Element-wise, asynchronous; d_out may equal d_kmers. */

@@ -10,19 +10,9 @@
 //     capture.py:26-69, file.readFastq, file.py:38-52).
 // Records are located through the positions of the text's '\n' bytes (zk_line_ends): record r is lines 4r .. 4r+3.
 #include "internal.hpp"
+#include "bait_table.hpp"
 #include "compact.hpp"
 #include "read_window.hpp"
-
-// the table behind the opaque zk_bait_table of the C-ABI (device memory of its own, outlives the calls)
-struct zk_bait_table {
-    zk_ctx* ctx = nullptr;
-    u64* keys = nullptr;       // sorted distinct k-mers [n_keys]
-    u32* offs = nullptr;       // [n_keys + 1]: ids[offs[i], offs[i+1]) are the records of keys[i], ascending
-    u32* ids = nullptr;        // [n_ids]
-    u32* dir = nullptr;        // [2^bits + 1]: keys whose top `bits` of `kbits` equal b are keys[dir[b], dir[b+1])
-    uint64_t n_keys = 0, n_ids = 0, n_records = 0;
-    int K = 0, kbits = 0, bits = 0;
-};
 
 namespace zk {
 
@@ -84,29 +74,7 @@ struct DistinctWords {   // first of each run of equal words
 // ---------------------------------------------------------------------------------------
 // the table
 // ---------------------------------------------------------------------------------------
-struct BaitView {
-    const u64* keys; const u32* offs; const u32* ids; const u32* dir; u64 n_keys; int kbits, shift;
-};
-
-static BaitView view_of(const zk_bait_table* t) {
-    BaitView v{nullptr, nullptr, nullptr, nullptr, 0, 64, 0};
-    if (t && t->n_keys) v = BaitView{t->keys, t->offs, t->ids, t->dir, t->n_keys, t->kbits, t->kbits - t->bits};
-    return v;
-}
-
-// x -> ids[lo, hi) of the key equal to x.  A miss costs the directory's two words (one line) and, in a non-empty
-// bucket, a search among its ~1-2 keys.
-__device__ __forceinline__ bool bait_find(const BaitView& t, u64 x, u32& lo, u32& hi) {
-    if (t.n_keys == 0) return false;
-    if (t.kbits < 64 && (x >> t.kbits) != 0) return false;
-    const u64 bk = x >> t.shift;
-    u32 a = t.dir[bk];
-    const u32 end = t.dir[bk + 1];
-    u32 e = end;
-    while (a < e) { const u32 mid = (a + e) >> 1; if (t.keys[mid] < x) a = mid + 1; else e = mid; }
-    if (a < end && t.keys[a] == x) { lo = t.offs[a]; hi = t.offs[a + 1]; return true; }
-    return false;
-}
+// (the table itself, its view and the lookup: bait_table.hpp)
 
 __global__ void dir_kernel(const u64* __restrict__ keys, u64 n_keys, int shift, u64 nb, u32* __restrict__ dir) {
     for (u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x; b <= nb; b += (u64)gridDim.x * blockDim.x) {
@@ -120,7 +88,7 @@ __global__ void dir_kernel(const u64* __restrict__ keys, u64 n_keys, int shift, 
 
 __global__ void put_u32_kernel(u32* p, u32 v) { *p = v; }
 
-static void table_free(zk_bait_table* t) {
+void table_free(zk_bait_table* t) {
     if (!t) return;
     if (t->ctx) { enter(t->ctx); (void)hipStreamSynchronize(t->ctx->stream); }
     if (t->keys) (void)hipFree(t->keys);
@@ -130,10 +98,24 @@ static void table_free(zk_bait_table* t) {
     delete t;
 }
 
-static int tmalloc(zk_ctx* c, void** p, uint64_t bytes) {
+int tmalloc(zk_ctx* c, void** p, uint64_t bytes) {
     hipError_t e = hipMalloc(p, bytes < 256 ? 256 : bytes);
     if (e != hipSuccess) return fail(c, ZK_ENOMEM, "hipMalloc(%llu) for the bait table failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
     return ZK_OK;
+}
+
+int bait_table_directory(zk_ctx* c, zk_bait_table* t) {
+    // about one key per bucket
+    int bits = 1;
+    while (bits < 26 && (1ull << bits) < t->n_keys) bits++;
+    if (bits > t->kbits) bits = t->kbits;
+    t->bits = bits;
+    const u64 nb = 1ull << bits;
+    ZK_TRY(tmalloc(c, (void**)&t->dir, 4 * (nb + 1)));
+    hipLaunchKernelGGL(dir_kernel, dim3(grid_cap(c, div_up(nb + 1, 256), 16)), dim3(256), 0, c->stream, t->keys, (u64)t->n_keys, t->kbits - bits, nb, t->dir);
+    ZK_HIP(c, hipGetLastError());
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    return check_device_error(c);
 }
 
 static int bait_table_build(zk_ctx* c, const u8* stream, uint64_t n, int K, zk_bait_table* t) {
@@ -178,17 +160,7 @@ static int bait_table_build(zk_ctx* c, const u8* stream, uint64_t n, int K, zk_b
     hipLaunchKernelGGL(put_u32_kernel, dim3(1), dim3(1), 0, c->stream, t->offs + n_keys, (u32)n_ids);
     ZK_HIP(c, hipGetLastError());
     t->n_ids = n_ids; t->n_keys = n_keys;
-    // directory: about one key per bucket
-    int bits = 1;
-    while (bits < 26 && (1ull << bits) < n_keys) bits++;
-    if (bits > t->kbits) bits = t->kbits;
-    t->bits = bits;
-    const u64 nb = 1ull << bits;
-    ZK_TRY(tmalloc(c, (void**)&t->dir, 4 * (nb + 1)));
-    hipLaunchKernelGGL(dir_kernel, dim3(grid_cap(c, div_up(nb + 1, 256), 16)), dim3(256), 0, c->stream, t->keys, (u64)n_keys, t->kbits - bits, nb, t->dir);
-    ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    return check_device_error(c);
+    return bait_table_directory(c, t);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -23,6 +23,7 @@ ZK_OK, ZK_EINVAL, ZK_ENOMEM, ZK_EHIP, ZK_ENOSPC, ZK_EOVERFLOW, ZK_EINTERNAL, ZK_
 KMERIZE_CANONICAL, KMERIZE_BOTH, KMERIZE_SUBSAMPLE, KMERIZE_CANONICAL_ONLY = 0, 1, 2, 4
 STRAND_ORPHANS = 1
 PROBE_TILE, PROBE_MAX_WINDOWS = 4096, 1024      # ZK_PROBE_TILE, ZK_PROBE_MAX_WINDOWS
+TALLY_TILE = 2048                               # ZK_TALLY_TILE
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -141,6 +142,10 @@ SIGNATURES = {
     "zk_bait_table_build": (_i, [_vp, _vp, _u64, _i, C.POINTER(_vp)]),
     "zk_bait_table_info": (_i, [_vp, _pu64, _pu64, _pu64]),
     "zk_bait_table_free": (None, [_vp]),
+    "zk_bait_table_arrays": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "zk_bait_table_from_arrays": (_i, [_vp, _i, _vp, _u64, _vp, _vp, _u64, _u64, C.POINTER(_vp)]),
+    "zk_bait_record_sizes": (_i, [_vp, _vp, _vp]),
+    "zk_bait_tally": (_i, [_vp, _vp, _vp, _u64, _vp]),
     "zk_line_ends": (_i, [_vp, _vp, _u64, _vp, _u64, _pu64]),
     "zk_capture_hits": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _pu64]),
     "zk_capture_gather": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _u64, _pu64, _pu64]),
@@ -242,11 +247,19 @@ class BaitTable:
     """zk_bait_table: sorted distinct K-mers of both strands of a set of sequences -> the ascending indices of the sequences
     that hold each one (device memory of its own, freed with the object)."""
 
-    def __init__(self, ctx, h):
-        self.ctx, self.h = ctx, h
+    def __init__(self, ctx, h, K=None):
+        self.ctx, self.h, self.K = ctx, h, K
         nk, ni, nr = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         ctx._check(ctx.lib.zk_bait_table_info(h, C.byref(nk), C.byref(ni), C.byref(nr)))
         self.n_keys, self.n_ids, self.n_records = nk.value, ni.value, nr.value
+
+    def arrays(self):
+        """(keys u64[n_keys], offs u32[n_keys + 1], ids u32[n_ids]) as borrowed DeviceArrays that keep the table alive"""
+        k, o, i = _vp(), _vp(), _vp()
+        self.ctx._check(self.ctx.lib.zk_bait_table_arrays(self.h, C.byref(k), C.byref(o), C.byref(i)))
+        return (DeviceArray.borrow(self.ctx, k.value, np.uint64, self.n_keys, keep=self),
+                DeviceArray.borrow(self.ctx, o.value, np.uint32, self.n_keys + 1, keep=self),
+                DeviceArray.borrow(self.ctx, i.value, np.uint32, self.n_ids, keep=self))
 
     def free(self):
         if self.h and self.ctx.h:
@@ -371,7 +384,7 @@ class Context:
     PROF_TAGS = {"hist_stream": 1, "hist_array": 2, "pass_stream": 3, "pass_keys": 4, "pass_pairs": 5, "rle": 6,
                  "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
-                 "probe_scan": 21}
+                 "probe_scan": 21, "bait_tally": 22}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -755,7 +768,28 @@ class Context:
         """BaitTable of a base stream of sequences, each followed by one '\\n' (a uint8 DeviceArray)."""
         h = _vp()
         self._check(self.lib.zk_bait_table_build(self.h, stream.ptr, stream.n, int(K), C.byref(h)))
-        return BaitTable(self, h.value)
+        return BaitTable(self, h.value, int(K))
+
+    # ---- complete alleles of a k-mer index (csrc/allele_tally.hip) ---------------------------------------------
+    def bait_table_from_arrays(self, K, keys, offs, ids, n_records):
+        """BaitTable from device arrays (u64 keys, u32 offs[len(keys) + 1], u32 ids), checked on the device and copied"""
+        assert keys.dtype.itemsize == 8 and offs.dtype.itemsize == 4 and ids.dtype.itemsize == 4 and offs.n == keys.n + 1
+        h = _vp()
+        self._check(self.lib.zk_bait_table_from_arrays(self.h, int(K), keys.ptr, keys.n, offs.ptr, ids.ptr, ids.n, int(n_records), C.byref(h)))
+        return BaitTable(self, h.value, int(K))
+
+    def bait_record_sizes(self, table):
+        """the number of keys that list each record -> u32 DeviceArray [n_records]"""
+        out = self.empty(table.n_records, np.uint32)
+        self._check(self.lib.zk_bait_record_sizes(self.h, table.h, out.ptr))
+        return out
+
+    def bait_tally(self, table, kmers, out=None):
+        """per record, the number of the ascending k-mers that are keys listing it -> u32 DeviceArray [n_records]"""
+        out = out if out is not None else self.empty(table.n_records, np.uint32)
+        assert out.n >= table.n_records and out.dtype.itemsize == 4
+        self._check(self.lib.zk_bait_tally(self.h, table.h, kmers.ptr, kmers.n, out.ptr))
+        return out
 
     def line_ends(self, text, out=None):
         """positions of the '\\n' bytes of a device text -> u64 DeviceArray view (out: a buffer to reuse; grown when too small)"""
