@@ -286,6 +286,41 @@ typedef struct { uint64_t value; int32_t J; int32_t reserved; } zk_probe_window;
 int zk_probe_scan(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, int K, const zk_probe_window* windows, uint32_t n_windows,
                   uint64_t* tallies);
 
+/* ---- k-mer spectra per contig and per file, `zot disass` (commands/disass.py) --------------------------------------------
+ * The reference counts, per FASTA record, the k-mers of basics.kmersList(K, seq, both) that pass basics.sub(seed, p, .) in a dict
+ * (disass.py:91-94) and summarises the dict's values; a second dict sums the records' dicts per file (disass.py:98-100).
+ * Key form: with both strands a window's key is c = min(x, rc x).  Every window emits x and rc x, so a run of n windows of c in
+ * a record stands for the dict entries
+ *     c a palindrome (c == rc c):   one entry of count 2n            if sub(c)
+ *     otherwise:                    [sub(c)] + [sub(rc c)] entries of count n
+ * With one strand (both == 0) the key is x and the run is [sub(x)] entries of count n.  sub is zk_subsample's comparison.
+ *
+ * zk_contig_spectra: d_stream holds the records' bases, each record followed by one '\n' (as zk_bait_table_build takes them; a
+ * non-empty stream ends with '\n'); windows restart after any byte outside AaCcGgTtUu.  Output:
+ *   d_words / d_freq   every record's histogram in one array: the distinct words record << 32 | count, ascending, each with the
+ *                      number of dict entries of that record and count (bins of frequency 0 are dropped; a record without
+ *                      entries has no word);
+ *   d_keys / d_counts  the batch's counted key list: ascending distinct keys with the number of windows of each, BEFORE the
+ *                      rule above (lists of several batches are union-summed, then zk_count_spectrum applies the rule once);
+ *   stats              n_records = '\n' bytes, n_windows, n_keys, n_bins.
+ * ZK_ENOSPC with the stats filled in (the sizes needed) if n_bins exceeds cap_bins or n_keys exceeds cap_keys; the array that
+ * fits is still written.  1 <= K <= 32 and p finite, else ZK_EINVAL before any launch; a batch of 2^31 windows or more, or of
+ * 2^32 records or more, is ZK_ERANGE.  All integer work: the same call returns the same bits.  ZK_CONTIG_TILE = the entries a
+ * workgroup takes per step in the kernels that cut the sorted (key, record) array into runs (tests place their sizes around
+ * it). */
+#define ZK_CONTIG_TILE 4096
+typedef struct { uint64_t n_records, n_windows, n_keys, n_bins; } zk_contig_stats;
+int zk_contig_spectra(zk_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, int K, int both, uint64_t seed, double p,
+                      uint64_t* d_words, uint64_t* d_freq, uint64_t cap_bins, uint64_t* d_keys, uint32_t* d_counts, uint64_t cap_keys,
+                      zk_contig_stats* stats);
+
+/* The histogram of a counted key list under the same rule: d_keys ascending distinct keys (canonical when both != 0), d_counts
+ * their window counts (count_bits 32 or 64) -> the ascending (count value, number of dict entries) bins in HOST arrays of
+ * cap_bins entries, with zk_hist's convention: ZK_ENOSPC with *n_bins = the number of bins (the first cap_bins are written).
+ * A palindrome's doubled count must fit 64 bits (ZK_EOVERFLOW).  K and p as above. */
+int zk_count_spectrum(zk_ctx* ctx, const uint64_t* d_keys, const void* d_counts, int count_bits, uint64_t n, int K, int both,
+                      uint64_t seed, double p, uint64_t* vals, uint64_t* freq, uint64_t cap_bins, uint64_t* n_bins);
+
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 
 /* misc.radix_sort(key_bits, xs) (library/misc.py:400-424): ascending, in place. */

@@ -227,4 +227,10 @@ __device__ __forceinline__ u64 murmer(u64 x, u64 s) {
     return h;
 }
 
+// basics.sub(seed, p, x) (zotmer/library/basics.py:252-259): float(murmer(x, seed)) / float(2**61 - 1) < p, in doubles as the reference
+__device__ __forceinline__ bool sub_keep(u64 x, u64 seed, double p) {
+    const double u = (double)murmer(x, seed) / (double)0x1FFFFFFFFFFFFFFFull;
+    return u < p;
+}
+
 }  // namespace zk

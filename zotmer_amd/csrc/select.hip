@@ -616,8 +616,7 @@ struct SubsampleOp {     // K2: float(murmer(x, seed)) / float(2**61 - 1) < p, i
     struct R { u64 k; };
     __device__ bool load(u64 idx, R& r) const {
         r.k = keys[idx];
-        const double u = (double)murmer(r.k, seed) / (double)0x1FFFFFFFFFFFFFFFull;
-        return u < p;
+        return sub_keep(r.k, seed, p);
     }
     __device__ void store(u64 pos, const R& r) const { out[pos] = r.k; }
 };
@@ -629,8 +628,7 @@ struct SubPairOp {       // K2 applied to an already counted set, in place (load
     struct R { u64 k; u32 c; };
     __device__ bool load(u64 idx, R& r) const {
         r.k = keys[idx]; r.c = cnts[idx];
-        const double u = (double)murmer(r.k, seed) / (double)0x1FFFFFFFFFFFFFFFull;
-        return u < p;
+        return sub_keep(r.k, seed, p);
     }
     __device__ void store(u64 pos, const R& r) const { keys[pos] = r.k; cnts[pos] = r.c; }
 };

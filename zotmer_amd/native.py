@@ -24,6 +24,7 @@ KMERIZE_CANONICAL, KMERIZE_BOTH, KMERIZE_SUBSAMPLE, KMERIZE_CANONICAL_ONLY = 0, 
 STRAND_ORPHANS = 1
 PROBE_TILE, PROBE_MAX_WINDOWS = 4096, 1024      # ZK_PROBE_TILE, ZK_PROBE_MAX_WINDOWS
 TALLY_TILE = 2048                               # ZK_TALLY_TILE
+CONTIG_TILE = 4096                              # ZK_CONTIG_TILE
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -45,6 +46,11 @@ class Spectrum(C.Structure):
 class StrandStats(C.Structure):
     """zk_strand_stats: what zk_strand_pairs found (include/zotk.h)"""
     _fields_ = [("n_pairs", C.c_uint64), ("n_orphans", C.c_uint64), ("n_palindromes", C.c_uint64)]
+
+
+class ContigStats(C.Structure):
+    """zk_contig_stats: what zk_contig_spectra saw, and the sizes its outputs need (include/zotk.h)"""
+    _fields_ = [("n_records", C.c_uint64), ("n_windows", C.c_uint64), ("n_keys", C.c_uint64), ("n_bins", C.c_uint64)]
 
 
 class ProbeWindow(C.Structure):
@@ -153,6 +159,8 @@ SIGNATURES = {
     "zk_strand_pairs": (_i, [_vp, _vp, _vp, _i, _u64, _i, _u64, _i, _vp, _vp, _u64, C.POINTER(StrandStats)]),
     "zk_format_pairs": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _pu64]),
     "zk_probe_scan": (_i, [_vp, _vp, _u64, _i, C.POINTER(ProbeWindow), _u32, _pu64]),
+    "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
+    "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
 
 _lib = None
@@ -880,6 +888,49 @@ class Context:
             self._check(self.lib.zk_probe_scan(self.h, kmers.ptr, kmers.n, int(K), arr, len(part), t.ctypes.data_as(_pu64)))
             out[lo:lo + len(part)] = t.reshape(-1, 3)
         return out
+
+    # ---- k-mer spectra per contig (csrc/contig_spectra.hip) ---------------------------------------------------
+    def contig_spectra(self, stream, K, both=True, seed=17, p=1.0, cap_bins=None, cap_keys=None, out=None):
+        """a base stream of records, each followed by '\\n' -> (words u64 view: record << 32 | count, ascending; freq u64 view;
+        keys u64 view: the counted key list; counts u32 view; ContigStats).  Capacities that prove too small are grown once.
+        out: (words, freq, keys, counts) arrays to write into first (their lengths are the capacities)."""
+        cap_bins = stream.n // 4 + 1024 if cap_bins is None else int(cap_bins)      # a guess; a record has at least one window per bin
+        cap_keys = stream.n if cap_keys is None else int(cap_keys)                   # a key has at least one window, a window one byte
+        st = ContigStats()
+        if out is not None:
+            cap_bins, cap_keys = min(out[0].n, out[1].n), min(out[2].n, out[3].n)
+        for _ in range(2):
+            if out is not None:
+                words, freq, keys, counts = out
+                out = None
+            else:
+                words, freq = self.empty(cap_bins, np.uint64), self.empty(cap_bins, np.uint64)
+                keys, counts = self.empty(cap_keys, np.uint64), self.empty(cap_keys, np.uint32)
+            rc = self.lib.zk_contig_spectra(self.h, stream.ptr, stream.n, int(K), int(bool(both)), int(seed), float(p), words.ptr, freq.ptr,
+                                            cap_bins, keys.ptr, counts.ptr, cap_keys, C.byref(st))
+            if rc != ZK_ENOSPC:
+                break
+            cap_bins, cap_keys = max(cap_bins, st.n_bins), max(cap_keys, st.n_keys)
+        self._check(rc)
+        return words.view(st.n_bins), freq.view(st.n_bins), keys.view(st.n_keys), counts.view(st.n_keys), st
+
+    def count_spectrum(self, keys, counts, K, both=True, seed=17, p=1.0):
+        """a counted key list (ascending distinct keys, u32 | u64 window counts) -> [(count, frequency), ...] ascending: the
+        histogram of the dict the reference would hold (zk_count_spectrum)"""
+        assert counts.n == keys.n
+        bits = counts.dtype.itemsize * 8
+        cap = 1 << 16
+        for _ in range(2):            # ZK_ENOSPC = more bins than cap; n then holds how many there are
+            vals = np.empty(cap, dtype=np.uint64)
+            freq = np.empty(cap, dtype=np.uint64)
+            n = C.c_uint64(0)
+            rc = self.lib.zk_count_spectrum(self.h, keys.ptr, counts.ptr, bits, keys.n, int(K), int(bool(both)), int(seed), float(p),
+                                            vals.ctypes.data_as(_pu64), freq.ctypes.data_as(_pu64), cap, C.byref(n))
+            if rc != ZK_ENOSPC or n.value <= cap:
+                break
+            cap = n.value
+        self._check(rc)
+        return [(int(v), int(f)) for v, f in zip(vals[:n.value], freq[:n.value])]
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
