@@ -142,6 +142,7 @@ int zk_tune(zk_ctx* ctx, int what, int value);
                                    pair + the text), one record each */
 #define ZK_PROF_PROBE_SCAN 21   /* zk_probe_scan: the one pass over the set (8 B read per entry, whatever the number of windows) */
 #define ZK_PROF_BAIT_TALLY 22   /* zk_bait_tally: the one pass over the set (8 B read per entry; the adds depend on the hits) */
+#define ZK_PROF_VARS_SCAN 23    /* zk_vars_scan: the one pass over both lists (8 + count bytes read per entry) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -320,6 +321,44 @@ int zk_contig_spectra(zk_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, in
  * A palindrome's doubled count must fit 64 bits (ZK_EOVERFLOW).  K and p as above. */
 int zk_count_spectrum(zk_ctx* ctx, const uint64_t* d_keys, const void* d_counts, int count_bits, uint64_t n, int K, int both,
                       uint64_t seed, double p, uint64_t* vals, uint64_t* freq, uint64_t cap_bins, uint64_t* n_bins);
+
+/* ---- bases enriched over a reference k-mer set, `zot vars -r` (commands/vars.py:85-119) -----------------------------------
+ * A group is the run of entries of a list that share x >> 2 (the context: the first K - 1 bases), at most 4, one per next base
+ * x & 3.  For every sample group whose context the reference has, the reference takes, per base j, p = gx[j] / gt (gx = the
+ * reference group's counts, gt their sum) and v = logBinGe(p, st, sx[j]) (sx = the sample group's counts, st their sum; v = 0
+ * unless 0 < p < 1), and prints the group when some v < -10.  logBinGe's first term is
+ *     F(p, n, k) = logChoose(n, k) + log(p) k + log1p(-p) (n - k)        (library/stats.py:214-222)
+ * and v >= F; for k <= n p the tail is at least 1/2.
+ *
+ * zk_vars_scan reads both lists once and returns, in ascending context order, one ROW for every sample group whose context is
+ * in the reference, whose reference group has at least 2 entries and which has a CANDIDATE base j:
+ *     0 < gx[j] < gt   and   sx[j] gt > st gx[j]  (exact, 128-bit products)   and   0 < p < 1 as a double   and
+ *     F_dev < threshold + G
+ * F_dev is F in double precision with the reference's logFac (the 25-entry table, n log n - n + log(n (1 + 4n (1 + 2n))) / 6 +
+ * log(pi) / 2 from 25 up) in the reference's order of operations, and G = 2^-47 * S bounds |F_dev - F| of any conforming libm,
+ * where S = k |log p| + (n - k) |log1p(-p)|, plus A(n) + A(n - k) + A(k) when 0 < k < n, A(m) = 64 below 25 and
+ * m log m + m + 64 from 25 up.  Every group the reference would print at `threshold` is a row; the host
+ * evaluates logBinGe on the rows only.
+ *   d_ctx          the rows' contexts (x >> 2), ascending;
+ *   d_row_counts   8 words per row: sx[0..3], gx[0..3] (0 where a base is absent);
+ *   stats          n_groups = sample groups; n_missing = those whose context is not in the reference, first_missing = the
+ *                  smallest such context (0 when there is none); n_mixed = joined groups whose reference group has >= 2
+ *                  entries; n_rows.
+ * Both lists: strictly ascending keys below 4^K (a precondition, not checked), counts of 32 or 64 bits (per list).  Either list
+ * may be empty.  ZK_ENOSPC when n_rows exceeds cap_rows: nothing is written, the stats are complete and zk_last_error names the
+ * size.  ZK_EOVERFLOW when the counts of a sample group, or of a reference group that a sample group joins, do not add up in 64
+ * bits.  ZK_EINVAL before any launch for K outside 1..32, count bits other than 32 / 64 or a threshold that is not finite.
+ *
+ * How the lists are cut (tests place groups on the borders): the merged sequence of both lists, the reference entry first where
+ * the keys are equal, is cut every ZK_VARS_TILE elements; tile t takes the reference entries [a_t, a_t+1) and the sample entries
+ * [b_t, b_t+1) with a_t + b_t = t * ZK_VARS_TILE, a_t = the reference entries among the first t * ZK_VARS_TILE merged elements.
+ * A tile sees 4 reference entries before and 3 after its slice, 1 sample entry before and 3 after; a sample group belongs to the
+ * tile that holds its first entry. */
+#define ZK_VARS_TILE 4096
+typedef struct { uint64_t n_groups, n_missing, first_missing, n_mixed, n_rows; } zk_vars_stats;
+int zk_vars_scan(zk_ctx* ctx, const uint64_t* d_ref_keys, const void* d_ref_counts, int ref_count_bits, uint64_t n_ref,
+                 const uint64_t* d_sam_keys, const void* d_sam_counts, int sam_count_bits, uint64_t n_sam, int K, double threshold,
+                 uint64_t* d_ctx, uint64_t* d_row_counts, uint64_t cap_rows, zk_vars_stats* stats);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

@@ -25,6 +25,7 @@ STRAND_ORPHANS = 1
 PROBE_TILE, PROBE_MAX_WINDOWS = 4096, 1024      # ZK_PROBE_TILE, ZK_PROBE_MAX_WINDOWS
 TALLY_TILE = 2048                               # ZK_TALLY_TILE
 CONTIG_TILE = 4096                              # ZK_CONTIG_TILE
+VARS_TILE = 4096                                # ZK_VARS_TILE
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -51,6 +52,12 @@ class StrandStats(C.Structure):
 class ContigStats(C.Structure):
     """zk_contig_stats: what zk_contig_spectra saw, and the sizes its outputs need (include/zotk.h)"""
     _fields_ = [("n_records", C.c_uint64), ("n_windows", C.c_uint64), ("n_keys", C.c_uint64), ("n_bins", C.c_uint64)]
+
+
+class VarsStats(C.Structure):
+    """zk_vars_stats: what zk_vars_scan saw, and the number of rows its outputs need (include/zotk.h)"""
+    _fields_ = [("n_groups", C.c_uint64), ("n_missing", C.c_uint64), ("first_missing", C.c_uint64), ("n_mixed", C.c_uint64),
+                ("n_rows", C.c_uint64)]
 
 
 class ProbeWindow(C.Structure):
@@ -159,6 +166,7 @@ SIGNATURES = {
     "zk_strand_pairs": (_i, [_vp, _vp, _vp, _i, _u64, _i, _u64, _i, _vp, _vp, _u64, C.POINTER(StrandStats)]),
     "zk_format_pairs": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _pu64]),
     "zk_probe_scan": (_i, [_vp, _vp, _u64, _i, C.POINTER(ProbeWindow), _u32, _pu64]),
+    "zk_vars_scan": (_i, [_vp, _vp, _vp, _i, _u64, _vp, _vp, _i, _u64, _i, _d, _vp, _vp, _u64, C.POINTER(VarsStats)]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
     "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
@@ -392,7 +400,7 @@ class Context:
     PROF_TAGS = {"hist_stream": 1, "hist_array": 2, "pass_stream": 3, "pass_keys": 4, "pass_pairs": 5, "rle": 6,
                  "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
-                 "probe_scan": 21, "bait_tally": 22}
+                 "probe_scan": 21, "bait_tally": 22, "vars_scan": 23}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -931,6 +939,25 @@ class Context:
             cap = n.value
         self._check(rc)
         return [(int(v), int(f)) for v, f in zip(vals[:n.value], freq[:n.value])]
+
+    # ---- bases enriched over a reference set (csrc/vars_scan.hip) ---------------------------------------------
+    def vars_scan(self, ref_keys, ref_counts, sam_keys, sam_counts, K, threshold=-10.0, cap_rows=None):
+        """two counted key lists (ascending distinct keys, u32 | u64 counts) -> (contexts u64 view, ascending; row counts u64
+        view, 8 per row: sx[0..3], gx[0..3]; VarsStats): the sample groups that can have a base with logBinGe below threshold
+        (zk_vars_scan).  A capacity that proves too small is grown once."""
+        assert ref_counts.n == ref_keys.n and sam_counts.n == sam_keys.n
+        cap = 1024 if cap_rows is None else int(cap_rows)
+        st = VarsStats()
+        for _ in range(2):
+            ctxs, rows = self.empty(cap, np.uint64), self.empty(8 * cap, np.uint64)
+            rc = self.lib.zk_vars_scan(self.h, ref_keys.ptr, ref_counts.ptr, ref_counts.dtype.itemsize * 8, ref_keys.n, sam_keys.ptr,
+                                       sam_counts.ptr, sam_counts.dtype.itemsize * 8, sam_keys.n, int(K), float(threshold), ctxs.ptr,
+                                       rows.ptr, cap, C.byref(st))
+            if rc != ZK_ENOSPC or st.n_rows <= cap:
+                break
+            cap = st.n_rows
+        self._check(rc)
+        return ctxs.view(st.n_rows), rows.view(8 * st.n_rows), st
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
