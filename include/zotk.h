@@ -143,6 +143,9 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_PROBE_SCAN 21   /* zk_probe_scan: the one pass over the set (8 B read per entry, whatever the number of windows) */
 #define ZK_PROF_BAIT_TALLY 22   /* zk_bait_tally: the one pass over the set (8 B read per entry; the adds depend on the hits) */
 #define ZK_PROF_VARS_SCAN 23    /* zk_vars_scan: the one pass over both lists (8 + count bytes read per entry) */
+#define ZK_PROF_LINKS 24        /* zk_debruijn_links: the successor kernel (8 B read, 4 written per k-mer; the check and the directory are not in it) */
+#define ZK_PROF_LINKS_RC 25     /* zk_debruijn_links: the reverse-complement ranks, a launch of their own (8 B read, 4 written per k-mer) */
+#define ZK_PROF_CONTIG_RENDER 26 /* zk_contig_render: the length pass (4 B per node, 16 per contig) and the write pass (12 B read per node + the text) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -359,6 +362,43 @@ typedef struct { uint64_t n_groups, n_missing, first_missing, n_mixed, n_rows; }
 int zk_vars_scan(zk_ctx* ctx, const uint64_t* d_ref_keys, const void* d_ref_counts, int ref_count_bits, uint64_t n_ref,
                  const uint64_t* d_sam_keys, const void* d_sam_counts, int sam_count_bits, uint64_t n_sam, int K, double threshold,
                  uint64_t* d_ctx, uint64_t* d_row_counts, uint64_t cap_rows, zk_vars_stats* stats);
+
+/* ---- zot contigs (commands/contigs.py): the non-branching paths of a k-mer set's de Bruijn graph ----------------------------
+ *
+ * The reference walks the ascending k-mer array S (n entries, m = 4^K - 1) from every index not yet seen: from x it goes to the
+ * only entry of S in [y0, y0 + 3], y0 = (x << 2) & m, while there is exactly one and it is not seen, and marks, for every node
+ * after the first, the index rank(rc(K, x)) = the number of entries below the reverse complement as seen too.  The two searches
+ * per k-mer are zk_debruijn_links (device), the ordered walk is zk_contig_walk (host: it depends on its order, DESIGN.md section
+ * 6i), the text is zk_contig_render (device).
+ *
+ * zk_debruijn_links:
+ *   d_next[i] = the index of the only entry in [y0, y0 | 3] when there is exactly one, else ZK_NO_LINK (none, or 2 to 4);
+ *   d_rc[i]   = the number of entries < rc(K, d_kmers[i]): 0 .. n (n only when the set is not closed under rc).
+ * d_kmers strictly ascending and below 4^K, 1 <= K <= 32, n < 2^32 - 1: anything else is ZK_EINVAL (checked on the device before
+ * anything is written: the outputs stay as they were).  n = 0 writes nothing.  The same call returns the same bits.
+ * How the set is cut (tests place sizes around it): workgroup t takes the entries [t * ZK_LINKS_TILE, (t + 1) * ZK_LINKS_TILE).
+ * Within one first base y0 ascends with x, so the successors of a tile lie in at most 4 ascending windows of S, which are staged
+ * in LDS; a tile whose windows hold more than 5 * ZK_LINKS_TILE entries searches them in place instead. */
+#define ZK_NO_LINK 0xFFFFFFFFu
+#define ZK_LINKS_TILE 1024
+int zk_debruijn_links(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, int K, uint32_t* d_next, uint32_t* d_rc);
+/* The walk, on HOST arrays (no zk_ctx, no device call).  For i = 0 .. n - 1 ascending, unless seen[i]: path = [i], seen[i] = 1;
+ * while j = next[cur] is a link and j is not seen: append j, seen[j] = 1, seen[rc[j]] = 1 (dropped when rc[j] == n: the set is not
+ * closed under rc), cur = j.  A path is kept iff len + K - 1 >= min_len; the marks of a path that is not kept stay.  Kept paths
+ * are appended to nodes in start order: contig c is nodes[offs[c], offs[c + 1]), its start index nodes[offs[c]]; offs takes
+ * cap_contigs + 1 entries.  ZK_ENOSPC with both counts filled in (the sizes needed) when cap_nodes or cap_contigs is too small;
+ * what the arrays hold is not specified then.  ZK_EINVAL for a next[i] that is neither below
+ * n nor ZK_NO_LINK, an rc[i] above n (found as the walk reads them: nothing is indexed out of range), K outside 1..32,
+ * n >= 2^32 - 1 or a null array. */
+int zk_contig_walk(const uint32_t* next, const uint32_t* rc, uint64_t n, int K, uint64_t min_len, uint32_t* nodes, uint64_t cap_nodes,
+                   uint64_t* offs, uint64_t cap_contigs, uint64_t* n_nodes, uint64_t* n_contigs);
+/* ">contig_<start>\n<the K bases of the first node><the last base of every later node>\n" for every contig, in order, letters
+ * ACGT, into d_out.  d_nodes (u32[n_nodes], every entry < n) and d_offs (u64[n_contigs + 1], ascending from 0 to n_nodes, no empty
+ * contig) are device copies of what zk_contig_walk left; both are checked on the device (ZK_EINVAL, nothing written).
+ * ZK_ENOSPC with *n_bytes = the size needed if it exceeds cap.  n_contigs = 0 writes nothing.  The body is written one byte per
+ * thread: the work of a thread does not grow with a contig's length. */
+int zk_contig_render(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, int K, const uint32_t* d_nodes, uint64_t n_nodes,
+                     const uint64_t* d_offs, uint64_t n_contigs, uint8_t* d_out, uint64_t cap, uint64_t* n_bytes);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

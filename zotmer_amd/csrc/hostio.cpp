@@ -9,6 +9,9 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <new>
+#include <vector>
+
 #include "../../include/zotk.h"
 
 namespace {
@@ -174,6 +177,55 @@ int zk_parse_fasta(const char* buf, uint64_t len, int final, uint64_t state[4], 
     state[0] = in_rec; state[1] = records;
     *out_len = o;
     *consumed = pos;
+    return ZK_OK;
+}
+
+// The walk of `zot contigs` (zotmer/commands/contigs.py:47-74) on the links of zk_debruijn_links: see include/zotk.h.  The
+// reference's test `xp == 1` compares a list with an int and never holds, so every unseen index starts a path.
+int zk_contig_walk(const uint32_t* next, const uint32_t* rc, uint64_t n, int K, uint64_t min_len, uint32_t* nodes, uint64_t cap_nodes,
+                   uint64_t* offs, uint64_t cap_contigs, uint64_t* n_nodes, uint64_t* n_contigs) {
+    if (!n_nodes || !n_contigs) return ZK_EINVAL;
+    *n_nodes = 0;
+    *n_contigs = 0;
+    if (K < 1 || K > 32 || n >= 0xFFFFFFFFull || !offs || (n && (!next || !rc)) || (cap_nodes && !nodes)) return ZK_EINVAL;
+    std::vector<uint64_t> seen;
+    try {
+        seen.assign((size_t)((n + 63) / 64), 0);
+    } catch (const std::bad_alloc&) {
+        return ZK_ENOMEM;
+    }
+    uint64_t nn = 0, nc = 0;          // counted past the capacities, written only below them
+    for (uint64_t i = 0; i < n; i++) {
+        if ((seen[i >> 6] >> (i & 63)) & 1) continue;
+        const uint64_t start = nn;
+        seen[i >> 6] |= 1ull << (i & 63);
+        if (nn < cap_nodes) nodes[nn] = (uint32_t)i;
+        nn++;
+        uint64_t cur = i;
+        for (;;) {
+            const uint32_t j = next[cur];
+            if (j == ZK_NO_LINK) break;
+            if (j >= n) return ZK_EINVAL;
+            if ((seen[j >> 6] >> (j & 63)) & 1) break;
+            seen[j >> 6] |= 1ull << (j & 63);
+            if (nn < cap_nodes) nodes[nn] = j;
+            nn++;
+            const uint32_t r = rc[j];
+            if (r > n) return ZK_EINVAL;
+            if (r < n) seen[r >> 6] |= 1ull << (r & 63);          // r == n: rc(x) is above every k-mer of a set that is not closed
+            cur = j;
+        }
+        if ((nn - start) + (uint64_t)K - 1 >= min_len) {
+            if (nc < cap_contigs) offs[nc] = start;
+            nc++;
+        } else {
+            nn = start;          // too short: the nodes go, the marks stay
+        }
+    }
+    *n_nodes = nn;
+    *n_contigs = nc;
+    if (nn > cap_nodes || nc > cap_contigs) return ZK_ENOSPC;
+    offs[nc] = nn;
     return ZK_OK;
 }
 

@@ -26,6 +26,8 @@ PROBE_TILE, PROBE_MAX_WINDOWS = 4096, 1024      # ZK_PROBE_TILE, ZK_PROBE_MAX_WI
 TALLY_TILE = 2048                               # ZK_TALLY_TILE
 CONTIG_TILE = 4096                              # ZK_CONTIG_TILE
 VARS_TILE = 4096                                # ZK_VARS_TILE
+LINKS_TILE = 1024                               # ZK_LINKS_TILE
+NO_LINK = 0xFFFFFFFF                            # ZK_NO_LINK
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -167,6 +169,9 @@ SIGNATURES = {
     "zk_format_pairs": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _pu64]),
     "zk_probe_scan": (_i, [_vp, _vp, _u64, _i, C.POINTER(ProbeWindow), _u32, _pu64]),
     "zk_vars_scan": (_i, [_vp, _vp, _vp, _i, _u64, _vp, _vp, _i, _u64, _i, _d, _vp, _vp, _u64, C.POINTER(VarsStats)]),
+    "zk_debruijn_links": (_i, [_vp, _vp, _u64, _i, _vp, _vp]),
+    "zk_contig_walk": (_i, [_vp, _vp, _u64, _i, _u64, _vp, _u64, _vp, _u64, _pu64, _pu64]),
+    "zk_contig_render": (_i, [_vp, _vp, _u64, _i, _vp, _u64, _vp, _u64, _vp, _u64, _pu64]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
     "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
@@ -188,6 +193,28 @@ def load():
             fn.argtypes = args
         _lib = lib
     return _lib
+
+
+def contig_walk(next_, rc, K, min_len):
+    """zk_contig_walk on host arrays (u32 next / rc of zk_debruijn_links) -> (nodes u32, offs u64[n_contigs + 1]): the paths
+    `zot contigs` keeps, in start order.  Host only: no context, no device.  Capacities that prove too small are grown once."""
+    lib = load()
+    next_ = np.ascontiguousarray(next_, dtype=np.uint32)
+    rc = np.ascontiguousarray(rc, dtype=np.uint32)
+    n = len(next_)
+    assert len(rc) == n
+    cap_nodes, cap_contigs = n, min(n, 1 << 16)
+    nn, nc = C.c_uint64(0), C.c_uint64(0)
+    for _ in range(2):
+        nodes, offs = np.empty(max(cap_nodes, 1), dtype=np.uint32), np.empty(cap_contigs + 1, dtype=np.uint64)
+        r = lib.zk_contig_walk(next_.ctypes.data, rc.ctypes.data, n, int(K), int(min_len), nodes.ctypes.data, cap_nodes, offs.ctypes.data,
+                               cap_contigs, C.byref(nn), C.byref(nc))
+        if r != ZK_ENOSPC:
+            break
+        cap_nodes, cap_contigs = max(cap_nodes, nn.value), max(cap_contigs, nc.value)
+    if r != ZK_OK:
+        raise ZotkError(r, "zk_contig_walk: the links are damaged (a next that is no index or ZK_NO_LINK, an rc above n) or an argument is bad")
+    return nodes[:nn.value], offs[:nc.value + 1]
 
 
 class DeviceArray:
@@ -400,7 +427,7 @@ class Context:
     PROF_TAGS = {"hist_stream": 1, "hist_array": 2, "pass_stream": 3, "pass_keys": 4, "pass_pairs": 5, "rle": 6,
                  "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
-                 "probe_scan": 21, "bait_tally": 22, "vars_scan": 23}
+                 "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -958,6 +985,31 @@ class Context:
             cap = st.n_rows
         self._check(rc)
         return ctxs.view(st.n_rows), rows.view(8 * st.n_rows), st
+
+    # ---- de Bruijn paths of a k-mer set (csrc/debruijn.hip) ----------------------------------------------------
+    def debruijn_links(self, kmers, K, out=None):
+        """ascending k-mers -> (next u32 DeviceArray: the index of the only successor or NO_LINK; rc u32 DeviceArray: the
+        number of k-mers below the reverse complement).  out: (next, rc) arrays to write into."""
+        nx, rc = out if out is not None else (self.empty(kmers.n, np.uint32), self.empty(kmers.n, np.uint32))
+        assert nx.n >= kmers.n and rc.n >= kmers.n and nx.dtype.itemsize == 4 and rc.dtype.itemsize == 4
+        self._check(self.lib.zk_debruijn_links(self.h, kmers.ptr, kmers.n, int(K), nx.ptr, rc.ptr))
+        return nx, rc
+
+    def contig_render(self, kmers, K, nodes, offs, out=None):
+        """device copies of contig_walk's nodes (u32) and offs (u64) -> the FASTA text as a uint8 DeviceArray view (out: a buffer
+        to reuse; grown when too small)"""
+        assert nodes.dtype.itemsize == 4 and offs.dtype.itemsize == 8 and offs.n >= 1
+        n_contigs = offs.n - 1
+        n = C.c_uint64(0)
+        if out is None:
+            out = self.empty(nodes.n + n_contigs * (int(K) + 19), np.uint8)
+        args = lambda o: (self.h, kmers.ptr, kmers.n, int(K), nodes.ptr, nodes.n, offs.ptr, n_contigs, o.ptr, o.n, C.byref(n))
+        rc = self.lib.zk_contig_render(*args(out))
+        if rc == ZK_ENOSPC:
+            out = self.empty(n.value, np.uint8)
+            rc = self.lib.zk_contig_render(*args(out))
+        self._check(rc)
+        return out.view(n.value)
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
