@@ -21,6 +21,12 @@
  *     byte that is not a base (the host parser keeps the line's '\n'); any byte outside
  *     AaCcGgTtUu ends the windows that touch it, as in basics.kmersList (basics.py:329-339).
  *     Stream pointers must be 16-byte aligned.
+ *   - THE CAPACITY CONVENTION.  An entry that produces a list takes `cap`, the number of entries each of its output arrays
+ *     holds (bytes for text).  ZK_ENOSPC when the result exceeds `cap`: nothing is written at or beyond index `cap` of any
+ *     output array, the count output (*n_out, *n_unique, *n_words ...) = the length needed, and the call may be repeated with
+ *     room on the same context.  What lies below index `cap` is unspecified after a refusal.  A capacity equal to the length
+ *     needed is enough; cap = 0 sizes the output.  The entries say where they differ (no count: zk_kmerize; a capacity that
+ *     is not the result's length: zk_kmerize with ZK_KMERIZE_SUBSAMPLE, zk_capture_hits).  tests/test_gpu_capacity.py pins it.
  *
  * There is no CPU fallback: without a visible MI355X zk_create returns NULL.
  */
@@ -160,12 +166,16 @@ int zk_pack_reads(zk_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_offs, u
 /* basics.kmersList(K, seq, both) over every sequence of the stream (library/basics.py:303-347,
  * called from reads.next, library/reads.py:108-117): k-mers in stream order, x then rc(x) per
  * window when both != 0.  acgt (may be NULL) = histogram of the low base of every emitted k-mer
- * (commands/kmerize.py:492-493).  d_out holds cap values; *n_out = values produced. */
+ * (commands/kmerize.py:492-493).  d_out holds cap values; *n_out = values produced.
+ * ZK_ENOSPC when they exceed cap: nothing is written at or beyond index cap (with both != 0 a window's pair is written whole or
+ * not at all), *n_out = the length needed, and the call may be repeated with room; acgt is complete either way. */
 int zk_encode(zk_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, int K, int both,
               uint64_t* d_out, uint64_t cap, uint64_t* n_out, uint64_t acgt[4]);
 
 /* basics.sub(seed, p, x) as a filter (library/basics.py:252-259; commands/kmerize.py:494-509):
- * keeps x iff float(murmer(x, seed)) / float(2**61 - 1) < p, compared in doubles. */
+ * keeps x iff float(murmer(x, seed)) / float(2**61 - 1) < p, compared in doubles.
+ * ZK_ENOSPC when the kept k-mers exceed cap: nothing is written at or beyond index cap of d_out, *n_out = the length needed,
+ * and the call may be repeated with room. */
 int zk_subsample(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, uint64_t seed, double p,
                  uint64_t* d_out, uint64_t cap, uint64_t* n_out);
 
@@ -188,7 +198,7 @@ int zk_bait_table_info(const zk_bait_table* table, uint64_t* n_keys, uint64_t* n
 void zk_bait_table_free(zk_bait_table* table);
 
 /* the positions of the '\n' bytes of d_text[0, n), ascending, into d_out (cap entries; ZK_ENOSPC with *n_lines = the count if
- * they do not fit).  The line structure file.readFastq walks (file.py:38-52): record r of a text cut at a record boundary is
+ * they do not fit: nothing at all is written then, and the call may be repeated with room).  The line structure file.readFastq walks (file.py:38-52): record r of a text cut at a record boundary is
  * lines 4r .. 4r+3, line i = [d_out[i-1] + 1, d_out[i]). */
 int zk_line_ends(zk_ctx* ctx, const uint8_t* d_text, uint64_t n, uint64_t* d_out, uint64_t cap, uint64_t* n_lines);
 
@@ -198,15 +208,18 @@ int zk_line_ends(zk_ctx* ctx, const uint8_t* d_text, uint64_t n, uint64_t* d_out
  * key of equal value, whatever the two K are.  Paired reads (capture.py -p): d_text2 / d_lines2 are mate 2, the hits are the
  * union over both mates.  veto (may be NULL): a read with any window in it is not captured (the -U of pulldown.py).
  * Output: the distinct (bait, read) pairs as words bait << 32 | read, ascending (each bait's reads contiguous and in input
- * order), in d_pairs.  cap must hold the pairs BEFORE deduplication (at most one per read chunk of 64 windows and bait);
- * ZK_ENOSPC with *n_pairs = that count if it does not. */
+ * order), in d_pairs.  cap must hold the pairs BEFORE deduplication (one per bait and chunk of 64 window starts of a sequence
+ * line that holds one of its k-mers), which d_pairs[0, cap) is the work space of; ZK_ENOSPC with *n_pairs = that count if it does
+ * not: nothing is written at or beyond index cap, and the call may be repeated with room (that count is then enough, though
+ * *n_pairs, the distinct pairs, comes back smaller). */
 int zk_capture_hits(zk_ctx* ctx, const zk_bait_table* baits, const zk_bait_table* veto, int read_K, const uint8_t* d_text1,
                     const uint64_t* d_lines1, const uint8_t* d_text2, const uint64_t* d_lines2, uint64_t n_reads, uint64_t* d_pairs,
                     uint64_t cap, uint64_t* n_pairs);
 
 /* ReadCache.add / flush (capture.py:26-69) for one batch: the records of d_pairs (from zk_capture_hits) as their four lines,
  * each stripped as str.strip() does (file.py:38-52) and followed by '\n', bait by bait, into d_out (cap bytes; ZK_ENOSPC with
- * *n_bytes = the size needed if they do not fit).  spans (host, 2 * (n_baits + 1) words): spans[b] = the first pair of bait b,
+ * *n_bytes = the size needed if they do not fit: no byte of d_out is written then, spans is complete, and the call may be
+ * repeated with room).  spans (host, 2 * (n_baits + 1) words): spans[b] = the first pair of bait b,
  * spans[n_baits + 1 + b] = its first byte in d_out (b = n_baits: the ends).  Paired input: once per mate, with that mate's text. */
 int zk_capture_gather(zk_ctx* ctx, const uint64_t* d_pairs, uint64_t n_pairs, uint32_t n_baits, const uint8_t* d_text,
                       const uint64_t* d_lines, uint64_t n_lines, uint8_t* d_out, uint64_t cap, uint64_t* spans, uint64_t* n_bytes);
@@ -407,11 +420,15 @@ int zk_sort_keys(zk_ctx* ctx, uint64_t* d_keys, uint64_t n, int key_bits);
 /* the same carrying a 32-bit payload (stable) */
 int zk_sort_pairs(zk_ctx* ctx, uint64_t* d_keys, uint32_t* d_vals, uint64_t n, int key_bits);
 /* the run-length half of kmerize.merge (commands/kmerize.py:41-132): distinct values of a sorted
- * array and their multiplicities.  d_uniq may equal d_sorted. */
+ * array and their multiplicities.  d_uniq may equal d_sorted.
+ * ZK_ENOSPC when the distinct values exceed cap: nothing is written at or beyond index cap of d_uniq or d_counts (with d_uniq ==
+ * d_sorted the array still holds its input from cap on), *n_unique = the length needed, and the call may be repeated with room
+ * (in place: on the input again, the entries below cap have been overwritten). */
 int zk_rle(zk_ctx* ctx, const uint64_t* d_sorted, uint64_t n, uint64_t* d_uniq, uint32_t* d_counts,
            uint64_t cap, uint64_t* n_unique);
 /* KmerAccumulator2.flush on an empty table (commands/kmerize.py:412-424): sort (destroys d_keys)
- * then count. */
+ * then count.  ZK_ENOSPC as zk_rle: nothing is written at or beyond index cap of d_uniq or d_counts, *n_unique = the length
+ * needed, and the call may be repeated with room (on the keys again: the sort has destroyed d_keys). */
 int zk_sort_count(zk_ctx* ctx, uint64_t* d_keys, uint64_t n, int key_bits,
                   uint64_t* d_uniq, uint32_t* d_counts, uint64_t cap, uint64_t* n_unique);
 
@@ -433,20 +450,29 @@ typedef struct {
 } zk_kmerize_stats;
 
 /* One in-memory `zot kmerize` (commands/kmerize.py:490-546 with KmerAccumulator2, :370-437) over
- * the base stream: sorted distinct k-mers of BOTH strands and their counts. */
+ * the base stream: sorted distinct k-mers of BOTH strands and their counts.
+ * ZK_ENOSPC when the table exceeds cap: nothing is written at or beyond index cap of d_kmers or d_counts, and the call may be
+ * repeated with room; a capacity equal to the table's length is enough on every plan.  The length needed is NOT returned:
+ * stats->n_unique is 0 and the other fields are unspecified after a refusal (some plans refuse before they have merged the
+ * strands); 2 * n_bytes entries always hold the table, n_bytes the canonical list.  With ZK_KMERIZE_SUBSAMPLE the subsample is
+ * applied to the counted table in the caller's arrays: cap must hold the table BEFORE the subsample, n_unique is its length
+ * after.  With ZK_KMERIZE_CANONICAL_ONLY cap counts the entries of the canonical list. */
 int zk_kmerize(zk_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, int K, int flags, double p, uint64_t seed,
                uint64_t* d_kmers, uint32_t* d_counts, uint64_t cap, zk_kmerize_stats* stats);
 
 /* The second half of zk_kmerize for a counted canonical list (ascending c, counts): sorted distinct k-mers of BOTH strands
  * -- (c, n) and (rc c, n) for every entry, a palindrome (c == rc c) counted n + n, as two emissions per window give
  * (commands/kmerize.py:490; library/reads.py:113-114).  zk_kmerize(flags) == zk_mirror_expand(zk_kmerize(flags |
- * ZK_KMERIZE_CANONICAL_ONLY)). */
+ * ZK_KMERIZE_CANONICAL_ONLY)).
+ * ZK_ENOSPC when the table (2 n entries less the palindromes) exceeds cap: nothing is written at or beyond index cap of d_kmers
+ * or d_counts, *n_out = the length needed, and the call may be repeated with room. */
 int zk_mirror_expand(zk_ctx* ctx, const uint64_t* d_canon_kmers, const uint32_t* d_canon_counts, uint64_t n, int K,
                      uint64_t* d_kmers, uint32_t* d_counts, uint64_t cap, uint64_t* n_out);
 
 /* hist[c] += 1 per distinct k-mer (commands/kmerize.py:543-545; merge.py:88-92), as ascending
  * (value, frequency) pairs in HOST arrays of cap_bins entries.  count_bits is 32 or 64.  ZK_ENOSPC: more than
- * cap_bins bins; *n_bins is then the number of bins (the first cap_bins are written), so one more call sizes it. */
+ * cap_bins bins; *n_bins is then the number of bins (the first cap_bins are written, nothing at or beyond index cap_bins of
+ * vals or freq), so one more call sizes it; the call may be repeated with room. */
 int zk_hist(zk_ctx* ctx, const void* d_counts, int count_bits, uint64_t n,
             uint64_t* vals, uint64_t* freq, uint64_t cap_bins, uint64_t* n_bins);
 
@@ -457,20 +483,27 @@ int zk_widen_counts(zk_ctx* ctx, const uint32_t* d_in, uint64_t* d_out, uint64_t
 
 /* merge.merge (commands/merge.py:26-86) and the merge half of kmerize.merge: two sorted-unique
  * (k-mer, count) lists -> one; equal k-mers add.  count_bits (32 or 64) is the element type of all
- * three count arrays.  acgt_w (may be NULL): acgt_w[x & 3] += count (merge.py:159). */
+ * three count arrays.  acgt_w (may be NULL): acgt_w[x & 3] += count (merge.py:159).
+ * ZK_ENOSPC when the union exceeds cap: nothing is written at or beyond index cap of d_ok or d_oc, *n_out = the length needed
+ * (acgt_w is complete as well), and the call may be repeated with room. */
 int zk_union_sum(zk_ctx* ctx, const uint64_t* d_xk, const void* d_xc, uint64_t nx,
                  const uint64_t* d_yk, const void* d_yc, uint64_t ny,
                  uint64_t* d_ok, void* d_oc, int count_bits, uint64_t cap, uint64_t* n_out, uint64_t acgt_w[4]);
 
 /* mergeNinto (commands/merge.py:127-163; twin commands/kmerize.py:269-304): k sorted-unique lists
  * -> one.  d_keys / d_counts / ns are HOST arrays of k device pointers / sizes; count_bits (32 or 64)
- * is the element type of every count array. */
+ * is the element type of every count array.
+ * ZK_ENOSPC when the union exceeds cap: nothing is written at or beyond index cap of d_ok or d_oc, *n_out = the length needed,
+ * and the call may be repeated with room.  Only the last pass writes the caller's arrays; the passes before it work in the
+ * context's workspace at the sizes they need. */
 int zk_merge_n(zk_ctx* ctx, int k, const uint64_t* const* d_keys, const void* const* d_counts, const uint64_t* ns,
                uint64_t* d_ok, void* d_oc, int count_bits, uint64_t cap, uint64_t* n_out, uint64_t acgt_w[4]);
 
 /* ---- K8/K9: dist ------------------------------------------------------------------------------- */
 
-/* Measure.prep, set mode (commands/dist.py:43-49): y = x >> shift, adjacent duplicates dropped. */
+/* Measure.prep, set mode (commands/dist.py:43-49): y = x >> shift, adjacent duplicates dropped.
+ * ZK_ENOSPC when the result exceeds cap: nothing is written at or beyond index cap of d_out, *n_out = the length needed, and the
+ * call may be repeated with room. */
 int zk_project_dedupe(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, int shift,
                       uint64_t* d_out, uint64_t cap, uint64_t* n_out);
 /* dist.split (library/dist.py:241-265): abc = (|X & Y|, |X \ Y|, |Y \ X|) of two sorted unique arrays. */
@@ -481,7 +514,7 @@ int zk_split(zk_ctx* ctx, const uint64_t* d_x, uint64_t nx, const uint64_t* d_y,
  * count_bits (32 or 64) is the element type of d_counts.  shift == 0 copies the k-mers and widens the counts.  The sums are
  * 64-bit: where the reference's array('I') raises OverflowError above 2^32 - 1 this goes on counting -- the one deliberate
  * difference.  The counts of a set must add up to less than 2^64.  ZK_ENOSPC with *n_out = the number of prefixes if they
- * exceed cap. */
+ * exceed cap: nothing at all is written to d_keys or d_sums then, *total is unspecified, and the call may be repeated with room. */
 int zk_project_sum(zk_ctx* ctx, const uint64_t* d_kmers, const void* d_counts, int count_bits, uint64_t n, int shift,
                    uint64_t* d_keys, uint64_t* d_sums, uint64_t cap, uint64_t* n_out, uint64_t* total);
 
@@ -511,10 +544,14 @@ int zk_lower_bound(zk_ctx* ctx, const uint64_t* d_sorted, uint64_t n, const uint
 /* ---- next-row commands on the same kernels ---------------------------------------- */
 
 /* project.project2 (commands/project.py:29-40): the (k-mer, count) entries of a set whose k-mer is in the
- * sorted reference set; 64-bit counts. */
+ * sorted reference set; 64-bit counts.
+ * ZK_ENOSPC when the entries kept exceed cap: nothing is written at or beyond index cap of d_ok or d_oc, *n_out = the length
+ * needed, and the call may be repeated with room. */
 int zk_project(zk_ctx* ctx, const uint64_t* d_ref, uint64_t n_ref, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n,
                uint64_t* d_ok, uint64_t* d_oc, uint64_t cap, uint64_t* n_out);
-/* sample.sampleD (commands/sample.py:27-34): keep iff float(murmer(x, seed) & (2^40 - 1)) / float(2^40 - 1) < p. */
+/* sample.sampleD (commands/sample.py:27-34): keep iff float(murmer(x, seed) & (2^40 - 1)) / float(2^40 - 1) < p.
+ * ZK_ENOSPC when the entries kept exceed cap: nothing is written at or beyond index cap of d_ok or d_oc, *n_out = the length
+ * needed, and the call may be repeated with room. */
 int zk_sample(zk_ctx* ctx, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint64_t seed, double p,
               uint64_t* d_ok, uint64_t* d_oc, uint64_t cap, uint64_t* n_out);
 
@@ -556,7 +593,9 @@ int zk_allreduce_u64(zk_ctx* ctx, uint64_t* vals, uint64_t n, int op);
 
 /* ---- K10: trim ---------------------------------------------------------------------------------- */
 
-/* trim.trim (commands/trim.py:54-62): keep (x, f) iff f >= lo and (hi == 0 or f <= hi). */
+/* trim.trim (commands/trim.py:54-62): keep (x, f) iff f >= lo and (hi == 0 or f <= hi).
+ * ZK_ENOSPC when the entries kept exceed cap: nothing is written at or beyond index cap of d_ok or d_oc, *n_out = the length
+ * needed, and the call may be repeated with room. */
 int zk_trim(zk_ctx* ctx, const uint64_t* d_kmers, const void* d_counts, int count_bits, uint64_t n,
             uint64_t lo, uint64_t hi, uint64_t* d_ok, void* d_oc, uint64_t cap, uint64_t* n_out);
 
@@ -574,12 +613,16 @@ int zk_codec64_decode(const uint64_t* words, uint64_t nw, int delta, uint64_t* o
 
 /* The same codec on the device (K11 / K12): values and words are DEVICE arrays; streams are byte-exact
  * with the host functions above and with the reference.  encode: d_words needs at most n entries;
+ * ZK_ENOSPC when the words exceed cap: nothing is written at or beyond index cap of d_words, *n_words = the length needed, and
+ * the call may be repeated with room.
  * decode: the exact value count comes back in *n_out, also with ZK_ENOSPC when it exceeds cap (so a first
- * call with cap = 0 sizes the output). */
+ * call with cap = 0 sizes the output): nothing is written at or beyond index cap of d_out -- with delta != 0 the values are
+ * summed in place only once they are known to fit -- and the call may be repeated with room. */
 int zk_codec64_encode_dev(zk_ctx* ctx, const uint64_t* d_vals, uint64_t n, int delta, uint64_t* d_words, uint64_t cap, uint64_t* n_words);
 int zk_codec64_decode_dev(zk_ctx* ctx, const uint64_t* d_words, uint64_t nw, int delta, uint64_t* d_out, uint64_t cap, uint64_t* n_out);
 /* zk_codec64_encode_dev (delta = 0) of 32-bit values: the counts of `zot kmerize` (array('I'), commands/kmerize.py:370-437) go into
- * the 'counts' member (files.writeKmersAndCounts2, library/files.py:209-217) without being widened to 64 bits first; same words. */
+ * the 'counts' member (files.writeKmersAndCounts2, library/files.py:209-217) without being widened to 64 bits first; same words,
+ * same ZK_ENOSPC: nothing at or beyond index cap of d_words, *n_words = the length needed, the call may be repeated with room. */
 int zk_codec64_encode_u32_dev(zk_ctx* ctx, const uint32_t* d_vals, uint64_t n, uint64_t* d_words, uint64_t cap, uint64_t* n_words);
 
 /* files.undelta (library/files.py:100-110) of a PIECE of a delta stream: in-place inclusive prefix sum of the decoded

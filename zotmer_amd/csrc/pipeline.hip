@@ -916,14 +916,17 @@ int merge_many(zk_ctx* c, int k, const u64* const* keys, const void* const* cnts
             }
             uint64_t no = 0;
             const uint64_t mark = c->arena_off;          // this pass's scratch starts here and is dead when it returns
+            int rc;
             if (g == 2) {
-                ZK_TRY(union_sum(c, cur[i].k, cur[i].c, cur[i].n, cur[i + 1].k, cur[i + 1].c, cur[i + 1].n, ok, oc, count_bits, capo, &no,
-                                 last ? acgt_w : nullptr));
+                rc = union_sum(c, cur[i].k, cur[i].c, cur[i].n, cur[i + 1].k, cur[i + 1].c, cur[i + 1].n, ok, oc, count_bits, capo, &no,
+                               last ? acgt_w : nullptr);
             } else {
                 const u64* gk[16]; const void* gc[16]; uint64_t gn[16];
                 for (int j = 0; j < g; j++) { gk[j] = cur[i + j].k; gc[j] = cur[i + j].c; gn[j] = cur[i + j].n; }
-                ZK_TRY(kway_union_sum(c, g, gk, gc, gn, ok, oc, count_bits, capo, &no, last ? acgt_w : nullptr));
+                rc = kway_union_sum(c, g, gk, gc, gn, ok, oc, count_bits, capo, &no, last ? acgt_w : nullptr);
             }
+            if (rc == ZK_ENOSPC && last) *n_out = no;          // the caller's arrays are too short: the length they need
+            if (rc != ZK_OK) return rc;
             c->arena_off = mark;
             nxt[o++] = L{ok, oc, no};
         }
