@@ -20,7 +20,37 @@
  *   - a "base stream" is the concatenation of the sequences of a batch, each followed by one
  *     byte that is not a base (the host parser keeps the line's '\n'); any byte outside
  *     AaCcGgTtUu ends the windows that touch it, as in basics.kmersList (basics.py:329-339).
- *     Stream pointers must be 16-byte aligned.
+ *     Which entries need a stream on a 16-byte boundary is said below.
+ *   - ARRAYS AND THEIR ALIGNMENT.  A d_* array needs only the alignment of its element type: 8 bytes for uint64_t, 4 for
+ *     uint32_t (and for `void*` counts of 32 bits), 1 for bytes.  A sub-range of a larger array -- a view at any element offset
+ *     of a slab, data_ptr() + 8 * off of a torch tensor -- is a valid argument, for inputs and outputs alike, and the arrays of
+ *     one call need not share a phase.  The one exception: the entries marked "16" below want their base stream or text (most
+ *     read it in 16-byte units; zk_fastq_mask writes its output so too) on a 16-byte boundary; given another pointer they
+ *     return ZK_EINVAL before any launch, write nothing, and the context stays usable.
+ *         entry                   stream / text argument            needs     (where the code says so)
+ *         zk_encode               d_stream                          16        select.hip:771
+ *         zk_capture_filter       d_stream                          16        select.hip:849        (d_out: any address)
+ *         zk_kmerize              d_stream                          16        radix_sort.hip:1820   (the first work of every plan)
+ *         zk_stream_checksum      d_stream                          16        capi.hip:379
+ *         zk_fastq_mask           d_text and d_stream               16 both   codec.hip:405
+ *         zk_pack_reads           d_bases, d_stream (output)        any address
+ *         zk_synth_reads          d_stream (output)                 any address
+ *         zk_bait_table_build     d_stream                          any address
+ *         zk_contig_spectra       d_stream                          any address
+ *         zk_line_ends            d_text                            any address
+ *         zk_last_newline         d_text                            any address
+ *         zk_capture_hits         d_text1, d_text2                  any address
+ *         zk_capture_gather       d_text, d_out                     any address
+ *         zk_strand_keys          d_text                            any address
+ *         zk_format_pairs         d_out                             any address
+ *         zk_contig_render        d_out                             any address
+ *         zk_copy                 d_dst, d_src                      any address, any byte count
+ *     An entry writes only the elements [0, result length) of its outputs and never more than [0, cap) -- nothing in front of the
+ *     pointer, nothing behind the result but what the capacity convention below allows (the work space of zk_capture_hits and of
+ *     zk_kmerize with ZK_KMERIZE_SUBSAMPLE is [0, cap)).  An entry does not change an input that is not also an output; the
+ *     exceptions are the ones the entries state: zk_sort_count destroys d_keys, and the in-place forms (zk_sort_keys,
+ *     zk_sort_pairs, zk_undelta, zk_add_u64, zk_rle with d_uniq == d_sorted, zk_can with d_out == d_kmers).
+ *     tests/test_gpu_views.py pins all of this, on views at the last place before a 128-byte line among others.
  *   - THE CAPACITY CONVENTION.  An entry that produces a list takes `cap`, the number of entries each of its output arrays
  *     holds (bytes for text).  ZK_ENOSPC when the result exceeds `cap`: nothing is written at or beyond index `cap` of any
  *     output array, the count output (*n_out, *n_unique, *n_words ...) = the length needed, and the call may be repeated with

@@ -357,6 +357,19 @@ class Context:
     def sync(self):
         self._check(self.lib.zk_sync(self.h))
 
+    def set_stream(self, handle):
+        """queue this context's work on a borrowed hipStream_t (an integer handle: torch.cuda.Stream().cuda_stream), which the
+        context never destroys; None: a new stream of its own.  Work already queued is waited for first.  The null stream --
+        handle 0, which is what torch's default stream reports -- cannot be borrowed (zk_set_stream reads NULL as "a stream of
+        your own"): ValueError, so that nobody gets an unordered stream without noticing; create a torch.cuda.Stream()."""
+        if handle is not None and int(handle) == 0:
+            raise ValueError("set_stream(0): the null stream cannot be borrowed; pass the handle of a stream that was created, or None")
+        self._check(self.lib.zk_set_stream(self.h, C.c_void_p(int(handle)) if handle is not None else None))
+
+    def get_stream(self):
+        """the hipStream_t the context queues its work on, as an integer handle"""
+        return self.lib.zk_get_stream(self.h) or 0
+
     def empty(self, n, dtype):
         dt = np.dtype(dtype)
         p = C.c_void_p(0)
