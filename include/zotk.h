@@ -42,6 +42,7 @@
  *         zk_capture_hits         d_text1, d_text2                  any address
  *         zk_capture_gather       d_text, d_out                     any address
  *         zk_strand_keys          d_text                            any address
+ *         zk_anchor_pileup        d_text                            any address
  *         zk_format_pairs         d_out                             any address
  *         zk_contig_render        d_out                             any address
  *         zk_copy                 d_dst, d_src                      any address, any byte count
@@ -182,6 +183,10 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_LINKS 24        /* zk_debruijn_links: the successor kernel (8 B read, 4 written per k-mer; the check and the directory are not in it) */
 #define ZK_PROF_LINKS_RC 25     /* zk_debruijn_links: the reverse-complement ranks, a launch of their own (8 B read, 4 written per k-mer) */
 #define ZK_PROF_CONTIG_RENDER 26 /* zk_contig_render: the length pass (4 B per node, 16 per contig) and the write pass (12 B read per node + the text) */
+#define ZK_PROF_PILEUP 27       /* zk_anchor_pileup: the lookup-and-emit kernel, one wave per read (pileup.hip; bytes = the text read + 12 B per pair
+                                   written; the check of the long lines is not in it) */
+#define ZK_PROF_PILEUP_CUT 28   /* zk_pileup_count: the gather (12 B read, 8 written per pair) and the cut (12 B read per pair, 16 B written per
+                                   distinct pair), one record each; the two sorts are ZK_PROF_PASS_PAIRS / ZK_PROF_TILE_SORT records */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -442,6 +447,47 @@ int zk_contig_walk(const uint32_t* next, const uint32_t* rc, uint64_t n, int K, 
  * thread: the work of a thread does not grow with a contig's length. */
 int zk_contig_render(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, int K, const uint32_t* d_nodes, uint64_t n_nodes,
                      const uint64_t* d_offs, uint64_t n_contigs, uint8_t* d_out, uint64_t cap, uint64_t* n_bytes);
+
+/* ---- reads placed on reference zones, `zot alu-finder` (commands/alu-finder.py:309-322, hits: 116-147) -----------------------
+ * The reference keeps refIdx[x] = [(zone, position), ...] for every K-mer of its zones, and per read pair runs `hits` on four
+ * lists of (k-mer, position): both orientations (basics.kmersWithPosLists, basics.py:490-533) of both mates.  `hits` collects the
+ * distinct diagonals (zone, q - p) over all windows (x, p) of the list and all (zone, q) in refIdx[x], then adds EVERY window of
+ * the list, matching or not, once per diagonal: acc[zone][r + p][x] += 1.
+ *
+ * Here the index is a bait table whose ids are ANCHORS (zk_bait_table_from_arrays: ascending and distinct per key).  The host
+ * lays the zones out on one u32 axis, one after another with at least 2 * pad free coordinates between them and pad before the
+ * first, so that anchor + (p' - p) names one (zone, position) for any two window positions p, p' of a line of at most pad
+ * bytes.
+ *
+ * zk_anchor_pileup: for each of the first n_reads records of a FASTQ text (d_lines from zk_line_ends, at least 4 * n_reads of
+ * them) the sequence line is stripped as str.strip() does (file.py:46; L bytes are left) and cut into its windows (x_j, j),
+ * j = the 0-based start; windows restart after any byte outside AaCcGgTtUu.  Orientation 0 is the list (x_j, p_j = j),
+ * orientation 1 the list (rc x_j, p_j = L - j - K).  Per orientation, D = {a - p_i : a in anchors(x_i)} (distinct), and the
+ * output is the multiset {(d + p_j, x_j) : d in D, j a window} over both orientations of every read: coordinates in d_coords,
+ * k-mers in d_kmers, |D| * windows pairs per read and orientation, in no specified order (zk_pileup_count sorts them).  One
+ * call takes one mate.
+ *   - 1 <= K <= 32 and K equal to the table's, else ZK_EINVAL before any launch.
+ *   - A line longer than pad with a hit (in either orientation) is ZK_ERANGE, found by a pass of its own before anything is
+ *     written: its coordinates could name another zone.  A batch of 2^32 pairs or more is ZK_ERANGE.
+ *   - The capacity convention: ZK_ENOSPC with *n_out = the pairs needed when they exceed cap, nothing written at or beyond
+ *     cap, repeatable with room.
+ *   - Exact for any number of diagonals: a wave keeps up to ZK_PILEUP_DIAGS diagonals of a read's orientation in registers;
+ *     a list with more is done again by a path without that bound (a diagonal belongs to the first window that gives it,
+ *     decided by looking its earlier windows up again), tests straddle the bound.
+ *   - An empty table, n_reads = 0, lines shorter than K: nothing is emitted.  All integer work. */
+#define ZK_PILEUP_DIAGS 256
+int zk_anchor_pileup(zk_ctx* ctx, const zk_bait_table* anchors, const uint8_t* d_text, const uint64_t* d_lines, uint64_t n_reads, int K,
+                     uint32_t pad, uint32_t* d_coords, uint64_t* d_kmers, uint64_t cap, uint64_t* n_out);
+
+/* The counted pile-up: the distinct (coordinate, k-mer) pairs of d_coords / d_kmers[0, n) (inputs, left as they are; n < 2^32;
+ * k-mers below 4^K), ascending by coordinate and then by k-mer, in d_oc / d_ok with the number of copies of each in d_cnt.
+ * Two stable pair sorts (by k-mer carrying the coordinate, by coordinate carrying the index), a gather, and a cut of the
+ * sorted pairs into runs -- head flags, a scan, run lengths -- over tiles of ZK_PILEUP_TILE pairs (tests place runs across
+ * them).  The capacity convention: ZK_ENOSPC with *n_out = the distinct pairs when they exceed cap, nothing written at all.
+ * All integer work: the same call returns the same bits. */
+#define ZK_PILEUP_TILE 4096
+int zk_pileup_count(zk_ctx* ctx, const uint32_t* d_coords, const uint64_t* d_kmers, uint64_t n, int K, uint32_t* d_oc, uint64_t* d_ok,
+                    uint32_t* d_cnt, uint64_t cap, uint64_t* n_out);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

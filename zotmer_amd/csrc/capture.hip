@@ -258,8 +258,6 @@ static int capture_hits(zk_ctx* c, const zk_bait_table* baits, const zk_bait_tab
 // ---------------------------------------------------------------------------------------
 // record gather
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ bool is_space(u32 ch) { return ch == ' ' || (ch >= 9 && ch <= 13); }   // str.strip()
-
 // line i of the text, stripped: [s, e)
 __device__ __forceinline__ void stripped_line(const u8* __restrict__ text, const u64* __restrict__ lines, u64 i, u64& s, u64& e) {
     s = i ? lines[i - 1] + 1 : 0;

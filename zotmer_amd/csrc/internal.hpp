@@ -60,10 +60,12 @@ struct zk_scalars {
     u64 links_bad;           // debruijn.hip: links_check_kernel found a key out of order or of 4^K and above
     u64 render_bad;          // debruijn.hip: contig_len_kernel found an offset out of order or a node that is no index
     u64 render_bytes;        // landing: the end of the last contig's text
+    u64 pileup_cursor;       // pileup.hip: pairs emitted (or that would have been)
+    u64 pileup_long;         // pileup.hip: long_line_kernel found a line longer than pad with a hit
 };
 // bytes of the fields first .. last (declared in that order, adjacent)
 #define ZK_SPAN(first, last) (offsetof(zk_scalars, last) + sizeof(zk_scalars::last) - offsetof(zk_scalars, first))
-static_assert(sizeof(zk_scalars) == 69 * sizeof(u64), "zk_scalars: u64 words only, no padding");
+static_assert(sizeof(zk_scalars) == 71 * sizeof(u64), "zk_scalars: u64 words only, no padding");
 static_assert(ZK_SPAN(rle_side, total) == 2 * sizeof(u64), "rle_prefix reads rle_side and total back as one range");
 static_assert(ZK_SPAN(total, acgt) == 5 * sizeof(u64), "the merges read total and acgt back as one range");
 static_assert(ZK_SPAN(acgt, n_keys) == 5 * sizeof(u64) && ZK_SPAN(acgt, sample_n) == 9 * sizeof(u64),

@@ -12,6 +12,8 @@ __device__ __forceinline__ u32 base_code(u32 ch, u32& ok) {     // A0 C1 G2 T/U3
     return t ^ (t >> 1);
 }
 
+__device__ __forceinline__ bool is_space(u32 ch) { return ch == ' ' || (ch >= 9 && ch <= 13); }   // what str.strip() strips
+
 __device__ __forceinline__ u64 spread_bits(u32 v) {      // bit i -> bit 2i
     u64 x = v;
     x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;

@@ -28,6 +28,7 @@ CONTIG_TILE = 4096                              # ZK_CONTIG_TILE
 VARS_TILE = 4096                                # ZK_VARS_TILE
 LINKS_TILE = 1024                               # ZK_LINKS_TILE
 NO_LINK = 0xFFFFFFFF                            # ZK_NO_LINK
+PILEUP_DIAGS, PILEUP_TILE = 256, 4096           # ZK_PILEUP_DIAGS, ZK_PILEUP_TILE
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -172,6 +173,8 @@ SIGNATURES = {
     "zk_debruijn_links": (_i, [_vp, _vp, _u64, _i, _vp, _vp]),
     "zk_contig_walk": (_i, [_vp, _vp, _u64, _i, _u64, _vp, _u64, _vp, _u64, _pu64, _pu64]),
     "zk_contig_render": (_i, [_vp, _vp, _u64, _i, _vp, _u64, _vp, _u64, _vp, _u64, _pu64]),
+    "zk_anchor_pileup": (_i, [_vp, _vp, _vp, _vp, _u64, _i, _u32, _vp, _vp, _u64, _pu64]),
+    "zk_pileup_count": (_i, [_vp, _vp, _vp, _u64, _i, _vp, _vp, _vp, _u64, _pu64]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
     "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
@@ -440,7 +443,8 @@ class Context:
     PROF_TAGS = {"hist_stream": 1, "hist_array": 2, "pass_stream": 3, "pass_keys": 4, "pass_pairs": 5, "rle": 6,
                  "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
-                 "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26}
+                 "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26,
+                 "pileup": 27, "pileup_cut": 28}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -1023,6 +1027,33 @@ class Context:
             rc = self.lib.zk_contig_render(*args(out))
         self._check(rc)
         return out.view(n.value)
+
+    # ---- reads piled up on reference zones (csrc/pileup.hip) ----------------------------------------------------
+    def anchor_pileup(self, table, text, lines, n_reads, K, pad, out=None):
+        """one mate of a FASTQ batch against a table whose ids are anchors -> (coordinates u32 view, k-mers u64 view): the pairs
+        (d + p, x) of every window of every read, once per diagonal d of its orientation's list, in no order (zk_anchor_pileup).
+        out: (coords, kmers) arrays to write into first; grown when too small."""
+        assert 4 * n_reads <= lines.n
+        n = C.c_uint64(0)
+        oc, ok = out if out is not None else (self.empty(text.n + 1024, np.uint32), self.empty(text.n + 1024, np.uint64))
+        assert oc.dtype.itemsize == 4 and ok.dtype.itemsize == 8
+        args = lambda a, b: (self.h, table.h, text.ptr, lines.ptr, int(n_reads), int(K), int(pad), a.ptr, b.ptr, min(a.n, b.n), C.byref(n))
+        rc = self.lib.zk_anchor_pileup(*args(oc, ok))
+        if rc == ZK_ENOSPC:
+            oc, ok = self.empty(n.value, np.uint32), self.empty(n.value, np.uint64)
+            rc = self.lib.zk_anchor_pileup(*args(oc, ok))
+        self._check(rc)
+        return oc.view(n.value), ok.view(n.value)
+
+    def pileup_count(self, coords, kmers, K):
+        """pairs of zk_anchor_pileup -> (coordinates u32, k-mers u64, counts u32) views: the distinct pairs, ascending by
+        coordinate and then by k-mer, with the number of copies of each (zk_pileup_count)"""
+        assert coords.n == kmers.n and coords.dtype.itemsize == 4 and kmers.dtype.itemsize == 8
+        n = C.c_uint64(0)
+        cap = coords.n
+        oc, ok, cnt = self.empty(cap, np.uint32), self.empty(cap, np.uint64), self.empty(cap, np.uint32)
+        self._check(self.lib.zk_pileup_count(self.h, coords.ptr, kmers.ptr, coords.n, int(K), oc.ptr, ok.ptr, cnt.ptr, cap, C.byref(n)))
+        return oc.view(n.value), ok.view(n.value), cnt.view(n.value)
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
