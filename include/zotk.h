@@ -41,6 +41,7 @@
  *         zk_last_newline         d_text                            any address
  *         zk_capture_hits         d_text1, d_text2                  any address
  *         zk_capture_gather       d_text, d_out                     any address
+ *         zk_pulldown_hits        d_text1, d_text2                  any address
  *         zk_strand_keys          d_text                            any address
  *         zk_anchor_pileup        d_text                            any address
  *         zk_format_pairs         d_out                             any address
@@ -187,6 +188,8 @@ int zk_tune(zk_ctx* ctx, int what, int value);
                                    written; the check of the long lines is not in it) */
 #define ZK_PROF_PILEUP_CUT 28   /* zk_pileup_count: the gather (12 B read, 8 written per pair) and the cut (12 B read per pair, 16 B written per
                                    distinct pair), one record each; the two sorts are ZK_PROF_PASS_PAIRS / ZK_PROF_TILE_SORT records */
+#define ZK_PROF_PULLDOWN_TALLY 29 /* zk_pulldown_hits: the tally (8 B read per distinct pair, one add each) and the histogram (5 B read per
+                                   read), one record each; the lookup before them is a ZK_PROF_CAPTURE_HITS record */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -258,6 +261,18 @@ int zk_capture_hits(zk_ctx* ctx, const zk_bait_table* baits, const zk_bait_table
  * spans[n_baits + 1 + b] = its first byte in d_out (b = n_baits: the ends).  Paired input: once per mate, with that mate's text. */
 int zk_capture_gather(zk_ctx* ctx, const uint64_t* d_pairs, uint64_t n_pairs, uint32_t n_baits, const uint8_t* d_text,
                       const uint64_t* d_lines, uint64_t n_lines, uint8_t* d_out, uint64_t cap, uint64_t* spans, uint64_t* n_bytes);
+
+/* ---- read pairs per bait with a histogram, `zot pulldown` (commands/pulldown.py) ---------------------------------------------
+ * zk_capture_hits with the bookkeeping of pulldown.py:77-99 behind it.  Arguments up to n_pairs: as zk_capture_hits, with the
+ * same contract for d_pairs, cap and *n_pairs (ZK_ENOSPC included).  veto (may be NULL) is the table of the -U sequences: a
+ * read with a window in it is "pushed up" -- it gives no pair and counts in no row -- and it is looked at even when baits
+ * has no keys.  d_hist (device, hist_cap words; hist_cap < n_records + 1 is ZK_EINVAL): d_hist[n], n = 0 .. n_records, = the reads
+ * of this batch that are not vetoed and hit exactly n distinct baits; the words from n_records + 1 on are not touched.
+ * *n_vetoed = the vetoed reads: sum(d_hist) + *n_vetoed == n_reads.  n_reads == 0 gives zeros.  After ZK_ENOSPC d_hist and
+ * *n_vetoed are unspecified. */
+int zk_pulldown_hits(zk_ctx* ctx, const zk_bait_table* baits, const zk_bait_table* veto, int read_K, const uint8_t* d_text1,
+                     const uint64_t* d_lines1, const uint8_t* d_text2, const uint64_t* d_lines2, uint64_t n_reads, uint64_t* d_pairs,
+                     uint64_t cap, uint64_t* n_pairs, uint64_t* d_hist, uint64_t hist_cap, uint64_t* n_vetoed);
 
 /* ---- complete alleles of a k-mer index, `zot mlst` (commands/mlst.py, library/index.py) -----------------------------------
  * The index of library/index.py:67-125 -- S, the sorted distinct K-mers of both strands of every FASTA record; T, CSR offsets;

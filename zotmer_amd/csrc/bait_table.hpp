@@ -47,4 +47,16 @@ int tmalloc(zk_ctx* c, void** p, uint64_t bytes);   // memory of a table (at lea
 // Synchronises and reads the device error word.
 int bait_table_directory(zk_ctx* c, zk_bait_table* t);
 
+// The two halves of zk_capture_hits, shared with zk_pulldown_hits (pulldown.hip).
+struct Mate { const u8* text; const u64* lines; };   // a FASTQ text and the positions of its line ends (m2.text null: single reads)
+// The window lookup, one wave per read: the (bait, read) pairs as they come, unsorted and with repeats, into pairs[0, cap);
+// *raw = how many there were (beyond cap nothing is written: the caller refuses).  mark (null, or u8[n_reads] zeroed on the
+// stream): 1 for every read with a window in the veto table.  Uses no arena memory; synchronises.
+int capture_lookup(zk_ctx* c, const zk_bait_table* baits, const zk_bait_table* veto, int RK, Mate m1, Mate m2, uint64_t n_reads,
+                   u64* pairs, uint64_t cap, u8* mark, uint64_t* raw);
+// pairs[0, raw) sorted, the distinct ones back in pairs[0, *n_pairs).  Takes capture_sort_bytes(raw) from the arena (the
+// caller has made room: arena_require); asynchronous but for the count.
+static inline uint64_t capture_sort_bytes(uint64_t raw) { return 16 * raw + raw / 32 + (4 << 20); }
+int capture_sort_dedupe(zk_ctx* c, const zk_bait_table* baits, u64* pairs, uint64_t raw, uint64_t* n_pairs);
+
 }  // namespace zk

@@ -173,10 +173,11 @@ __device__ __forceinline__ u32 wave_min_u32(u32 v) {
     return v;
 }
 
-struct Mate { const u8* text; const u64* lines; };
-
+// MARK: lane 0 of a wave whose read is vetoed says so in mark[r] (zk_pulldown_hits counts those reads and keeps them out of its
+// histogram); zk_capture_hits runs the instantiation without it
+template <bool MARK>
 __global__ __launch_bounds__(256) void capture_hits_kernel(BaitView bt, BaitView vt, int RK, Mate m1, Mate m2, u64 n_reads,
-                                                           u64* __restrict__ pairs, u64 cap, u64* n_raw) {
+                                                           u64* __restrict__ pairs, u64 cap, u64* n_raw, u8* __restrict__ mark) {
     const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     const u64 nw = ((u64)gridDim.x * blockDim.x) >> 6;
@@ -193,7 +194,10 @@ __global__ __launch_bounds__(256) void capture_hits_kernel(BaitView bt, BaitView
                     veto = __ballot(hit) != 0;
                 }
             }
-            if (veto) continue;
+            if (veto) {
+                if (MARK && lane == 0) mark[r] = 1;
+                continue;
+            }
         }
         for (int m = 0; m < mates; m++) {
             const Mate mt = m ? m2 : m1;
@@ -217,28 +221,28 @@ __global__ __launch_bounds__(256) void capture_hits_kernel(BaitView bt, BaitView
     }
 }
 
-static int capture_hits(zk_ctx* c, const zk_bait_table* baits, const zk_bait_table* veto, int RK, Mate m1, Mate m2,
-                        uint64_t n_reads, u64* pairs, uint64_t cap, uint64_t* n_pairs) {
-    *n_pairs = 0;
-    if (n_reads == 0 || baits->n_keys == 0) return ZK_OK;
+int capture_lookup(zk_ctx* c, const zk_bait_table* baits, const zk_bait_table* veto, int RK, Mate m1, Mate m2, uint64_t n_reads,
+                   u64* pairs, uint64_t cap, u8* mark, uint64_t* raw) {
     u64* d_raw = &c->d_scalars->capture_raw;
     ZK_HIP(c, hipMemsetAsync(d_raw, 0, sizeof(u64), c->stream));
+    const dim3 grid(grid_cap(c, div_up(n_reads, 4), 16));
     prof_begin(c, ZK_PROF_CAPTURE_HITS, 0);
-    hipLaunchKernelGGL(capture_hits_kernel, dim3(grid_cap(c, div_up(n_reads, 4), 16)), dim3(256), 0, c->stream, view_of(baits), view_of(veto), RK, m1, m2,
-                       (u64)n_reads, pairs, (u64)cap, d_raw);
+    if (mark)
+        hipLaunchKernelGGL(capture_hits_kernel<true>, grid, dim3(256), 0, c->stream, view_of(baits), view_of(veto), RK, m1, m2, (u64)n_reads, pairs,
+                           (u64)cap, d_raw, mark);
+    else
+        hipLaunchKernelGGL(capture_hits_kernel<false>, grid, dim3(256), 0, c->stream, view_of(baits), view_of(veto), RK, m1, m2, (u64)n_reads, pairs,
+                           (u64)cap, d_raw, (u8*)nullptr);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->capture_raw));
     ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
-    const uint64_t raw = c->h_scalars->capture_raw;
-    if (raw > cap) {
-        *n_pairs = raw;
-        return fail(c, ZK_ENOSPC, "capture: %llu (bait, read) pairs before deduplication, room for %llu", (unsigned long long)raw,
-                    (unsigned long long)cap);
-    }
-    if (raw == 0) return ZK_OK;
-    ZK_TRY(arena_require(c, 16 * raw + raw / 32 + (4 << 20), 16 * raw + raw / 32 + (4 << 20)));
+    *raw = c->h_scalars->capture_raw;
+    return ZK_OK;
+}
+
+int capture_sort_dedupe(zk_ctx* c, const zk_bait_table* baits, u64* pairs, uint64_t raw, uint64_t* n_pairs) {
     u64 *alt, *res;
     ZK_TRY(arena_alloc(c, 8 * raw, (void**)&alt));
     int bbits = 1;
@@ -250,8 +254,25 @@ static int capture_hits(zk_ctx* c, const zk_bait_table* baits, const zk_bait_tab
     uint64_t n = 0;
     ZK_TRY(compact_count(c, dw, raw, &cnt, &n));
     ZK_TRY(compact_write(c, dw, raw, cnt));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
     *n_pairs = n;
+    return ZK_OK;
+}
+
+static int capture_hits(zk_ctx* c, const zk_bait_table* baits, const zk_bait_table* veto, int RK, Mate m1, Mate m2,
+                        uint64_t n_reads, u64* pairs, uint64_t cap, uint64_t* n_pairs) {
+    *n_pairs = 0;
+    if (n_reads == 0 || baits->n_keys == 0) return ZK_OK;
+    uint64_t raw = 0;
+    ZK_TRY(capture_lookup(c, baits, veto, RK, m1, m2, n_reads, pairs, cap, nullptr, &raw));
+    if (raw > cap) {
+        *n_pairs = raw;
+        return fail(c, ZK_ENOSPC, "capture: %llu (bait, read) pairs before deduplication, room for %llu", (unsigned long long)raw,
+                    (unsigned long long)cap);
+    }
+    if (raw == 0) return ZK_OK;
+    ZK_TRY(arena_require(c, capture_sort_bytes(raw), capture_sort_bytes(raw)));
+    ZK_TRY(capture_sort_dedupe(c, baits, pairs, raw, n_pairs));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
     return check_device_error(c);
 }
 

@@ -165,6 +165,7 @@ SIGNATURES = {
     "zk_line_ends": (_i, [_vp, _vp, _u64, _vp, _u64, _pu64]),
     "zk_capture_hits": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _pu64]),
     "zk_capture_gather": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _u64, _pu64, _pu64]),
+    "zk_pulldown_hits": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _pu64, _vp, _u64, _pu64]),
     "zk_strand_keys": (_i, [_vp, _vp, _vp, _u64, _i, _i, _u64, _u64, _vp, _u64, _pu64]),
     "zk_strand_pairs": (_i, [_vp, _vp, _vp, _i, _u64, _i, _u64, _i, _vp, _vp, _u64, C.POINTER(StrandStats)]),
     "zk_format_pairs": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _pu64]),
@@ -444,7 +445,7 @@ class Context:
                  "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
                  "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26,
-                 "pileup": 27, "pileup_cut": 28}
+                 "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -893,6 +894,25 @@ class Context:
             rc = self.lib.zk_capture_gather(*args(out))
         self._check(rc)
         return out.view(n.value), spans[:n_baits + 1], spans[n_baits + 1:]
+
+    # ---- read pairs per bait (csrc/pulldown.hip) --------------------------------------------------------------
+    def pulldown_hits(self, table, read_K, text1, lines1, n_reads, text2=None, lines2=None, veto=None, out=None):
+        """capture_hits with pulldown.py's bookkeeping -> (pairs: u64 DeviceArray view as capture_hits gives it, hist:
+        numpy u64[n_records + 1] with hist[n] = the reads that are not vetoed and hit n distinct baits, the vetoed reads)"""
+        assert 4 * n_reads <= lines1.n and (lines2 is None or 4 * n_reads <= lines2.n)
+        n, nv = C.c_uint64(0), C.c_uint64(0)
+        if out is None:
+            out = self.empty(2 * n_reads + 1024, np.uint64)
+        hist = self.empty(table.n_records + 1, np.uint64)
+        args = lambda o: (self.h, table.h, veto.h if veto is not None else None, int(read_K), text1.ptr, lines1.ptr,
+                          text2.ptr if text2 is not None else None, lines2.ptr if lines2 is not None else None, int(n_reads), o.ptr,
+                          o.n, C.byref(n), hist.ptr, hist.n, C.byref(nv))
+        rc = self.lib.zk_pulldown_hits(*args(out))
+        if rc == ZK_ENOSPC:
+            out = self.empty(n.value + 1024, np.uint64)
+            rc = self.lib.zk_pulldown_hits(*args(out))
+        self._check(rc)
+        return out.view(n.value), hist.to_host(), nv.value
 
     # ---- strand bias (csrc/strand_bias.hip) ------------------------------------------------------------------
     def strand_keys(self, text, lines, n_reads, K, reverse, T, out, offset=0, seed=17):
