@@ -44,6 +44,7 @@
  *         zk_pulldown_hits        d_text1, d_text2                  any address
  *         zk_strand_keys          d_text                            any address
  *         zk_anchor_pileup        d_text                            any address
+ *         zk_capture_kmers        d_text1, d_text2                  any address
  *         zk_format_pairs         d_out                             any address
  *         zk_contig_render        d_out                             any address
  *         zk_copy                 d_dst, d_src                      any address, any byte count
@@ -190,6 +191,10 @@ int zk_tune(zk_ctx* ctx, int what, int value);
                                    distinct pair), one record each; the two sorts are ZK_PROF_PASS_PAIRS / ZK_PROF_TILE_SORT records */
 #define ZK_PROF_PULLDOWN_TALLY 29 /* zk_pulldown_hits: the tally (8 B read per distinct pair, one add each) and the histogram (5 B read per
                                    read), one record each; the lookup before them is a ZK_PROF_CAPTURE_HITS record */
+#define ZK_PROF_CAPTURE_KMERS 30 /* zk_capture_kmers: the emit kernel, one wave per (bait, read) pair (hgvs_find.hip; bytes = 12 B written per entry);
+                                   the count passes before it are not in it */
+#define ZK_PROF_PATH_SCAN 31    /* zk_path_scan: the count pass and the emit pass over the entries (16 B read per entry each, 8 B written per
+                                   match), one record each */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -503,6 +508,49 @@ int zk_anchor_pileup(zk_ctx* ctx, const zk_bait_table* anchors, const uint8_t* d
 #define ZK_PILEUP_TILE 4096
 int zk_pileup_count(zk_ctx* ctx, const uint32_t* d_coords, const uint64_t* d_kmers, uint64_t n, int K, uint32_t* d_oc, uint64_t* d_ok,
                     uint32_t* d_cnt, uint64_t cap, uint64_t* n_out);
+
+/* ---- variants called from captured read pairs, `zot hgvs-find` (commands/hgvs-find.py:917-1131) ---------------------------------
+ * The reference hands every read pair to capture.addReadPairAndKmers (library/capture.py:99-135): ns = the baits that hold a
+ * k-mer of either mate, and for each n in ns every element of kmersList(K, mate, True) of both mates -- every window x and its
+ * reverse complement, a palindrome therefore twice -- is added to capKmers[n].  The alleles are then recovered from capKmers[n]
+ * through Hamming neighbours of an expected k-mer path (library/debruijn.py:334-409, hgvs-find.py:517-583).
+ *
+ * zk_capture_kmers: d_pairs[0, n_pairs) is what zk_capture_hits returns (bait << 32 | read, ascending; any 8-byte aligned
+ * address).  For every pair word, every window x of the sequence line of that read in each text (d_lines* from zk_line_ends;
+ * d_text2 and d_lines2 both NULL: single reads) gives the entries (bait, x) and (bait, rc x): baits in d_baits, k-mers in d_kmers.
+ * Windows restart after any byte outside AaCcGgTtUu (white space around the line gives no window, so the line needs no
+ * stripping).  The order of the entries is unspecified, their multiset is fixed: zk_pileup_count sorts and counts them.
+ *   - 1 <= K <= 32, else ZK_EINVAL before any launch.  A pair whose read is >= n_reads is ZK_EINVAL, nothing written.
+ *   - 2^32 entries or more is ZK_ERANGE (use shorter slices of the pair list), *n_out = the entries.
+ *   - The capacity convention: ZK_ENOSPC with *n_out = the entries needed when they exceed cap, nothing written at all,
+ *     repeatable with room.
+ *   - Three passes: the reads the pairs name are marked and their valid windows counted, once per read however many baits hit
+ *     it; the pairs' exclusive offsets (a scan); then one wave per pair, 64 window starts per step, the lanes of a step writing
+ *     neighbouring entries (the windows of the step, then their reverse complements).  No atomics; all integer work. */
+int zk_capture_kmers(zk_ctx* ctx, const uint64_t* d_pairs, uint64_t n_pairs, const uint8_t* d_text1, const uint64_t* d_lines1,
+                     const uint8_t* d_text2, const uint64_t* d_lines2, uint64_t n_reads, int K, uint32_t* d_baits, uint64_t* d_kmers,
+                     uint64_t cap, uint64_t* n_out);
+
+/* fixed_path_kmers' candidate search (library/debruijn.py:364-383) and findAnchors' (hgvs-find.py:534-553), for many windows and
+ * many baits in one call.  The entries d_baits / d_kmers / d_counts[0, n) are a counted list as zk_pileup_count writes it:
+ * ascending by bait and then by k-mer, n < 2^32, k-mers below 4^K.  windows is a HOST array ascending by bait (a bait may have
+ * many).  Entry e matches window w iff
+ *     d_baits[e] == w.bait  &&  (d_kmers[e] & w.mask) == (w.value & w.mask)  &&  ham(d_kmers[e], w.value) <= w.max_ham
+ *     &&  d_counts[e] >= w.min_count,
+ * ham being basics.ham (basics.py:123-133, as for zk_probe_scan: a base that differs in one bit or in both is one mismatch).
+ * Every match is written as (window index, entry index) into d_win / d_entry, ascending by window and then by entry.
+ *   - ZK_EINVAL before any launch: K outside 1 .. 32, windows not ascending by bait, a value or a mask >= 4^K.
+ *   - n == 0 or n_windows == 0: *n_out = 0.  The capacity convention: ZK_ENOSPC with *n_out = the matches when they exceed cap,
+ *     nothing written at all, repeatable with room.
+ *   - A workgroup takes one tile of ZK_PATH_TILE entries, a wave a quarter of it; the windows of the baits that occur in the
+ *     tile are staged in LDS, ZK_PATH_CHUNK at a time.  A count pass writes the matches per (window, tile), window-major; a scan
+ *     turns them into offsets; the emit pass repeats the comparison and ranks a match by ballots within its wave and by the
+ *     waves' counts within its tile.  No atomics: the same call returns the same bits.  `reserved` is ignored. */
+#define ZK_PATH_TILE 4096
+#define ZK_PATH_CHUNK 256
+typedef struct { uint64_t value, mask; uint32_t bait, max_ham, min_count, reserved; } zk_path_window;
+int zk_path_scan(zk_ctx* ctx, const uint32_t* d_baits, const uint64_t* d_kmers, const uint32_t* d_counts, uint64_t n, int K,
+                 const zk_path_window* windows, uint32_t n_windows, uint32_t* d_win, uint32_t* d_entry, uint64_t cap, uint64_t* n_out);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

@@ -63,10 +63,13 @@ struct zk_scalars {
     u64 pileup_cursor;       // pileup.hip: pairs emitted (or that would have been)
     u64 pileup_long;         // pileup.hip: long_line_kernel found a line longer than pad with a hit
     u64 pulldown_vetoed;     // pulldown.hip: reads with a window in the veto table
+    u64 capkmers_bad;        // hgvs_find.hip: capkmers_mark_kernel found a pair whose read is no record of the batch
+    u64 capkmers_total;      // landing: the end of the last pair's entries
+    u64 path_total;          // landing: the end of the last (window, tile) cell's matches
 };
 // bytes of the fields first .. last (declared in that order, adjacent)
 #define ZK_SPAN(first, last) (offsetof(zk_scalars, last) + sizeof(zk_scalars::last) - offsetof(zk_scalars, first))
-static_assert(sizeof(zk_scalars) == 72 * sizeof(u64), "zk_scalars: u64 words only, no padding");
+static_assert(sizeof(zk_scalars) == 75 * sizeof(u64), "zk_scalars: u64 words only, no padding");
 static_assert(ZK_SPAN(rle_side, total) == 2 * sizeof(u64), "rle_prefix reads rle_side and total back as one range");
 static_assert(ZK_SPAN(total, acgt) == 5 * sizeof(u64), "the merges read total and acgt back as one range");
 static_assert(ZK_SPAN(acgt, n_keys) == 5 * sizeof(u64) && ZK_SPAN(acgt, sample_n) == 9 * sizeof(u64),

@@ -29,6 +29,7 @@ VARS_TILE = 4096                                # ZK_VARS_TILE
 LINKS_TILE = 1024                               # ZK_LINKS_TILE
 NO_LINK = 0xFFFFFFFF                            # ZK_NO_LINK
 PILEUP_DIAGS, PILEUP_TILE = 256, 4096           # ZK_PILEUP_DIAGS, ZK_PILEUP_TILE
+PATH_TILE, PATH_CHUNK = 4096, 256               # ZK_PATH_TILE, ZK_PATH_CHUNK
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -66,6 +67,13 @@ class VarsStats(C.Structure):
 class ProbeWindow(C.Structure):
     """zk_probe_window: the J bases `value` of a probe, compared with the top J bases of every k-mer (include/zotk.h)"""
     _fields_ = [("value", C.c_uint64), ("J", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PathWindow(C.Structure):
+    """zk_path_window: a k-mer `value` that the entries of `bait` are compared with, under `mask`, up to `max_ham` substituted
+    bases, from `min_count` copies on (include/zotk.h)"""
+    _fields_ = [("value", C.c_uint64), ("mask", C.c_uint64), ("bait", C.c_uint32), ("max_ham", C.c_uint32),
+                ("min_count", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class KmerizeStats(C.Structure):
@@ -176,6 +184,8 @@ SIGNATURES = {
     "zk_contig_render": (_i, [_vp, _vp, _u64, _i, _vp, _u64, _vp, _u64, _vp, _u64, _pu64]),
     "zk_anchor_pileup": (_i, [_vp, _vp, _vp, _vp, _u64, _i, _u32, _vp, _vp, _u64, _pu64]),
     "zk_pileup_count": (_i, [_vp, _vp, _vp, _u64, _i, _vp, _vp, _vp, _u64, _pu64]),
+    "zk_capture_kmers": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _i, _vp, _vp, _u64, _pu64]),
+    "zk_path_scan": (_i, [_vp, _vp, _vp, _vp, _u64, _i, C.POINTER(PathWindow), _u32, _vp, _vp, _u64, _pu64]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
     "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
@@ -445,7 +455,7 @@ class Context:
                  "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
                  "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26,
-                 "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29}
+                 "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -1074,6 +1084,51 @@ class Context:
         oc, ok, cnt = self.empty(cap, np.uint32), self.empty(cap, np.uint64), self.empty(cap, np.uint32)
         self._check(self.lib.zk_pileup_count(self.h, coords.ptr, kmers.ptr, coords.n, int(K), oc.ptr, ok.ptr, cnt.ptr, cap, C.byref(n)))
         return oc.view(n.value), ok.view(n.value), cnt.view(n.value)
+
+    # ---- variants called from captured read pairs (csrc/hgvs_find.hip) -----------------------------------------
+    def capture_kmers_into(self, pairs, text1, lines1, n_reads, K, text2, lines2, out_baits, out_kmers):
+        """zk_capture_kmers into the arrays given -> (entries written or, if they did not fit, needed; whether they fit).
+        2^32 entries or more never fit: the caller passes fewer pairs."""
+        assert 4 * n_reads <= lines1.n and (lines2 is None or 4 * n_reads <= lines2.n)
+        assert out_baits.dtype.itemsize == 4 and out_kmers.dtype.itemsize == 8
+        n = C.c_uint64(0)
+        rc = self.lib.zk_capture_kmers(self.h, pairs.ptr, pairs.n, text1.ptr, lines1.ptr, text2.ptr if text2 is not None else None,
+                                       lines2.ptr if lines2 is not None else None, int(n_reads), int(K), out_baits.ptr, out_kmers.ptr,
+                                       min(out_baits.n, out_kmers.n), C.byref(n))
+        if rc not in (ZK_ENOSPC, ZK_ERANGE):
+            self._check(rc)
+        return n.value, rc == ZK_OK
+
+    def capture_kmers(self, pairs, text1, lines1, n_reads, K, text2=None, lines2=None, out=None):
+        """pairs of capture_hits (or a slice of them) -> (baits u32 view, k-mers u64 view): (bait, x) and (bait, rc x) for every
+        window x of the pair's read in each text, in no order (zk_capture_kmers).  out: (baits, kmers) arrays to write into
+        first; grown when too small."""
+        ob, ok = out if out is not None else (self.empty(256 * pairs.n + 1024, np.uint32), self.empty(256 * pairs.n + 1024, np.uint64))
+        n, fit = self.capture_kmers_into(pairs, text1, lines1, n_reads, K, text2, lines2, ob, ok)
+        if not fit:
+            if n >= 1 << 32:
+                raise ZotkError(ZK_ERANGE, "zk_capture_kmers: %d entries in one call (at most 2^32 - 1); pass fewer pairs" % n)
+            ob, ok = self.empty(n, np.uint32), self.empty(n, np.uint64)
+            n, fit = self.capture_kmers_into(pairs, text1, lines1, n_reads, K, text2, lines2, ob, ok)
+            assert fit
+        return ob.view(n), ok.view(n)
+
+    def path_scan(self, baits, kmers, counts, K, windows, out=None):
+        """a counted (bait, k-mer) list as pileup_count gives it + windows = [(bait, value, mask, max_ham, min_count), ...]
+        ascending by bait -> (window indices, entry indices): numpy u32 arrays of the matches, ascending
+        by window and then by entry (zk_path_scan).  out: (win, entry) u32 DeviceArrays to write into first; grown when too small."""
+        assert baits.n == kmers.n == counts.n and baits.dtype.itemsize == 4 and kmers.dtype.itemsize == 8 and counts.dtype.itemsize == 4
+        arr = (PathWindow * max(len(windows), 1))(*[PathWindow(int(v), int(m), int(b), int(h), int(q), 0) for b, v, m, h, q in windows])
+        nw = len(windows)
+        n = C.c_uint64(0)
+        ow, oe = out if out is not None else (self.empty(4 * nw + 1024, np.uint32), self.empty(4 * nw + 1024, np.uint32))
+        args = lambda a, b: (self.h, baits.ptr, kmers.ptr, counts.ptr, baits.n, int(K), arr, nw, a.ptr, b.ptr, min(a.n, b.n), C.byref(n))
+        rc = self.lib.zk_path_scan(*args(ow, oe))
+        if rc == ZK_ENOSPC:
+            ow, oe = self.empty(n.value, np.uint32), self.empty(n.value, np.uint32)
+            rc = self.lib.zk_path_scan(*args(ow, oe))
+        self._check(rc)
+        return ow.to_host(n.value), oe.to_host(n.value)
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
