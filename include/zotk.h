@@ -195,6 +195,9 @@ int zk_tune(zk_ctx* ctx, int what, int value);
                                    the count passes before it are not in it */
 #define ZK_PROF_PATH_SCAN 31    /* zk_path_scan: the count pass and the emit pass over the entries (16 B read per entry each, 8 B written per
                                    match), one record each */
+#define ZK_PROF_LCP_RESOLVE 32  /* zk_lcp_resolve: every launch of the call as one record (lcp_scan.hip; bytes = 48 per index k-mer + 12 per
+                                   k-mer and doubling round; the searches in the sample are not in the figure) */
+#define ZK_PROF_SCAN_PLACE 33   /* zk_scan_place: the offer pass and the gather (8 B per entry, 17 B per slot); the check before them is not in it */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -551,6 +554,50 @@ int zk_capture_kmers(zk_ctx* ctx, const uint64_t* d_pairs, uint64_t n_pairs, con
 typedef struct { uint64_t value, mask; uint32_t bait, max_ham, min_count, reserved; } zk_path_window;
 int zk_path_scan(zk_ctx* ctx, const uint32_t* d_baits, const uint64_t* d_kmers, const uint32_t* d_counts, uint64_t n, int K,
                  const zk_path_window* windows, uint32_t n_windows, uint32_t* d_win, uint32_t* d_entry, uint64_t cap, uint64_t* n_out);
+
+/* ---- gene alleles from a k-mer set, `zot scan` (commands/scan.py) -----------------------------------------------------------------
+ * zk_lcp_resolve: d_S[0, nS) are the index's k-mers and d_X[0, nX) the sample's, both strictly ascending and below 4^K (not
+ * checked).  With lcp = basics.lcp (basics.py:160-170), d_L / d_Y receive exactly what resolveAll (scan.py:95-120) leaves in
+ * its L and Y, which is the result of two SEQUENTIAL loops:
+ *     pass 1   x = the first element of X that is >= S[i], or the last element of X where there is none;
+ *              l = lcp(K, x, S[i]);  (L[i], Y[i]) = (l, x) if l > 0, else (0, 0)
+ *     pass 2   for i = 1 .. nS - 1 in this order:  x = Y[i - 1] as it stands NOW;  l = lcp(K, x, S[i]);
+ *              if l > L[i]: (L[i], Y[i]) = (l, x)
+ * This is NOT the better of the two neighbours of S[i] in X: a value travels on through pass 2 for as long as it beats every
+ * pass-1 value it meets, a 0 left by pass 1 travels too (it matches leading A's), and a predecessor in X that no entry
+ * carried is never looked at.
+ *   - 1 <= K <= 32, else ZK_EINVAL (K = 32 uses all 64 bits of the xor).  nS == 0: nothing is written, ZK_OK.  nX == 0 with
+ *     nS > 0: ZK_EINVAL (the reference dies there with NameError).  nS >= 2^32: ZK_ERANGE (the index's T is 32 bits wide).
+ *   - How it is computed (csrc/lcp_scan.hip): pass 1 is a search per entry.  For pass 2 every j finds
+ *     nb(j), the first i > j where Y1[j] no longer beats L1[i]; the entries that keep their pass-1 value are the orbit of 0
+ *     under nb, marked by pointer doubling in ceil(log2 nS) rounds; every other entry takes the value of the last marked entry
+ *     before it.  A workgroup takes ZK_LCP_TILE entries in every kernel of the call.
+ *   - How far one thread can walk: the search for nb(j) looks at entries one by one only inside a tile, steps over a whole
+ *     tile (and over 256 tiles at once) whose largest L1 is below the value's lcp with the tile's last entry, and can walk a
+ *     tile to its end without stopping only where that lcp falls inside it, at most K times.  That bounds every walk by
+ *     512 (K + 2) + nS / 65536 steps.  The input that drives it there is a sample of two elements around an index whose
+ *     k-mers all begin with A, with pass-1 values that rise just under a falling lcp; on clustered trial lists of up to 400
+ *     k-mers the longest walk was 142 steps.  Without the stepping the same input costs nS steps per entry.
+ *   - No atomics, no floating point: the same call returns the same bits.  Workspace: 9 bytes per index k-mer.
+ *
+ * zk_scan_place: scan.py:281-304 for all records in one call.  The index lists, for S[i], the entries j in [T[i], T[i + 1]):
+ * record U[j] and signed 1-based position V[j] (negative: the reverse strand).  Record n owns the slots
+ * [d_rec_off[n], d_rec_off[n + 1]) of d_P / d_Q (d_rec_off: n_rec + 1 words, the exclusive prefix sum of lens[n] - K + 1), and
+ * entry j names slot q = V[j] - 1 of its record, on the reverse strand -(V[j] + 1), where it offers y = Y[i], on the reverse
+ * strand rc(K, Y[i]).  Per slot the winner is the entry with the largest L[i]; among equals the smallest j, which is the first
+ * in the reference's (i, j) order; Q = its L, P = its y.  A slot whose best L is 0, or that no entry names, is (0, 0).
+ * d_cnt[n * (K + 1) + l] = the entries of record n whose L is l.  All three outputs are written in full.
+ *   - ZK_EINVAL with nothing written: K outside 1 .. 32; T not ascending from 0 to n_entries; d_rec_off not ascending from 0;
+ *     an L above K; an entry whose record is >= n_rec, whose V is 0 or whose slot lies outside its record.
+ *     nS, n_entries or n_rec >= 2^32: ZK_ERANGE.
+ *   - A check pass; then per entry a search of its i in T, one 32-bit add and (where L > 0) one 64-bit max of
+ *     (L << 32 | 2^32 - 1 - j) on a workspace word per slot; then a gather per slot.  Integer atomics only: the result does
+ *     not depend on their order.  Workspace: 8 bytes per slot. */
+#define ZK_LCP_TILE 256
+int zk_lcp_resolve(zk_ctx* ctx, const uint64_t* d_S, uint64_t nS, const uint64_t* d_X, uint64_t nX, int K, uint8_t* d_L, uint64_t* d_Y);
+int zk_scan_place(zk_ctx* ctx, const uint8_t* d_L, const uint64_t* d_Y, uint64_t nS, const uint32_t* d_T, const uint32_t* d_U,
+                  const int32_t* d_V, uint64_t n_entries, const uint64_t* d_rec_off, uint64_t n_rec, int K, uint64_t* d_P, uint8_t* d_Q,
+                  uint32_t* d_cnt);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

@@ -66,10 +66,12 @@ struct zk_scalars {
     u64 capkmers_bad;        // hgvs_find.hip: capkmers_mark_kernel found a pair whose read is no record of the batch
     u64 capkmers_total;      // landing: the end of the last pair's entries
     u64 path_total;          // landing: the end of the last (window, tile) cell's matches
+    u64 place_bad;           // lcp_scan.hip: scan_check_kernel found an array that breaks zk_scan_place's rules
+    u64 place_slots;         // landing: the last record offset = the slots of P and Q
 };
 // bytes of the fields first .. last (declared in that order, adjacent)
 #define ZK_SPAN(first, last) (offsetof(zk_scalars, last) + sizeof(zk_scalars::last) - offsetof(zk_scalars, first))
-static_assert(sizeof(zk_scalars) == 75 * sizeof(u64), "zk_scalars: u64 words only, no padding");
+static_assert(sizeof(zk_scalars) == 77 * sizeof(u64), "zk_scalars: u64 words only, no padding");
 static_assert(ZK_SPAN(rle_side, total) == 2 * sizeof(u64), "rle_prefix reads rle_side and total back as one range");
 static_assert(ZK_SPAN(total, acgt) == 5 * sizeof(u64), "the merges read total and acgt back as one range");
 static_assert(ZK_SPAN(acgt, n_keys) == 5 * sizeof(u64) && ZK_SPAN(acgt, sample_n) == 9 * sizeof(u64),
@@ -373,4 +375,5 @@ int make_partition(zk_ctx* c, const u64* A, u64 nA, const u64* B, u64 nB, u64** 
 int project_sum(zk_ctx* c, const u64* keys, const void* cnts, int count_bits, uint64_t n, int shift, u64* out_k, u64* out_s, uint64_t cap,
                 uint64_t* n_out, uint64_t* total);
 int spectrum_sums(zk_ctx* c, const u64* A, const u64* sA, u64 nA, const u64* B, const u64* sB, u64 nB, double cx, double cy, zk_spectrum* out);
+// lcp_scan.hip: zk_lcp_resolve and zk_scan_place; nothing of it is called from another unit
 }  // namespace zk

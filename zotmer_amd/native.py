@@ -30,6 +30,7 @@ LINKS_TILE = 1024                               # ZK_LINKS_TILE
 NO_LINK = 0xFFFFFFFF                            # ZK_NO_LINK
 PILEUP_DIAGS, PILEUP_TILE = 256, 4096           # ZK_PILEUP_DIAGS, ZK_PILEUP_TILE
 PATH_TILE, PATH_CHUNK = 4096, 256               # ZK_PATH_TILE, ZK_PATH_CHUNK
+LCP_TILE = 256                                  # ZK_LCP_TILE
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -186,6 +187,8 @@ SIGNATURES = {
     "zk_pileup_count": (_i, [_vp, _vp, _vp, _u64, _i, _vp, _vp, _vp, _u64, _pu64]),
     "zk_capture_kmers": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _i, _vp, _vp, _u64, _pu64]),
     "zk_path_scan": (_i, [_vp, _vp, _vp, _vp, _u64, _i, C.POINTER(PathWindow), _u32, _vp, _vp, _u64, _pu64]),
+    "zk_lcp_resolve": (_i, [_vp, _vp, _u64, _vp, _u64, _i, _vp, _vp]),
+    "zk_scan_place": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _i, _vp, _vp, _vp]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
     "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
@@ -455,7 +458,7 @@ class Context:
                  "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
                  "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26,
-                 "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31}
+                 "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31, "lcp_resolve": 32, "scan_place": 33}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -1129,6 +1132,24 @@ class Context:
             rc = self.lib.zk_path_scan(*args(ow, oe))
         self._check(rc)
         return ow.to_host(n.value), oe.to_host(n.value)
+
+    # ---- gene alleles from a k-mer set (csrc/lcp_scan.hip) -------------------------------------------------------
+    def lcp_resolve(self, S, X, K, out=None):
+        """ascending index k-mers S and sample k-mers X -> (L u8, Y u64) DeviceArrays of S.n entries: what the reference's
+        resolveAll leaves (zk_lcp_resolve).  out: (L, Y) arrays to write into."""
+        L, Y = out if out is not None else (self.empty(S.n, np.uint8), self.empty(S.n, np.uint64))
+        assert L.n >= S.n and Y.n >= S.n and L.dtype.itemsize == 1 and Y.dtype.itemsize == 8
+        self._check(self.lib.zk_lcp_resolve(self.h, S.ptr, S.n, X.ptr, X.n, int(K), L.ptr, Y.ptr))
+        return L, Y
+
+    def scan_place(self, L, Y, T, U, V, rec_off, n_slots, K):
+        """(L, Y) of lcp_resolve and the index's T (u32[nS + 1]), U (u32), V (i32), rec_off (u64[n_rec + 1], n_slots its last
+        word) -> (P u64[n_slots], Q u8[n_slots], cnt u32[n_rec * (K + 1)]) DeviceArrays (zk_scan_place)"""
+        nS, n_rec = T.n - 1, rec_off.n - 1
+        assert U.n == V.n and T.dtype.itemsize == 4 and U.dtype.itemsize == 4 and V.dtype.itemsize == 4 and rec_off.dtype.itemsize == 8
+        P, Q, cnt = self.empty(n_slots, np.uint64), self.empty(n_slots, np.uint8), self.empty(n_rec * (int(K) + 1), np.uint32)
+        self._check(self.lib.zk_scan_place(self.h, L.ptr, Y.ptr, nS, T.ptr, U.ptr, V.ptr, U.n, rec_off.ptr, n_rec, int(K), P.ptr, Q.ptr, cnt.ptr))
+        return P, Q, cnt
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
