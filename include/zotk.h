@@ -198,6 +198,7 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_LCP_RESOLVE 32  /* zk_lcp_resolve: every launch of the call as one record (lcp_scan.hip; bytes = 48 per index k-mer + 12 per
                                    k-mer and doubling round; the searches in the sample are not in the figure) */
 #define ZK_PROF_SCAN_PLACE 33   /* zk_scan_place: the offer pass and the gather (8 B per entry, 17 B per slot); the check before them is not in it */
+#define ZK_PROF_SEQ_TALLY 34    /* zk_sequence_tally: the tile kernel (seq_tally.hip; bytes = the text read); the one-wave state kernel is not in it */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -598,6 +599,27 @@ int zk_lcp_resolve(zk_ctx* ctx, const uint64_t* d_S, uint64_t nS, const uint64_t
 int zk_scan_place(zk_ctx* ctx, const uint8_t* d_L, const uint64_t* d_Y, uint64_t nS, const uint32_t* d_T, const uint32_t* d_U,
                   const int32_t* d_V, uint64_t n_entries, const uint64_t* d_rec_off, uint64_t n_rec, int K, uint64_t* d_P, uint8_t* d_Q,
                   uint32_t* d_cnt);
+
+/* ---- `zot hgvs-index -T`: how often the genome holds the k-mers of a bait table (seq_tally.hip) --------------------------------
+ * zotmer/commands/hgvs-find.py:884-891 for one piece of one sequence: `for x in kmers(K, seq): if x in counts: counts[x] += 1`
+ * with seq the stripped, joined lines of a FASTA record (file.readFasta, file.py:19-36) and kmers the forward windows
+ * (basics.py:261-301).  d_text[0, n) is a piece of the record's body, cut anywhere; K is the table's.
+ *   - '\n' and '\r' are skipped; any other byte outside AaCcGgTtUu ends the current run of bases.  Every window of K
+ *     consecutive bases that equals key i of the table (the i-th of its ascending keys, zk_bait_table_arrays) adds 1 to
+ *     d_counts[i]: d_counts is ADDED TO, so that a caller sums over pieces and files.
+ *   - state (host, in / out; zeros before a record) = {the last min(run, K - 1) bases of the text so far, as a 2-bit value with
+ *     the last base lowest; that length}.  A text fed in pieces gives the counts and the final state of the text fed whole.
+ *   - *n_windows = the windows of K bases met (whether or not they are keys).  *first_gt = the least i with d_text[i] == '>'
+ *     and (i == 0 or d_text[i - 1] is '\n' or '\r'), else n: where a next record's header would start.  Counting does not stop
+ *     there; the caller decides what to feed.
+ *   - n == 0 or a table without keys: d_counts untouched, the state still advanced, ZK_OK.
+ *   - ZK_EINVAL: a null ctx, table, state, n_windows or first_gt; a null d_text with n > 0; a null d_counts with keys in the
+ *     table; state[1] > K - 1 (bits of state[0] above 2 * state[1] are ignored).
+ *   - A workgroup takes ZK_SEQTALLY_TILE text bytes; a window belongs to the tile that holds its last base.  Integer adds only:
+ *     the same call returns the same bits. */
+#define ZK_SEQTALLY_TILE 4096
+int zk_sequence_tally(zk_ctx* ctx, const zk_bait_table* table, const uint8_t* d_text, uint64_t n, uint64_t state[2], uint64_t* d_counts,
+                      uint64_t* n_windows, uint64_t* first_gt);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

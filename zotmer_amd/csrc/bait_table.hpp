@@ -26,9 +26,9 @@ static inline BaitView view_of(const zk_bait_table* t) {
     return v;
 }
 
-// x -> ids[lo, hi) of the key equal to x.  A miss costs the directory's two words (one line) and, in a non-empty
-// bucket, a search among its ~1-2 keys.
-__device__ __forceinline__ bool bait_find(const BaitView& t, u64 x, u32& lo, u32& hi) {
+// x -> the position i of the key equal to x (keys[i] == x).  A miss costs the directory's two words (one line) and, in a
+// non-empty bucket, a search among its ~1-2 keys.
+__device__ __forceinline__ bool bait_index(const BaitView& t, u64 x, u32& i) {
     if (t.n_keys == 0) return false;
     if (t.kbits < 64 && (x >> t.kbits) != 0) return false;
     const u64 bk = x >> t.shift;
@@ -36,8 +36,16 @@ __device__ __forceinline__ bool bait_find(const BaitView& t, u64 x, u32& lo, u32
     const u32 end = t.dir[bk + 1];
     u32 e = end;
     while (a < e) { const u32 mid = (a + e) >> 1; if (t.keys[mid] < x) a = mid + 1; else e = mid; }
-    if (a < end && t.keys[a] == x) { lo = t.offs[a]; hi = t.offs[a + 1]; return true; }
+    if (a < end && t.keys[a] == x) { i = a; return true; }
     return false;
+}
+
+// x -> ids[lo, hi) of the key equal to x
+__device__ __forceinline__ bool bait_find(const BaitView& t, u64 x, u32& lo, u32& hi) {
+    u32 i;
+    if (!bait_index(t, x, i)) return false;
+    lo = t.offs[i]; hi = t.offs[i + 1];
+    return true;
 }
 
 // capture.hip

@@ -31,6 +31,7 @@ NO_LINK = 0xFFFFFFFF                            # ZK_NO_LINK
 PILEUP_DIAGS, PILEUP_TILE = 256, 4096           # ZK_PILEUP_DIAGS, ZK_PILEUP_TILE
 PATH_TILE, PATH_CHUNK = 4096, 256               # ZK_PATH_TILE, ZK_PATH_CHUNK
 LCP_TILE = 256                                  # ZK_LCP_TILE
+SEQTALLY_TILE = 4096                            # ZK_SEQTALLY_TILE
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -189,6 +190,7 @@ SIGNATURES = {
     "zk_path_scan": (_i, [_vp, _vp, _vp, _vp, _u64, _i, C.POINTER(PathWindow), _u32, _vp, _vp, _u64, _pu64]),
     "zk_lcp_resolve": (_i, [_vp, _vp, _u64, _vp, _u64, _i, _vp, _vp]),
     "zk_scan_place": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _i, _vp, _vp, _vp]),
+    "zk_sequence_tally": (_i, [_vp, _vp, _vp, _u64, _pu64, _vp, _pu64, _pu64]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
     "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
@@ -458,7 +460,8 @@ class Context:
                  "union_sum": 7, "select": 8, "mirror": 9, "intersect": 10, "count_hist": 11, "pass_packed": 12, "sample": 13, "tile_sort": 14,
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
                  "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26,
-                 "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31, "lcp_resolve": 32, "scan_place": 33}
+                 "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31, "lcp_resolve": 32, "scan_place": 33,
+                 "seq_tally": 34}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -1150,6 +1153,18 @@ class Context:
         P, Q, cnt = self.empty(n_slots, np.uint64), self.empty(n_slots, np.uint8), self.empty(n_rec * (int(K) + 1), np.uint32)
         self._check(self.lib.zk_scan_place(self.h, L.ptr, Y.ptr, nS, T.ptr, U.ptr, V.ptr, U.n, rec_off.ptr, n_rec, int(K), P.ptr, Q.ptr, cnt.ptr))
         return P, Q, cnt
+
+    # ---- genome tally of `zot hgvs-index -T` (csrc/seq_tally.hip) -------------------------------------------------
+    def sequence_tally(self, table, text, state, counts, n=None):
+        """a piece of a FASTA record's body (uint8 DeviceArray, its first n bytes) -> counts[i] += the forward windows equal to
+        key i of the table (u64 DeviceArray [n_keys], added to).  state: (value, length) of the bases the text before ended
+        with, (0, 0) before a record -> (state after, windows met, first_gt: where a line starts with '>', else n)"""
+        n = text.n if n is None else int(n)
+        assert n <= text.n and counts.dtype.itemsize == 8 and counts.n >= table.n_keys
+        st = (C.c_uint64 * 2)(int(state[0]), int(state[1]))
+        nw, gt = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.zk_sequence_tally(self.h, table.h, text.ptr, n, st, counts.ptr, C.byref(nw), C.byref(gt)))
+        return (int(st[0]), int(st[1])), nw.value, gt.value
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
