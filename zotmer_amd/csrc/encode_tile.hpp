@@ -28,6 +28,14 @@ template <int T> struct TileImage {
     u32 valid[NCH];
 };
 
+// Record-aligned tiles (uniform records: stream_pass.hip's make_tiling, radix_sort.hip's record_tiles) give `cpr` threads to a
+// record: the record of thread t is t / cpr, taken as a multiply by inv = (u32)ceil(2^32 / cpr), exact for t < 2^16.  At cpr == 1
+// (records with no more windows than a thread takes) that inverse is 2^32 and does not fit its 32 bits -- it arrives as 0 -- so
+// the thread is its own record there.
+__device__ __forceinline__ u32 record_of_thread(u32 t, u32 cpr, u32 inv) {
+    return cpr == 1u ? t : (u32)(((u64)t * inv) >> 32);
+}
+
 // the 16 stream bytes at `off` (zero past the end), as four little-endian words
 __device__ __forceinline__ uint4 load_chunk16(const u8* __restrict__ stream, u64 n_bytes, u64 off) {
     uint4 q = make_uint4(0, 0, 0, 0);

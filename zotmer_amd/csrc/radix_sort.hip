@@ -65,7 +65,7 @@ struct SortArgs {
     // bytes (rec - 1 bases + the separator); a tile takes `rpt` records, a thread one of the `cpr` 16-window chunks of a
     // record, which has `wpr` windows.  Verified by the histogram kernel before it is used (see sort_stream).
     u32 rec, rpt, cpr, wpr;
-    u32 cpr_inv;        // ceil(2^32 / cpr): thread / cpr as a multiply (exact for thread < 2^16)
+    u32 cpr_inv;        // (u32)ceil(2^32 / cpr): thread / cpr as a multiply (record_of_thread, encode_tile.hpp; 0 at cpr == 1)
     // outputs
     u64* kout;
     u32* vout;
@@ -959,7 +959,7 @@ __global__ __launch_bounds__(C::BLOCK, C::WPE) void pass_pipe_kernel(SortArgs a,
                 // -- or spilled -- across the tile loop)
                 u32 p0 = 16u * tid_o, lim = 0xffffu;
                 if (a.rec) {
-                    const u32 r = (u32)(((u64)tid_o * a.cpr_inv) >> 32), j = tid_o - r * a.cpr;
+                    const u32 r = record_of_thread((u32)tid_o, a.cpr, a.cpr_inv), j = tid_o - r * a.cpr;
                     p0 = r * a.rec + 16u * j;
                     const int left = (int)a.wpr - 16 * (int)j;              // windows of the record from this chunk on
                     lim = (r < a.rpt) ? ((left >= 16) ? 0xffffu : ((1u << (left > 0 ? left : 0)) - 1u)) : 0u;

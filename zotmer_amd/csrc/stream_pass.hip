@@ -39,7 +39,7 @@ __host__ __device__ constexpr P0Geom p0_geom(bool wide) { return wide ? P0Geom{P
 struct StreamTiling {
     u32 rec;              // bytes per record (bases + separator) if the stream might consist of uniform records, else 0
     u32 rpt, cpr, wpr;    // records per tile, threads per record, windows per record
-    u32 cpr_inv;          // ceil(2^32 / cpr)
+    u32 cpr_inv;          // (u32)ceil(2^32 / cpr): 0 at cpr == 1 (record_of_thread, encode_tile.hpp)
     u32 tile_bytes;       // stream bytes per tile of the pass (rpt * rec, or P0_TILE positions)
     u32 ranges;
     u64 range_bytes;      // stream bytes per range: a whole number of tiles, a multiple of 16
@@ -501,7 +501,7 @@ __global__ __launch_bounds__(P0_BLOCK, 4) void stream_pass0_kernel(P0Args a) {
     // this thread's windows inside a tile: NW consecutive ones from tile position p0 on
     u32 p0 = (u32)NW * tid, wlim = (1u << NW) - 1u;          // wlim: which of them exist at all
     if (a.by_record) {
-        const u32 r = (u32)(((u64)tid * a.tl.cpr_inv) >> 32), j = tid - r * a.tl.cpr;
+        const u32 r = record_of_thread((u32)tid, a.tl.cpr, a.tl.cpr_inv), j = tid - r * a.tl.cpr;
         p0 = r * a.tl.rec + (u32)NW * j;
         const int left = (int)a.tl.wpr - NW * (int)j;
         wlim = (r < a.tl.rpt) ? ((left >= NW) ? (1u << NW) - 1u : ((1u << (left > 0 ? left : 0)) - 1u)) : 0u;
@@ -866,7 +866,7 @@ __global__ __launch_bounds__(PW_BLOCK) void stream_pass0_wide_kernel(P0Args a) {
     if (tid == 0) { sm.anybad = 0; sm.units[0] = 0; }
     u32 p0 = (u32)NW * tid, wlim = (1u << NW) - 1u;
     if (a.by_record) {
-        const u32 rr = (u32)(((u64)tid * a.tl.cpr_inv) >> 32), j = tid - rr * a.tl.cpr;
+        const u32 rr = record_of_thread((u32)tid, a.tl.cpr, a.tl.cpr_inv), j = tid - rr * a.tl.cpr;
         p0 = rr * a.tl.rec + (u32)NW * j;
         const int left = (int)a.tl.wpr - NW * (int)j;
         wlim = (rr < a.tl.rpt) ? ((left >= NW) ? (1u << NW) - 1u : ((1u << (left > 0 ? left : 0)) - 1u)) : 0u;
