@@ -148,7 +148,9 @@ int zk_upload_async(zk_ctx* ctx, void* d_dst, const void* src, uint64_t bytes);
                                   * mirror words sorted on 26 bits in three passes and merged with the counted list by the merge-path union; 2 = block
                                   * by block, the dedupe sorting its blocks (the route before the unsorted dedupe, for the A / B); 3 = tests: as 1,
                                   * but blocks declined by the union go straight to the last resort (the counted list sorted and copied densely,
-                                  * the merge-path union) */
+                                  * the merge-path union); 4 = as 1, but the mirror words are written by a kernel of their own that reads the counted
+                                  * list back, not by the dedupe beside its words (the route before that, for the A / B); 5 = tests: as 1, with room
+                                  * for 1024 mirror words only, so that the dedupe runs out of it and the kernel of 4 takes over */
 #define ZK_TUNE_COMM_SELF_LOOP 16 /* tests: 1 = the piece a rank keeps goes through grouped ncclSend / ncclRecv to itself, in the same rounds as
                                   * the other pieces (instead of a device copy), and zk_allreduce_u64 calls ncclAllReduce with one rank too:
                                   * the RCCL data path of zk_comm_* executed on a box with one GPU; 0 (default) */

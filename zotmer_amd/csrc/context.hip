@@ -347,7 +347,7 @@ int zk_tune(zk_ctx* c, int what, int value) {
     if (what == ZK_TUNE_TILE_SORT) { c->tile_sort = value ? 1 : 0; return ZK_OK; }
     if (what == ZK_TUNE_TAG_PASS) { c->tag_pass = value ? 1 : 0; return ZK_OK; }
     if (what == ZK_TUNE_DEDUPE_BITS) { c->dedupe_bits = value < 0 ? 0 : value; return ZK_OK; }
-    if (what == ZK_TUNE_STRAND_BLOCKS) { c->strand_blocks = value < 0 ? 0 : (value > 3 ? 1 : value); return ZK_OK; }
+    if (what == ZK_TUNE_STRAND_BLOCKS) { c->strand_blocks = value < 0 ? 0 : (value > 5 ? 1 : value); return ZK_OK; }
     if (what == ZK_TUNE_DEDUPE_LIMIT) { c->dedupe_limit = value < 1 ? 1 : (value > 65536 ? 65536 : value); return ZK_OK; }
     if (what == ZK_TUNE_STREAM_RANGES) { c->stream_ranges = value < 0 ? 0 : (value > 4096 ? 4096 : value); return ZK_OK; }
     if (what == ZK_TUNE_XCD_GROUP) {

@@ -16,7 +16,7 @@ struct DedupeArgs {
     u64* nwords;        // [chunks] words of block v
     int tag_bits;       // key bits below the block bits
     int pack;
-    u32* flags;         // |= 1: a table filled up, |= 2: some count went to the side list
+    u32* flags;         // |= 1: a table filled up, |= 2: some count went to the side list, |= 4: m_out is too small (see m_cap)
     u32* counter;       // the next block to take
     u64* big;           // (key, count) pairs whose count does not fit `pack` bits
     u32* n_big;
@@ -31,6 +31,13 @@ struct DedupeArgs {
     u32* n_retry;       // ... and how many; dedupe_kernel counts them afterwards, in its larger table with 32-bit counts
     u32 limit;          // ... blocks of this many keys or more are declined (<= 65 536)
     u64* dbg;           // or null (zk_debug_buffer + 8192 words): [workgroup][16] ticks per phase of a block, summed (tools/p0_phases.py)
+    // dedupe2_kernel, unsorted, the strand route (strand_blocks.hip): the mirror image of every word it writes, rc(key) << pack | count,
+    // densely and in no order -- a wave takes the place of its words from m_cursor with one add
+    u64* m_out;         // or null: not written
+    u64* m_cursor;      // words of m_out taken so far
+    u64 m_cap;          // words m_out holds: a wave whose words would pass it writes none of them and sets flags |= 4
+    u64* m_hist;        // [MAX_PASSES][MIRROR_RADIX] += the digit counts of the passes that will group the list (MirrorHist::raw)
+    int m_K, m_passes, m_shift[2], m_bits[2];          // ... at most two of them: bits [m_shift[p], m_shift[p] + m_bits[p]) of a mirror word
 };
 
 #ifdef ZK_PHASES          // make CXXFLAGS_EXTRA=-DZK_PHASES: the diagnostic build tools/p0_phases.py reads

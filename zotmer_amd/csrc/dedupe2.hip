@@ -12,6 +12,13 @@
 // -- 11 K entries in 76 KB, and while one workgroup of the CU sorts and writes its block the other one inserts.
 // UNSORTED (the strand route at odd K, strand_blocks.hip, which sorts every block again with its mirror image): the block's distinct
 // words are written compacted in table order instead -- no counting sort, no ranks (12.1 -> 9.4 ms at config 2, profiles/r08).
+// MIRROR (that route, 32-bit tags in): every word's mirror image, rc(k-mer) << pack | count, is written as well, from the registers
+// that hold the word -- densely into DedupeArgs::m_out, in no order the route needs: a block takes the place of its words with one add
+// on a global cursor, the waves theirs inside it from the LDS add that places the words themselves.  The digits of the two passes
+// that will group the list by block are counted in LDS for the life of the workgroup and added to m_hist at its end.  This takes the
+// place of strand_mirror_kernel, which read the counted list back to write the same words: 2.95 ms, for 1.76 ms more here (9.37 ->
+// 11.12 ms; 0.15 of it the two swaps in flight that make room for the digit counts; profiles/r21).  A list that does not fit m_cap
+// words sets flags |= 4 and the host falls back on that kernel; so it does for the blocks this kernel declines.
 #include "dedupe.hpp"
 #include <type_traits>
 
@@ -33,6 +40,13 @@ struct Dedupe2Smem {
     };
     u32 ticket;
     u32 nout;                             // UNSORTED: the block's entries written so far
+};
+// MIRROR: ... with the digit counts of the mirror words, kept for the life of the workgroup and added to DedupeArgs::m_hist at its end.
+// 4 KB more: beside four swaps in flight (77 832 bytes) that is 8 bytes more than two workgroups per CU have -- two swaps (75 788)
+template <int BLOCK_, int BATCH_, int ITEMS_>
+struct Dedupe2MirrorSmem : Dedupe2Smem<BLOCK_, BATCH_, ITEMS_> {
+    u32 bins[2][MIRROR_RADIX];
+    u64 mbase;                            // the block's place in DedupeArgs::m_out
 };
 
 // what a workgroup carries from one block to the next: the block it is about to count, with the first tile of its tags already
@@ -81,10 +95,10 @@ __device__ __forceinline__ void dedupe2_load(const DedupeArgs& a, u64 lo, u32 po
     }
 }
 
-template <int BLOCK, int BATCH, int ITEMS_, bool TAGIN, bool UNSORTED>
-__device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, Dedupe2Smem<BLOCK, BATCH, ITEMS_>& sm, Dedupe2Next<ITEMS_>& st, u32 (&ph)[8], u32& tlast) {
-    using S = Dedupe2Smem<BLOCK, BATCH, ITEMS_>;
-    constexpr int ITEMS = S::ITEMS, TILE = S::TILE, ALL = S::ALL, SPT = S::SPT, NB = S::NB;
+template <class S, bool TAGIN, bool UNSORTED, bool MIRROR>
+__device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, S& sm, Dedupe2Next<S::ITEMS>& st, u32 (&ph)[8], u32& tlast) {
+    constexpr int BLOCK = S::BLOCK, BATCH = S::BATCH, ITEMS = S::ITEMS, TILE = S::TILE, ALL = S::ALL, SPT = S::SPT, NB = S::NB;
+    static_assert(!MIRROR || UNSORTED, "the mirror words are written beside the unsorted ones");
     constexpr u32 EMPTY = ~0u;            // no entry; the all-ones tag has the last entry to itself (see `home`)
     constexpr u32 HS = ALL - 1;
     int tid = threadIdx.x;
@@ -203,7 +217,11 @@ __device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, Dedupe2Smem<B
         // ---- the block's entries in table order, compacted (the strand route sorts every block again: strand_blocks.hip) ------
         // thread t owns the entries t, t + BLOCK, ...; a wave counts what its lanes hold (one ballot per round), takes its share of
         // the block's words with one LDS add and writes them, every round a run of consecutive words
-        next_block(nchunk);          // the next block's first tile travels while this one is written
+        // MIRROR: the block takes the place of its mirror words in m_out with ONE add on the global cursor, once every wave's share is
+        // in nout (a barrier); the answer travels while the next block's bounds are fetched, and a second barrier hands it to the waves,
+        // whose words lie in m_out as they lie in the block.  (An add per wave needs neither barrier, but 2 M adds a step on one word
+        // that every XCD shares pass through one place: the step took 87-90 ms against 72-73.)
+        if constexpr (!MIRROR) next_block(nchunk);          // the next block's first tile travels while this one is written
         const u16* cnt16 = reinterpret_cast<const u16*>(sm.cnt);
         u32 wn = 0;
 #pragma unroll
@@ -211,6 +229,23 @@ __device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, Dedupe2Smem<B
         u32 wbase = 0;
         if (lane == 0 && wn) wbase = atomicAdd(&sm.nout, wn);
         wbase = (u32)__shfl((int)wbase, 0, 64);
+        u32 mrun = 0;          // the wave's mirror words written so far
+        u64* mp = nullptr;          // ... from here on; null: none are written
+        u64* op = nullptr;          // (MIRROR: the wave's words from here on, both places from the one count)
+        if constexpr (MIRROR) {
+            __syncthreads();
+            u64 g = 0;
+            if (tid == 0) g = atomicAdd(a.m_cursor, (u64)sm.nout);
+            next_block(nchunk);
+            if (tid == 0) sm.mbase = g;
+            __syncthreads();
+            const u64 mb = sm.mbase;
+            const u64 mbase = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(mb >> 32)) << 32) | (u64)(u32)__builtin_amdgcn_readfirstlane((int)mb);
+            const u32 wb = (u32)__builtin_amdgcn_readfirstlane((int)wbase);
+            op = a.out + lo + wb;
+            if (mbase + sm.nout <= a.m_cap) mp = a.m_out + mbase + wb;
+            else if (tid == 0) atomicOr(a.flags, 4u);          // m_out is too small: the host has strand_mirror_kernel write the list
+        }
         DD_PHASE(3);          // entries counted, the wave's words placed
         const u64 hi_part = (u64)chunk << a.tag_bits;
 #pragma unroll
@@ -224,9 +259,22 @@ __device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, Dedupe2Smem<B
                     if (at < a.big_cap) { a.big[2 * (u64)at] = k; a.big[2 * (u64)at + 1] = c; }
                     atomicOr(a.flags, 2u);
                 }
-                a.out[lo + wbase + popc_below(bal)] = (k << a.pack) | (u64)(c > maxc ? 0u : c);
+                const u64 cw = (u64)(c > maxc ? 0u : c);
+                if constexpr (MIRROR) op[mrun + popc_below(bal)] = (k << a.pack) | cw;
+                else a.out[lo + wbase + popc_below(bal)] = (k << a.pack) | cw;
+                if constexpr (MIRROR) {
+                    if (mp) {          // (the block's place + wbase + mrun + popc_below(bal) < the block's place + nout <= m_cap)
+                        const u64 mw = (revcomp(a.m_K, k) << a.pack) | cw;
+                        mp[mrun + popc_below(bal)] = mw;
+                        // the digits are the word's top bits: the second one is all there is above the first (one pass: 0, never read)
+                        const u32 top = (u32)(mw >> a.m_shift[0]);
+                        atomicAdd(&sm.bins[0][top & ((1u << a.m_bits[0]) - 1u)], 1u);
+                        atomicAdd(&sm.bins[1][(top >> a.m_bits[0]) & (MIRROR_RADIX - 1)], 1u);
+                    }
+                }
             }
-            wbase += (u32)__popcll(bal);
+            if constexpr (MIRROR) mrun += (u32)__popcll(bal);
+            else wbase += (u32)__popcll(bal);
         }
         __syncthreads();
         if (tid == 0) a.nwords[chunk] = sm.nout;          // (read before the caller's barrier; the next block clears it after)
@@ -336,12 +384,14 @@ __device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, Dedupe2Smem<B
 
 // Persistent: two workgroups per CU draw the blocks from a counter -- in order, not strided: the sizes go with the first bases, a
 // stride of the grid would give one workgroup all the big ones.
-template <int BLOCK, int BATCH, int ITEMS, bool TAGIN, bool UNSORTED>
+template <int BLOCK, int BATCH, int ITEMS, bool TAGIN, bool UNSORTED, bool MIRROR = false>
 __global__ __launch_bounds__(BLOCK, 2 * BLOCK / 256) void dedupe2_kernel(DedupeArgs a) {
-    using S = Dedupe2Smem<BLOCK, BATCH, ITEMS>;
+    using S = typename std::conditional<MIRROR, Dedupe2MirrorSmem<BLOCK, BATCH, ITEMS>, Dedupe2Smem<BLOCK, BATCH, ITEMS>>::type;
     __shared__ S sm;
     static_assert(sizeof(S) <= 80 * 1024, "two workgroups per CU");
     Dedupe2Next<ITEMS> st;
+    if constexpr (MIRROR)
+        for (int q = threadIdx.x; q < 2 * MIRROR_RADIX; q += BLOCK) (&sm.bins[0][0])[q] = 0;
     if (threadIdx.x == 0) sm.ticket = atomicAdd(a.counter, 1u);
     __syncthreads();
     st.chunk = (u32)__builtin_amdgcn_readfirstlane((int)sm.ticket);
@@ -359,10 +409,16 @@ __global__ __launch_bounds__(BLOCK, 2 * BLOCK / 256) void dedupe2_kernel(DedupeA
     (void)tlast;
     u32 nblk = 0;
     while (st.chunk < a.chunks) {
-        dedupe2_block<BLOCK, BATCH, ITEMS, TAGIN, UNSORTED>(a, sm, st, ph, tlast);          // leaves the next block in st
+        dedupe2_block<S, TAGIN, UNSORTED, MIRROR>(a, sm, st, ph, tlast);          // leaves the next block in st
         __syncthreads();          // the table and the ticket word are free again
         DD_PHASE(6);
         nblk++;
+    }
+    if constexpr (MIRROR) {          // (every wave's adds are behind the barrier above, or the one after the ticket)
+        for (int q = threadIdx.x; q < a.m_passes * MIRROR_RADIX; q += BLOCK) {
+            const u32 x = (&sm.bins[0][0])[q];
+            if (x) atomicAdd(&a.m_hist[q], (u64)x);
+        }
     }
     if (a.dbg && threadIdx.x == 0 && blockIdx.x < 256) {
         for (int k = 0; k < 8; k++) a.dbg[(u64)blockIdx.x * 16 + k] = ph[k];
@@ -370,12 +426,22 @@ __global__ __launch_bounds__(BLOCK, 2 * BLOCK / 256) void dedupe2_kernel(DedupeA
     }
 }
 
-// variant: bits 0-1 = compare-and-swaps in flight per thread (0: 4, 1: 1, 2: 2).  Tiles of 8 tags a thread; 16 (twice the bytes on
+// variant: bits 0-1 = compare-and-swaps in flight per thread (0: 4, 1: 1, 2: 2; with the mirror words 0: 2: 9.37 against 9.51 ms
+// without them, profiles/r21).  Tiles of 8 tags a thread; 16 (twice the bytes on
 // their way from memory): 14.5 against 12.6 ms.  (1024-thread workgroups, two to a CU, have 64 registers a thread: the entries a
 // thread holds while the block is sorted do not fit -- 25 to 40 spilled; not instantiated.)
 int launch_dedupe2(zk_ctx* c, const DedupeArgs& a, bool tagin, int variant, bool unsorted) {
     const u32 want = 2u * (u32)c->num_cus;
     const u32 grid = a.chunks < want ? a.chunks : want;
+    if (a.m_out) {
+        // the mirror words as well: tags in, unsorted, and (the digit counts' 4 KB of LDS) at most two swaps in flight
+        if (!tagin || !unsorted || !a.m_cursor || !a.m_hist || a.m_passes < 1 || a.m_passes > 2 || a.m_bits[0] > MIRROR_RBITS || a.m_bits[1] > MIRROR_RBITS)
+            return fail(c, ZK_EINTERNAL, "launch_dedupe2: mirror words with %d passes, tags %d, unsorted %d", a.m_passes, (int)tagin, (int)unsorted);
+        if ((variant & 3) == 1) hipLaunchKernelGGL((dedupe2_kernel<512, 1, 8, true, true, true>), dim3(grid), dim3(512), 0, c->stream, a);
+        else hipLaunchKernelGGL((dedupe2_kernel<512, 2, 8, true, true, true>), dim3(grid), dim3(512), 0, c->stream, a);
+        ZK_HIP(c, hipGetLastError());
+        return ZK_OK;
+    }
 #define ZK_DD2(N, T, U) hipLaunchKernelGGL((dedupe2_kernel<512, N, 8, T, U>), dim3(grid), dim3(512), 0, c->stream, a)
 #define ZK_DD2B(T, U) switch (variant & 3) { case 1: ZK_DD2(1, T, U); break; case 2: ZK_DD2(2, T, U); break; default: ZK_DD2(4, T, U); break; }
     if (unsorted) {

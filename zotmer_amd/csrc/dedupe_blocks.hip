@@ -417,7 +417,7 @@ constexpr u32 DEDUPE_BAD_CAP = 64;                // blocks whose table filled u
 // ---- dedupe_pass, stage 1: the lists (block starts, words per block, the side lists) and the kernels' arguments ----
 // The lists go to *r at once; r->unsorted says whether dedupe2_kernel may leave its blocks in table order.
 static int dedupe_lists(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int pack, u64* work, uint64_t max_chunks,
-                        const u32* tags, const u64* tag_cuts, bool unsorted, bool two_per_cu, DedupeArgs& a, DedupeResult* r) {
+                        const u32* tags, const u64* tag_cuts, bool unsorted, bool two_per_cu, const DedupeMirror* mirror, DedupeArgs& a, DedupeResult* r) {
     uint64_t chunks = 1ull << b;          // one block per value of the top bits
     if (max_chunks && chunks > max_chunks) chunks = max_chunks;
     u64 *cuts, *nwords, *incl, *big;
@@ -446,7 +446,21 @@ static int dedupe_lists(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, in
     unsorted = unsorted && two_per_cu;          // (dedupe_kernel's blocks leave it sorted)
     if (!max_chunks && !unsorted && a.tag_bits >= 14 && c->arena_size - c->arena_off > 64ull * chunks * (4 + 8 + 8) + (32ull << 20) + n / 16)
         ZK_TRY(arena_alloc(c, sizeof(u32) * 64 * chunks, (void**)&a.sub));
-    ZK_HIP(c, hipMemsetAsync(&c->d_scalars->dedupe_flags, 0, ZK_SPAN(dedupe_flags, dedupe_n_bad), c->stream));
+    // the strand route: dedupe2_kernel writes the mirror words too, and counts the digits of the passes that will group them by block
+    // (sort_keys_upper_counted) -- the plan depends on K and pack alone; more than two passes: strand_mirror_kernel as before
+    if (mirror && mirror->out && mirror->cap && unsorted && tags && !max_chunks && c->sort_variant == 3) {
+        const PassPlan plan = sort_plan_upper(c, key_bits + pack, key_bits + pack - b);
+        if (plan.passes <= 2) {
+            ZK_TRY(arena_alloc(c, sizeof(u64) * MAX_PASSES * MIRROR_RADIX, (void**)&a.m_hist));
+            ZK_HIP(c, hipMemsetAsync(a.m_hist, 0, sizeof(u64) * MAX_PASSES * MIRROR_RADIX, c->stream));
+            a.m_out = mirror->out; a.m_cap = mirror->cap; a.m_K = mirror->K; a.m_passes = plan.passes;
+            a.m_cursor = &c->d_scalars->dedupe_m_cursor;
+            r->mh.passes = plan.passes; r->mh.raw = a.m_hist;
+            for (int p = 0; p < plan.passes; p++) { a.m_shift[p] = r->mh.shift[p] = plan.shift[p]; a.m_bits[p] = r->mh.bits[p] = plan.bits[p]; }
+            r->m_words = a.m_out; r->m_cap = a.m_cap;
+        }
+    }
+    ZK_HIP(c, hipMemsetAsync(&c->d_scalars->dedupe_flags, 0, ZK_SPAN(dedupe_flags, dedupe_m_cursor), c->stream));
     r->cuts = cuts; r->nwords = nwords; r->incl = incl; r->big = big; r->chunks = (uint32_t)chunks; r->pack = pack; r->work = work;
     r->tag_bits = a.tag_bits; r->unsorted = unsorted;
     return ZK_OK;
@@ -461,7 +475,7 @@ static void launch_one_per_cu(zk_ctx* c, const DedupeArgs& d) {
 
 // ---- stage 2: the launch -- dedupe2_kernel with dedupe_kernel as the second chance of what it declines, or dedupe_kernel alone;
 // the five counters are in c->h_scalars afterwards
-static int dedupe_launch(zk_ctx* c, DedupeArgs& a, bool two_per_cu, bool unsorted) {
+static int dedupe_launch(zk_ctx* c, DedupeArgs& a, bool two_per_cu, bool unsorted, DedupeResult* r) {
     // algorithmic bytes: every key read once (a 32-bit tag, or the whole key), one word written per distinct key (added by
     // dedupe_pass, once the scan has said how many)
     prof_begin(c, ZK_PROF_RLE, (a.tin ? 4 : 8) * a.n);
@@ -473,9 +487,14 @@ static int dedupe_launch(zk_ctx* c, DedupeArgs& a, bool two_per_cu, bool unsorte
     } else launch_one_per_cu(c, a);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(fetch_span(c, &c->h_scalars->dedupe_flags, ZK_SPAN(dedupe_flags, dedupe_n_bad)));
+    ZK_TRY(fetch_span(c, &c->h_scalars->dedupe_flags, ZK_SPAN(dedupe_flags, dedupe_m_cursor)));
     ZK_TRY(fetch(c, &c->h_scalars->dedupe_n_in, a.cuts + a.chunks));
     ZK_TRY(check_device_error(c));
+    if (two_per_cu) { r->retry = a.retry; r->n_retry = (uint32_t)c->h_scalars->dedupe_n_retry; }
+    if (a.m_out) {
+        r->m_placed = c->h_scalars->dedupe_m_cursor;
+        r->m_emitted = !((uint32_t)c->h_scalars->dedupe_flags & 4u) && r->m_placed <= a.m_cap;
+    }
     if (two_per_cu && (uint32_t)c->h_scalars->dedupe_n_retry) {
         // the blocks dedupe2_kernel declined (65 536 keys or more; a table that filled up): dedupe_kernel's table is larger and its
         // counts are 32 bits wide -- what it declines too goes on the list the host counts by sorting
@@ -484,7 +503,7 @@ static int dedupe_launch(zk_ctx* c, DedupeArgs& a, bool two_per_cu, bool unsorte
         ZK_HIP(c, hipMemsetAsync(a.counter, 0, sizeof(u32), c->stream));
         launch_one_per_cu(c, d);
         ZK_HIP(c, hipGetLastError());
-        ZK_TRY(fetch_span(c, &c->h_scalars->dedupe_flags, ZK_SPAN(dedupe_flags, dedupe_n_bad)));
+        ZK_TRY(fetch_span(c, &c->h_scalars->dedupe_flags, ZK_SPAN(dedupe_flags, dedupe_m_cursor)));
         ZK_TRY(check_device_error(c));
     }
     return ZK_OK;
@@ -525,7 +544,7 @@ static int dedupe_bad_blocks(zk_ctx* c, const DedupeArgs& a, uint32_t n_bad, Ded
 //                 max_chunks > 0: only the leading blocks (the sample; *n_in = the keys they cover).
 //   dedupe_finish moves the words together and apart into out_k / out_c (r.n_out entries each).
 int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int pack, u64* work, uint64_t cap, DedupeResult* r,
-                uint64_t* n_in, uint64_t max_chunks, const u32* tags, const u64* tag_cuts, bool unsorted) {
+                uint64_t* n_in, uint64_t max_chunks, const u32* tags, const u64* tag_cuts, bool unsorted, const DedupeMirror* mirror) {
     *r = DedupeResult();
     if (n_in) *n_in = n;
     if (n == 0) return ZK_OK;
@@ -533,8 +552,8 @@ int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int
     if (cap < n) return fail(c, ZK_ENOSPC, "dedupe_pass: work buffer of %llu words for %llu keys", (unsigned long long)cap, (unsigned long long)n);
     DedupeArgs a = {};
     const bool two_per_cu = key_bits - b <= 32 && c->dedupe_variant >= 0;
-    ZK_TRY(dedupe_lists(c, keys, n, key_bits, b, pack, work, max_chunks, tags, tag_cuts, unsorted, two_per_cu, a, r));
-    ZK_TRY(dedupe_launch(c, a, two_per_cu, r->unsorted));
+    ZK_TRY(dedupe_lists(c, keys, n, key_bits, b, pack, work, max_chunks, tags, tag_cuts, unsorted, two_per_cu, mirror, a, r));
+    ZK_TRY(dedupe_launch(c, a, two_per_cu, r->unsorted, r));
     r->flags = (uint32_t)c->h_scalars->dedupe_flags;
     r->n_big = (uint32_t)c->h_scalars->dedupe_n_big;
     if (r->n_big > DEDUPE_BIG_CAP) r->flags |= 1;          // more counts beyond the field than the side list holds: the long way
@@ -549,7 +568,7 @@ int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int
     ZK_TRY(fetch(c, &c->h_scalars->dedupe_n_out, r->incl + r->chunks - 1));
     ZK_TRY(stream_sync(c));
     r->n_out = c->h_scalars->dedupe_n_out;
-    prof_add_bytes(c, ZK_PROF_RLE, 8 * r->n_out);          // one word written per distinct key
+    prof_add_bytes(c, ZK_PROF_RLE, 8 * r->n_out);          // one word written per distinct key (its mirror image: booked by strand_blocks)
     r->sub = a.sub;
     if (n_in) *n_in = c->h_scalars->dedupe_n_in;          // keys covered by the blocks that were counted
     return ZK_OK;

@@ -25,8 +25,9 @@ struct zk_scalars {
     u64 n_keys;              // hist_scan_kernel: live keys of a sort
     u64 rec_info[3];         // first_newline_kernel + the stream histogram: first newline, newlines, bad bytes (one pointer)
     u64 sample_n;            // (u32) StreamSample: keys set aside; cleared together with rec_info
-    // -- adjacent: dedupe_pass clears and reads back [dedupe_flags .. dedupe_n_bad] as one range --
+    // -- adjacent: dedupe_pass clears and reads back [dedupe_flags .. dedupe_m_cursor] as one range --
     u64 dedupe_flags, dedupe_n_retry, dedupe_counter, dedupe_n_big, dedupe_n_bad;   // (u32 each) DedupeArgs
+    u64 dedupe_m_cursor;     // DedupeArgs::m_cursor: mirror words placed (dedupe2_kernel, then strand_mirror_kernel over the declined blocks)
     // -- no order below this line --
     u64 dedupe_n_in;         // landing: cuts[chunks]
     u64 dedupe_n_out;        // landing: incl[chunks - 1]
@@ -72,7 +73,7 @@ struct zk_scalars {
 };
 // bytes of the fields first .. last (declared in that order, adjacent)
 #define ZK_SPAN(first, last) (offsetof(zk_scalars, last) + sizeof(zk_scalars::last) - offsetof(zk_scalars, first))
-static_assert(sizeof(zk_scalars) == 81 * sizeof(u64), "zk_scalars: u64 words only, no padding");
+static_assert(sizeof(zk_scalars) == 82 * sizeof(u64), "zk_scalars: u64 words only, no padding");
 static_assert(ZK_SPAN(rle_side, total) == 2 * sizeof(u64), "rle_prefix reads rle_side and total back as one range");
 static_assert(ZK_SPAN(total, acgt) == 5 * sizeof(u64), "the merges read total and acgt back as one range");
 static_assert(ZK_SPAN(acgt, n_keys) == 5 * sizeof(u64) && ZK_SPAN(acgt, sample_n) == 9 * sizeof(u64),
@@ -81,7 +82,7 @@ static_assert(ZK_SPAN(rec_info, sample_n) == 4 * sizeof(u64), "sort_stream clear
 static_assert(offsetof(zk_scalars, dedupe_n_retry) == offsetof(zk_scalars, dedupe_flags) + 8 &&
               offsetof(zk_scalars, dedupe_counter) == offsetof(zk_scalars, dedupe_flags) + 16 &&
               offsetof(zk_scalars, dedupe_n_big) == offsetof(zk_scalars, dedupe_flags) + 24 &&
-              ZK_SPAN(dedupe_flags, dedupe_n_bad) == 5 * sizeof(u64), "dedupe_pass clears and reads its five words as one range");
+              ZK_SPAN(dedupe_flags, dedupe_m_cursor) == 6 * sizeof(u64), "dedupe_pass clears and reads its six words as one range");
 
 struct zk_ctx {
     int device = 0;
@@ -116,7 +117,9 @@ struct zk_ctx {
     int tile_sort = 1;         // sorts of keys that do not repeat: LSD passes over the top bits, then tiles sorted to the end in LDS (tilesort.hip)
     int dedupe_bits = 0;       // tests: > 0 = the block dedupe with this many block bits whatever the input's size (pipeline.hip)
     int strand_blocks = 1;     // zk_kmerize, block dedupe at odd K: both strands rebuilt block by block (strand_blocks.hip); 0 = mirror sort + merge-path union;
-                               // 2 = block by block from sorted dedupe blocks (the route before the unsorted dedupe); 3 = tests: as 1, declined blocks go to the merge-path union
+                               // 2 = block by block from sorted dedupe blocks (the route before the unsorted dedupe); 3 = tests: as 1, declined blocks go to the merge-path union;
+                               // 4 = as 1, the mirror words written by strand_mirror_kernel instead of the dedupe (the route before the fused form);
+                               // 5 = tests: as 1, room for 1024 mirror words only (the dedupe runs out of it: strand_mirror_kernel after all)
     int stream_ranges = 0;     // ... ranges the stream is cut into (0 = one per CU for variant 1, two for 2 and 3; tests use a few so that a range has many tiles)
 
     // workspace arena: a bump allocator reset at the start of every API call
@@ -269,9 +272,12 @@ struct MirrorHist { int passes; int shift[4]; int bits[4]; u64* raw; };         
 // ... and the sort that takes them (dedupe_finish; default geometry only)
 int sort_keys_upper_counted(zk_ctx* c, u64* keys, u64* alt, uint64_t n, int key_bits, int lo_bit, u64* counted, u64** result);
 // dedupe_blocks.hip
+// where dedupe2_kernel may write the mirror image of its words (the strand route, strand_blocks.hip): cap words at out, K bases a key
+struct DedupeMirror { u64* out = nullptr; uint64_t cap = 0; int K = 0; };
 struct DedupeResult {
     uint64_t n_out = 0;          // distinct keys
-    uint32_t flags = 0;          // bit 0: a table filled up (unusable), bit 1: counts beyond the packed field exist (patched by dedupe_finish)
+    uint32_t flags = 0;          // bit 0: a table filled up (unusable), bit 1: counts beyond the packed field exist (patched by dedupe_finish),
+                                 // bit 2: the mirror words did not fit their room (m_emitted is false)
     uint32_t n_big = 0;
     u64 *cuts = nullptr, *nwords = nullptr, *incl = nullptr, *big = nullptr, *work = nullptr;
     u32* sub = nullptr;          // [chunks][64] or null: how a block's entries split on the 6 bits after the block bits
@@ -279,11 +285,20 @@ struct DedupeResult {
     int pack = 0;
     int tag_bits = 0;            // key bits below the block bits
     bool unsorted = false;       // the blocks dedupe2_kernel counted are in table order (dedupe_sort_blocks sorts them)
+    // the mirror words rc(key) << pack | count of the blocks dedupe2_kernel counted: m_placed of them at m_words, densely, in no order,
+    // their digit counts added to mh.raw.  The blocks it declined (retry[0 .. n_retry)) are still missing: strand_mirror_kernel's
+    bool m_emitted = false;
+    u64* m_words = nullptr;
+    uint64_t m_cap = 0, m_placed = 0;
+    MirrorHist mh = {};
+    u32* retry = nullptr;
+    uint32_t n_retry = 0;
 };
 // unsorted: dedupe2_kernel leaves its blocks in table order (the strand route sorts every block again; nobody else may read them so)
+// mirror (unsorted, tags, no sample): ... and writes their mirror words there, if the passes over them are at most two
 int dedupe_pass(zk_ctx* c, const u64* keys, uint64_t n, int key_bits, int b, int pack, u64* work, uint64_t cap, DedupeResult* r,
                 uint64_t* n_in = nullptr, uint64_t max_chunks = 0, const u32* tags = nullptr, const u64* tag_cuts = nullptr,
-                bool unsorted = false);
+                bool unsorted = false, const DedupeMirror* mirror = nullptr);
 // the keys back from their tags: key = (block number << tag_bits) | tag
 int expand_tags(zk_ctx* c, const u32* tags, const u64* cuts, uint32_t blocks, int tag_bits, u64* keys_out, uint64_t first_block = 0, uint64_t n_blocks = 0);
 // packed_out: out_k takes the words themselves, (key << pack) | count, and out_c is not written (the caller merges them as they are)

@@ -376,7 +376,7 @@ static KmerizePlan plan_kmerize(const zk_ctx* c, uint64_t n_bytes, int K, bool b
     p.look = !p.dedupe_bit && !both && c->early_collapse && !pack_bits_for(K) && p.tile_top && p.look_bits < 2 * K;
     p.blocks_mirror = !canonical_only && p.pack && p.dedupe_bit == MIRROR_GROUP_BITS && mirror_groups(K);
     p.blocks_strands = p.blocks_mirror && (K & 1) && c->strand_blocks;
-    p.blocks_unsorted = p.blocks_mirror && (K & 1) && (c->strand_blocks == 1 || c->strand_blocks == 3);
+    p.blocks_unsorted = p.blocks_mirror && (K & 1) && (c->strand_blocks == 1 || c->strand_blocks >= 3);
     return p;
 }
 
@@ -535,7 +535,15 @@ static int count_blocks(zk_ctx* c, const KmerizePlan& p, const SortBufs& b, cons
     const u32* tg = s.tags.written ? (const u32*)s.keys : nullptr;
     if (!s.presampled) ZK_TRY(dedupe_pass(c, s.keys, s.n, 2 * K, p.dedupe_bit, pk, s.other, b.cap_keys, &d, &n_in, (1u << 20) / per + 4, tg, s.tags.cuts));
     if (s.presampled || (!(d.flags & 1) && (double)d.n_out <= REPEAT_RATIO * (double)n_in)) {
-        ZK_TRY(dedupe_pass(c, s.keys, s.n, 2 * K, p.dedupe_bit, pk, s.other, b.cap_keys, &d, nullptr, 0, tg, s.tags.cuts, p.blocks_unsorted));
+        // the strand route: the dedupe writes the mirror words too, behind the tags it reads (they take the first 4 n bytes of the keys'
+        // buffer; whole keys leave no room) -- strand_blocks then finds them there
+        DedupeMirror mo;
+        const uint64_t tag_words = align256(4 * s.n) / 8;
+        if (tg && p.blocks_strands && p.blocks_unsorted && c->strand_blocks != 4 && tag_words < b.cap_keys) {
+            mo.out = s.keys + tag_words; mo.cap = b.cap_keys - tag_words; mo.K = K;
+            if (c->strand_blocks == 5 && mo.cap > 1024) mo.cap = 1024;
+        }
+        ZK_TRY(dedupe_pass(c, s.keys, s.n, 2 * K, p.dedupe_bit, pk, s.other, b.cap_keys, &d, nullptr, 0, tg, s.tags.cuts, p.blocks_unsorted, &mo));
         if (!(d.flags & 1)) {
             const uint64_t uc = r->uc = d.n_out;
             // Every count fits the field (the usual case) and both strands are wanted: the copy that closes the gaps also

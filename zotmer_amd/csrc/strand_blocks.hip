@@ -10,8 +10,11 @@
 //     place(b) = (entries of C before block b) + (entries of M before block b).
 //
 // So M needs no more than grouping by its top 18 bits, and the union needs no merge path:
-//   1. strand_mirror_kernel: M written densely, rc(k-mer) << pack | count at the canonical word's own index (whole lines), the digit
-//      counts of the two passes below taken on the way;
+//   1. M written densely, rc(k-mer) << pack | count, in no order at all, with the digit counts of the two passes below: by the dedupe
+//      itself beside its words (dedupe2.hip, MIRROR; DedupeResult::m_emitted), this step then only adds the blocks the dedupe declined
+//      (strand_mirror_kernel over their list, the words' places from the same cursor) and checks that every word has its mirror image.
+//      Else -- whole keys instead of tags, a plan of more than two passes, no room, ZK_TUNE_STRAND_BLOCKS 4 -- strand_mirror_kernel
+//      reads the whole list back and writes M at the canonical word's own index (whole lines);
 //   2. two passes of the key kernel over M's top 18 key bits (sort_keys_upper_counted): M grouped by block;
 //   3. strand_starts_kernel: where every block of M starts (a binary search per block);
 //   4. strand_block_union_kernel: one workgroup per block reads C_b (in place, where the dedupe wrote it) and M_b, sorts the two in
@@ -20,6 +23,8 @@
 //
 // Buffers: C's gapped words stay in the dedupe's work buffer until the union has read them; M and the ping-pong buffer of its passes
 // (2 x 8 U bytes for U distinct canonical k-mers) are the first and second half of the keys' buffer, which the dedupe has finished with.
+// The dedupe's own M lies behind the tags it read (the first 4 n bytes of that buffer); the second buffer is then the start of the
+// buffer, or the room behind M.
 //
 // A block of more entries than a tile holds (low-complexity sequence, genomes whose 9-base prefixes are far from uniform), or one
 // whose entries crowd a few groups, is declined onto a list, and strand_big_block_kernel takes the listed blocks alone: 256 splitters
@@ -37,20 +42,31 @@ constexpr u32 SB_GROUP_MAX = 128;                         // a group of more ent
 typedef TileSortSmem<SB_ITEMS, SB_GROUPS, false> StrandSmem;
 constexpr int SB_BLOCK_BITS = 18;
 
-// block v's words w -> out_m[incl[v] - nwords[v] + i] = rc(w >> pack) << pack | (w & count mask), with the digit counts of mh
+// block v's words w -> out_m[incl[v] - nwords[v] + i] = rc(w >> pack) << pack | (w & count mask), with the digit counts of mh.
+// list (or null): only the blocks list[0 .. chunks), the ones dedupe2_kernel declined and so wrote no mirror words for; a block takes
+// the place of its words behind the dedupe's from the same cursor (m_cap: the words out_m holds; no block is written across it)
 __global__ __launch_bounds__(256) void strand_mirror_kernel(const u64* __restrict__ in, const u64* __restrict__ cuts, const u64* __restrict__ incl,
                                                             const u64* __restrict__ nwords, u32 chunks, int pack, int K, u64* __restrict__ out_m,
-                                                            MirrorHist mh) {
+                                                            MirrorHist mh, const u32* __restrict__ list, u64* cursor, u64 m_cap) {
     __shared__ u32 bins[4 * 512];
+    __shared__ u64 placed;
     const bool hist = mh.passes > 0;
     if (hist) {
         for (int q = threadIdx.x; q < 4 * 512; q += blockDim.x) bins[q] = 0;
         __syncthreads();
     }
     const u64 maxc = (1ull << pack) - 1;
-    for (u32 v = blockIdx.x; v < chunks; v += gridDim.x) {
+    for (u32 t = blockIdx.x; t < chunks; t += gridDim.x) {
+        const u32 v = list ? list[t] : t;
         const u64 cnt = nwords[v];
-        const u64 dst0 = incl[v] - cnt;
+        u64 dst0 = incl[v] - cnt;
+        if (list) {
+            if (threadIdx.x == 0) placed = atomicAdd(cursor, cnt);
+            __syncthreads();
+            dst0 = placed;
+            __syncthreads();          // (the word is free for the next block)
+            if (dst0 + cnt > m_cap) continue;
+        }
         const u64* src = in + cuts[v];
         for (u64 i0 = threadIdx.x; i0 < cnt; i0 += 4ull * blockDim.x) {
             u64 w4[4];
@@ -325,21 +341,54 @@ int strand_blocks(zk_ctx* c, const DedupeResult& r, u64* keys_buf, uint64_t buf_
     const int pk = r.pack, key_bits = 2 * K + pk, lo_bit = key_bits - SB_BLOCK_BITS;
     u64* mw = keys_buf;
     u64* malt = keys_buf + a8w;
-    // 1. M, densely, with the digit counts of its passes
+    // 1. M, densely, with the digit counts of its passes.  The dedupe has written it (all but the blocks it declined), if there is room for
+    // the passes' second buffer before or behind it and the digits it counted are the ones the passes will take
     MirrorHist mh = {};
-    if (c->sort_variant == 3) {
+    bool fused = r.m_emitted && r.m_words >= keys_buf && r.m_words + r.m_cap <= keys_buf + buf_words && uc <= r.m_cap && c->sort_variant == 3;
+    if (fused) {
         const PassPlan plan = sort_plan_upper(c, key_bits, lo_bit);
-        if (plan.passes <= 4) {
-            ZK_TRY(arena_alloc(c, sizeof(u64) * MAX_PASSES * 512, (void**)&mh.raw));
-            ZK_HIP(c, hipMemsetAsync(mh.raw, 0, sizeof(u64) * MAX_PASSES * 512, c->stream));
-            mh.passes = plan.passes;
-            for (int p = 0; p < plan.passes; p++) { mh.shift[p] = plan.shift[p]; mh.bits[p] = plan.bits[p]; }
-        }
+        fused = plan.passes == r.mh.passes;
+        for (int p = 0; fused && p < plan.passes; p++) fused = plan.shift[p] == r.mh.shift[p] && plan.bits[p] == r.mh.bits[p];
+        const uint64_t before = (uint64_t)(r.m_words - keys_buf), behind = buf_words - before;
+        if (before < a8w && behind < 2 * a8w) fused = false;
+        if (fused) malt = before >= a8w ? keys_buf : r.m_words + a8w;
     }
-    prof_begin(c, ZK_PROF_SELECT, 16 * uc);
-    hipLaunchKernelGGL(strand_mirror_kernel, dim3((u32)c->num_cus * 8), dim3(256), 0, c->stream, r.work, r.cuts, r.incl, r.nwords, r.chunks, pk, K, mw, mh);
-    prof_end(c);
-    ZK_HIP(c, hipGetLastError());
+    if (fused) {
+        mw = r.m_words;
+        mh = r.mh;
+        uint64_t placed = r.m_placed;
+        // (the step's record and its algorithmic bytes are the same whoever writes the words: a step's records add up alike on either form)
+        prof_begin(c, ZK_PROF_SELECT, 16 * uc);
+        if (r.n_retry) {
+            // the blocks the dedupe declined (65 536 keys or more, a table that filled up: counted by dedupe_kernel or the host since)
+            hipLaunchKernelGGL(strand_mirror_kernel, dim3(grid_cap(c, r.n_retry, 8)), dim3(256), 0, c->stream, r.work, r.cuts, r.incl, r.nwords, r.n_retry, pk, K,
+                               mw, mh, r.retry, &c->d_scalars->dedupe_m_cursor, (u64)r.m_cap);
+        }
+        prof_end(c);
+        if (r.n_retry) {
+            ZK_HIP(c, hipGetLastError());
+            ZK_TRY(fetch(c, &c->h_scalars->dedupe_m_cursor));
+            ZK_TRY(stream_sync(c));
+            placed = c->h_scalars->dedupe_m_cursor;
+        }
+        // (the passes scatter by the digit counts: they must be the counts of exactly the uc words that are there)
+        if (placed != uc) return fail(c, ZK_EINTERNAL, "strand_blocks: %llu mirror words for %llu entries", (unsigned long long)placed, (unsigned long long)uc);
+    } else {
+        if (c->sort_variant == 3) {
+            const PassPlan plan = sort_plan_upper(c, key_bits, lo_bit);
+            if (plan.passes <= 4) {
+                ZK_TRY(arena_alloc(c, sizeof(u64) * MAX_PASSES * 512, (void**)&mh.raw));
+                ZK_HIP(c, hipMemsetAsync(mh.raw, 0, sizeof(u64) * MAX_PASSES * 512, c->stream));
+                mh.passes = plan.passes;
+                for (int p = 0; p < plan.passes; p++) { mh.shift[p] = plan.shift[p]; mh.bits[p] = plan.bits[p]; }
+            }
+        }
+        prof_begin(c, ZK_PROF_SELECT, 16 * uc);
+        hipLaunchKernelGGL(strand_mirror_kernel, dim3((u32)c->num_cus * 8), dim3(256), 0, c->stream, r.work, r.cuts, r.incl, r.nwords, r.chunks, pk, K, mw, mh,
+                           (const u32*)nullptr, (u64*)nullptr, (u64)0);
+        prof_end(c);
+        ZK_HIP(c, hipGetLastError());
+    }
     // 2. grouped by its top 18 key bits
     u64* sk = nullptr;
     if (mh.passes) ZK_TRY(sort_keys_upper_counted(c, mw, malt, uc, key_bits, lo_bit, mh.raw, &sk));
