@@ -675,7 +675,9 @@ int zk_kmerize(zk_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, int K, in
  * (commands/kmerize.py:490; library/reads.py:113-114).  zk_kmerize(flags) == zk_mirror_expand(zk_kmerize(flags |
  * ZK_KMERIZE_CANONICAL_ONLY)).
  * ZK_ENOSPC when the table (2 n entries less the palindromes) exceeds cap: nothing is written at or beyond index cap of d_kmers
- * or d_counts, *n_out = the length needed, and the call may be repeated with room. */
+ * or d_counts, *n_out = the length needed, and the call may be repeated with room.
+ * ZK_EOVERFLOW when the n + n of a palindrome does not fit 32 bits (n >= 2^31; the reference's array('I') raises OverflowError
+ * there): no wrapped count is handed out as a result, the contents of d_kmers / d_counts are unspecified, and the ctx stays usable. */
 int zk_mirror_expand(zk_ctx* ctx, const uint64_t* d_canon_kmers, const uint32_t* d_canon_counts, uint64_t n, int K,
                      uint64_t* d_kmers, uint32_t* d_counts, uint64_t cap, uint64_t* n_out);
 
