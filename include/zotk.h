@@ -47,6 +47,7 @@
  *         zk_capture_kmers        d_text1, d_text2                  any address
  *         zk_format_pairs         d_out                             any address
  *         zk_contig_render        d_out                             any address
+ *         zk_spike_pairs          d_text, d_heads, d_out1, d_out2   any address
  *         zk_copy                 d_dst, d_src                      any address, any byte count
  *     An entry writes only the elements [0, result length) of its outputs and never more than [0, cap) -- nothing in front of the
  *     pointer, nothing behind the result but what the capacity convention below allows (the work space of zk_capture_hits and of
@@ -201,6 +202,8 @@ int zk_tune(zk_ctx* ctx, int what, int value);
                                    k-mer and doubling round; the searches in the sample are not in the figure) */
 #define ZK_PROF_SCAN_PLACE 33   /* zk_scan_place: the offer pass and the gather (8 B per entry, 17 B per slot); the check before them is not in it */
 #define ZK_PROF_SEQ_TALLY 34    /* zk_sequence_tally: the tile kernel (seq_tally.hip; bytes = the text read); the one-wave state kernel is not in it */
+#define ZK_PROF_SPIKE_PAIRS 35  /* zk_spike_pairs: the write pass, one wave per pair (spikein.hip; bytes = the two texts written) */
+#define ZK_PROF_SPIKE_SIZE 36   /* zk_spike_pairs: the size pass and the two scans behind it as one record (bytes = 16 per pair) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -622,6 +625,43 @@ int zk_scan_place(zk_ctx* ctx, const uint8_t* d_L, const uint64_t* d_Y, uint64_t
 #define ZK_SEQTALLY_TILE 4096
 int zk_sequence_tally(zk_ctx* ctx, const zk_bait_table* table, const uint8_t* d_text, uint64_t n, uint64_t state[2], uint64_t* d_counts,
                       uint64_t* n_windows, uint64_t* first_gt);
+
+/* ---- `zot spikein`: simulated read pairs with variants (spikein.hip) ------------------------------------------------------------
+ * zotmer/commands/spikein.py:380-394 and :267-317 with the draws of zotmer_amd/synth.py: rnd(seed, tag, index), integers only.
+ *
+ * zk_spike_zone_counts: draw n of [first, first + count) falls into the first zone z with d_cum[z] > rnd(seed, 16, n) % T, where
+ * d_cum[0 .. n_zones) are the inclusive cumulative zone lengths (ascending) and T = d_cum[n_zones - 1]; d_counts[z] (u64) is
+ * ADDED TO, so a caller may cut the draws into calls.  count == 0: nothing is touched.  ZK_EINVAL: n_zones == 0 or a null array
+ * with count > 0, T == 0, count >= 2^40.  Integer adds only: the same call returns the same bits.
+ *
+ * zk_spike_pairs: the FASTQ records of the pairs [first, first + count), mate 1 to d_out1 and mate 2 to d_out2, in pair order.
+ *   - Pair p belongs to the zone z with d_first[z] <= p < d_first[z + 1] (d_first: n_zones + 1 ascending pair numbers; a zone
+ *     may be empty).  d_zones holds 12 words a zone, 6 for the wild type and then 6 for the mutant: {offset of the allele's
+ *     window in d_text, first allele coordinate of the window, its length, G = the allele's length, s0, e0} (the coordinates
+ *     signed).  The windows are raw bytes, any case, any character.  The header prefix `ch:st-en nm ` of zone z is
+ *     d_heads[d_head_offs[z], d_head_offs[z + 1]).
+ *   - The pair is a mutant when the low 32 bits of rnd(seed, 17, p) are below thr_v (thresholds are fractions of 2^32, at most
+ *     2^32 = always); u = s0 + rnd(seed, 18, p) % (e0 - s0 + 1); fl = max(I + ((sd_q * z) >> 32), L + L / 2) with z the sum of
+ *     the twelve 16-bit fields of rnd(seed, 19, 3 p + k), k = 0, 1, 2, less 6 * 65535, and the shift arithmetic; u - fl < 0
+ *     gives u = fl, then u + fl > G gives u = G - fl; bit 0 of rnd(seed, 20, p) set is strand '-', the reverse complement of
+ *     allele[u, u + fl), bases upper-cased first and only ACGT complemented.  Mate 1 is the fragment's first L bases, mate 2
+ *     its last L.  Base j of mate m is replaced when the low 32 bits of r = rnd(seed, 21, (2 p + m) L + j) are below thr_e: by
+ *     element (r >> 32) % 3 of the other three of ACGT, or by 'ACGT'[(r >> 32) % 4] where it is none of them.
+ *   - The record: '@' prefix u ' ' fl ' ' strand ' ' errors '\n' read '\n' '+' '\n' 'I' * L '\n', the errors `j c > d` (j
+ *     decimal, c the upper-cased base before) joined by ';'.
+ *   - n_bytes[0], n_bytes[1] = the bytes of the two texts.  ZK_ENOSPC when either exceeds its capacity: both needed sizes are
+ *     in n_bytes, nothing is written beyond [0, cap) of either output, the call may be repeated with room; cap 0 sizes.
+ *   - ZK_EINVAL, with nothing written to the outputs: a pair that no zone holds, a fragment that leaves its window, a window
+ *     outside d_text or outside [0, G], e0 < s0, header offsets out of order (all found by the size pass); L outside
+ *     1 .. 2^20, I outside 1 .. 2^40 - 1, sd_q outside 0 .. 2^43 - 1, a threshold above 2^32, first or count >= 2^40.
+ *   - count == 0 writes nothing.  No atomics: the same call returns the same bytes, and a run cut at any pair numbers into
+ *     several calls returns the bytes of one call.  Workspace: 16 bytes per pair. */
+int zk_spike_zone_counts(zk_ctx* ctx, const uint64_t* d_cum, uint64_t n_zones, uint64_t seed, uint64_t first, uint64_t count,
+                         uint64_t* d_counts);
+int zk_spike_pairs(zk_ctx* ctx, const uint8_t* d_text, uint64_t n_text, const uint64_t* d_zones, const uint64_t* d_first, uint64_t n_zones,
+                   const uint8_t* d_heads, const uint64_t* d_head_offs, uint64_t n_heads, uint64_t seed, int L, int64_t I, int64_t sd_q,
+                   uint64_t thr_v, uint64_t thr_e, uint64_t first, uint64_t count, uint8_t* d_out1, uint64_t cap1, uint8_t* d_out2,
+                   uint64_t cap2, uint64_t n_bytes[2]);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

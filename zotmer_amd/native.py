@@ -191,6 +191,9 @@ SIGNATURES = {
     "zk_lcp_resolve": (_i, [_vp, _vp, _u64, _vp, _u64, _i, _vp, _vp]),
     "zk_scan_place": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _i, _vp, _vp, _vp]),
     "zk_sequence_tally": (_i, [_vp, _vp, _vp, _u64, _pu64, _vp, _pu64, _pu64]),
+    "zk_spike_zone_counts": (_i, [_vp, _vp, _u64, _u64, _u64, _u64, _vp]),
+    "zk_spike_pairs": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _u64, _i, C.c_int64, C.c_int64, _u64, _u64, _u64, _u64,
+                            _vp, _u64, _vp, _u64, _pu64]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
     "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
@@ -461,7 +464,7 @@ class Context:
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
                  "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26,
                  "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31, "lcp_resolve": 32, "scan_place": 33,
-                 "seq_tally": 34}
+                 "seq_tally": 34, "spike_pairs": 35, "spike_size": 36}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -1165,6 +1168,39 @@ class Context:
         nw, gt = C.c_uint64(0), C.c_uint64(0)
         self._check(self.lib.zk_sequence_tally(self.h, table.h, text.ptr, n, st, counts.ptr, C.byref(nw), C.byref(gt)))
         return (int(st[0]), int(st[1])), nw.value, gt.value
+
+    # ---- simulated read pairs of `zot spikein` (csrc/spikein.hip) ---------------------------------------------------
+    def spike_zone_counts(self, cum, seed, first, count, counts):
+        """the zone draws [first, first + count) added to counts (u64 DeviceArray, one per zone); cum: the inclusive cumulative
+        zone lengths (u64 DeviceArray)"""
+        assert cum.dtype.itemsize == 8 and counts.dtype.itemsize == 8 and counts.n >= cum.n
+        self._check(self.lib.zk_spike_zone_counts(self.h, cum.ptr, cum.n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(count), counts.ptr))
+
+    def spike_pairs_into(self, text, zones, first_pair, heads, head_offs, seed, L, I, sd_q, thr_v, thr_e, first, count, out1, out2):
+        """zk_spike_pairs into the two uint8 arrays given -> ((bytes of mate 1, bytes of mate 2) written or, if they did not fit,
+        needed; whether they fit).  zones: u64[12 * n_zones], first_pair and head_offs: u64[n_zones + 1]."""
+        nz = first_pair.n - 1
+        assert zones.n == 12 * nz and head_offs.n == nz + 1 and zones.dtype.itemsize == 8 and first_pair.dtype.itemsize == 8
+        assert head_offs.dtype.itemsize == 8 and text.dtype.itemsize == 1 and heads.dtype.itemsize == 1
+        nb = (C.c_uint64 * 2)(0, 0)
+        rc = self.lib.zk_spike_pairs(self.h, text.ptr, text.n, zones.ptr, first_pair.ptr, nz, heads.ptr, head_offs.ptr, heads.n,
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(L), int(I), int(sd_q), int(thr_v), int(thr_e), int(first), int(count),
+                                     out1.ptr, out1.n, out2.ptr, out2.n, nb)
+        if rc != ZK_ENOSPC:
+            self._check(rc)
+        return (int(nb[0]), int(nb[1])), rc == ZK_OK
+
+    def spike_pairs(self, text, zones, first_pair, heads, head_offs, seed, L, I, sd_q, thr_v, thr_e, first, count, out=None):
+        """-> (mate 1 text, mate 2 text) as uint8 DeviceArray views.  out: (out1, out2) buffers to write into first; grown when
+        too small."""
+        o1, o2 = out if out is not None else (self.empty(0, np.uint8), self.empty(0, np.uint8))
+        args = (text, zones, first_pair, heads, head_offs, seed, L, I, sd_q, thr_v, thr_e, first, count)
+        nb, fit = self.spike_pairs_into(*args, o1, o2)
+        if not fit:
+            o1, o2 = self.empty(nb[0], np.uint8), self.empty(nb[1], np.uint8)
+            nb, fit = self.spike_pairs_into(*args, o1, o2)
+            assert fit
+        return o1.view(nb[0]), o2.view(nb[1])
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)

@@ -149,3 +149,54 @@ CONFIGS = {
     "config2": dict(reads=50_000_000, L=150, K=25, genome=100_000_000, sub=0.005, n=0.0005),
     "config5": dict(reads=300_000_000, L=150, K=31, genome=3_100_000_000, sub=0.005, n=0.0005),
 }
+
+
+# ---- simulated read pairs (`zot spikein`); the HIP version is csrc/spikein.hip -------------------------------
+# Integer-only from end to end, on Python ints, so that the host, the tests' restatement and the device agree bit for bit.
+# Every draw of pair p is rnd(seed, tag, index); pairs are numbered in output order, so a run cut into any number of device
+# calls gives the same bytes.
+T_ZONE, T_ALLELE, T_POS, T_LEN, T_STRAND, T_ERR = 16, 17, 18, 19, 20, 21      # the device's draws
+T_ANON, T_POP = 22, 23                                                         # the host's: insN / delinsN bases, the -m lottery
+_MASK64 = 0xFFFFFFFFFFFFFFFF
+IH_MAX = 6 * 65535            # |z| of spike_len_z never exceeds it
+
+
+def mix64_int(z):
+    z = (z + 0x9E3779B97F4A7C15) & _MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return z ^ (z >> 31)
+
+
+def rnd_int(seed, tag, i):
+    """rnd(seed, tag, i) on Python ints"""
+    return mix64_int((mix64_int((int(seed) + int(tag)) & _MASK64) + int(i)) & _MASK64)
+
+
+def spike_sd_q(I, D):
+    """the standard deviation I * D of the fragment length in units of 2^-16, as the device takes it"""
+    return int(round(I * D * 65536))
+
+
+def spike_len_z(seed, p):
+    """Irwin-Hall: twelve 16-bit fields of three draws, less their mean: mean 0, standard deviation 2^16 (to 1e-9)"""
+    z = -IH_MAX
+    for k in range(3):
+        r = rnd_int(seed, T_LEN, 3 * p + k)
+        z += (r & 0xFFFF) + ((r >> 16) & 0xFFFF) + ((r >> 32) & 0xFFFF) + (r >> 48)
+    return z
+
+
+def spike_frag_len(seed, p, I, sd_q, L):
+    """fl = max(I + floor(sd_q * z / 2^32), L + L // 2)"""
+    return max(I + ((sd_q * spike_len_z(seed, p)) >> 32), L + L // 2)
+
+
+def spike_flmax(I, sd_q, L):
+    return max(L + L // 2, I + ((sd_q * IH_MAX) >> 32))
+
+
+def spike_zone_of(seed, n, cum):
+    """the zone of draw n: rnd(seed, T_ZONE, n) % T looked up in the inclusive cumulative zone lengths"""
+    import bisect
+    return bisect.bisect_right(cum, rnd_int(seed, T_ZONE, n) % cum[-1])
