@@ -306,7 +306,7 @@ def test_render_a_contig_across_many_workgroups(ctx):
 
 def test_render_start_indices_of_one_to_seven_digits(ctx):
     K, xs = million()
-    starts = [0, 7, 42, 777, 1234, 54321, 654321, 1000002, 999999, 100000, 99999, 10, 9]
+    starts = [0, 7, 42, 777, 1234, 54321, 654321, 1000002, 999999, 100000, 99999, 10, 9, 99, 100, 999, 1000, 9999, 10000]
     paths = [[s] + [(s * 31 + j) % len(xs) for j in range(1, 1 + i % 4)] for i, s in enumerate(starts)]
     text = render(ctx, K, xs, paths)
     assert text == R.text_of(K, xs.tolist(), paths)

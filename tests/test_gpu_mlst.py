@@ -241,6 +241,23 @@ def test_empty_table_no_records_and_no_entries(ctx, big):
     assert native.ZK_OK == 0
 
 
+@pytest.mark.parametrize("K", [12, 32])
+def test_a_table_of_one_key(ctx, K):
+    """the directory at its smallest (two buckets, one key): entries below the key, equal to it and above it, at both ends of the
+    key range, and -- below K = 32 -- entries with bits above the 2K of a k-mer, which no bucket answers for"""
+    top = (1 << (2 * K)) - 1
+    for key in (0, 1, 0x5A5A5A, top >> 1, (top >> 1) + 1, top - 1, top):
+        t = Arrays(K, [key], [np.array([1])], 3).table(ctx)
+        assert (t.n_keys, t.n_ids) == (1, 1)
+        others = {0, 1, key - 1, key + 1, top >> 1, (top >> 1) + 1, top - 1, top} - {key, -1, top + 1}
+        if K < 32:
+            others |= {key | (1 << (2 * K)), key | (1 << 63), (1 << 64) - 1}
+        for x in sorted(others):
+            assert tally(ctx, t, [x]).tolist() == [0, 0, 0], (key, x)
+        assert tally(ctx, t, [key]).tolist() == [0, 1, 0], key
+        assert tally(ctx, t, sorted(others | {key})).tolist() == [0, 1, 0], key
+
+
 def test_same_call_same_bits_and_a_fresh_context(ctx, big):
     from zotmer_amd import native
     arr, table = big

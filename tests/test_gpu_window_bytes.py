@@ -466,6 +466,97 @@ def test_strip_capture_gather(ctx):
     assert first_pair.tolist() == [0, n] and first_byte.tolist() == [0, len(want)]
 
 
+# ---- sequence lines around the 64-window step of the one-wave-per-read walk -----------------------------------------------------------
+
+WALK_K = 25
+
+
+@functools.lru_cache(maxsize=None)
+def walk_case():
+    """FASTQ records whose sequence lines are K - 1, K, K + 1, 62 + K .. 65 + K, 127 + K and 128 + K letters long: no window, one, two;
+    the last window in lanes 62 and 63 of the first step, the first windows of the second step; and the same one step on
+    -> (text, the sequence lines)"""
+    K = WALK_K
+    lens = [K - 1, K, K + 1, 62 + K, 63 + K, 64 + K, 65 + K, 127 + K, 128 + K]
+    seqs = [W.base_run(n, 900 + n) for n in lens]
+    assert [len(W.windows(s, K)) for s in seqs] == [0, 1, 2, 63, 64, 65, 66, 128, 129]
+    text = b"".join(b"CATG\n" + s + b"\nTTG\n" + b"G" * len(s) + b"\n" for s in seqs)
+    return text, seqs
+
+
+def walk_table(seqs, pad=0):
+    """the LAST window of every line as a key: record (anchor) pad + the line's number"""
+    K = WALK_K
+    last = [(W.windows(s, K)[-1][1], pad + r) for r, s in enumerate(seqs) if len(s) >= K]
+    return W.table_arrays([x for x, _ in last], [r for _, r in last])
+
+
+def test_walk_lengths_capture_and_pulldown_hits(ctx):
+    K = WALK_K
+    text, seqs = walk_case()
+    table = walk_table(seqs)
+    d = ctx.upload_stream(text)
+    lines = ctx.line_ends(d)
+    n = len(seqs)
+    want = np.array(sorted((r << 32) | r for r in range(1, n)), dtype=U64)          # every line but the short one hits its own record
+    t = table_on_device(ctx, K, table, n)
+    veto = table_on_device(ctx, K, W.table_arrays([W.windows(seqs[5], K)[-1][1]], [0]), 1)    # the window in lane 0 of the second step
+    try:
+        assert np.array_equal(ctx.capture_hits(t, K, d, lines, n).to_host(), want)
+        assert np.array_equal(ctx.capture_hits(t, K, d, lines, n, d, lines).to_host(), want)
+        gp, gh, gv = ctx.pulldown_hits(t, K, d, lines, n)
+        assert np.array_equal(gp.to_host(), want) and gh[0] == 1 and gh[1] == n - 1 and gv == 0
+        assert np.array_equal(ctx.capture_hits(t, K, d, lines, n, veto=veto).to_host(), want[want != U64((5 << 32) | 5)])
+        gp, gh, gv = ctx.pulldown_hits(t, K, d, lines, n, veto=veto)
+        assert gv == 1 and gh[1] == n - 2
+    finally:
+        t.free()
+        veto.free()
+
+
+def test_walk_lengths_strand_keys(ctx):
+    K = WALK_K
+    text, seqs = walk_case()
+    d = ctx.upload_stream(text)
+    lines = ctx.line_ends(d)
+    for reverse in (0, 1):
+        want = W.tagged_keys(K, seqs, reverse)
+        out = ctx.empty(len(want) + 64, np.uint64)
+        n, fit = ctx.strand_keys(d, lines, len(seqs), K, reverse, (1 << (2 * K)) - 1, out)
+        assert fit and n == len(want) == 518
+        assert np.array_equal(np.sort(out.to_host()[:n]), want), reverse
+
+
+def test_walk_lengths_capture_kmers(ctx):
+    K = WALK_K
+    text, seqs = walk_case()
+    d = ctx.upload_stream(text)
+    lines = ctx.line_ends(d)
+    n = len(seqs)
+    pairs = (U64(3) << U64(32)) | np.arange(n, dtype=U64)
+    want = np.concatenate([W.kmers_both(s, K) for s in seqs])
+    for mates, reps in (((), 1), ((d, lines), 2)):
+        ob, ok = ctx.capture_kmers(ctx.upload(pairs), d, lines, n, K, *mates)
+        assert ob.n == reps * len(want) and np.all(ob.to_host() == 3)
+        assert np.array_equal(np.sort(ok.to_host()), np.sort(np.tile(want, reps)))
+
+
+def test_walk_lengths_anchor_pileup(ctx):
+    K, pad = WALK_K, 256
+    text, seqs = walk_case()
+    table = walk_table(seqs, pad)
+    want = pileup_want(K, table, seqs)
+    assert len(want) == 518                      # one diagonal per line, from its last window, in the forward list only
+    d = ctx.upload_stream(text)
+    lines = ctx.line_ends(d)
+    t = table_on_device(ctx, K, table, 3 * pad)
+    try:
+        oc, ok = ctx.anchor_pileup(t, d, lines, len(seqs), K, pad)
+        assert sorted(zip(oc.to_host().tolist(), ok.to_host().tolist())) == want
+    finally:
+        t.free()
+
+
 # ---- stream ends and surroundings ----------------------------------------------------------------------------------------------------------------
 
 def lengths(K, tiles):

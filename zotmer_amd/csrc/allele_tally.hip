@@ -72,8 +72,7 @@ __global__ void table_check_kernel(const u64* __restrict__ keys, u64 n_keys, int
             // ids[i - 1] < ids[i] unless i is where a list starts: some offs[p] == i.  Rules 3-5 make offs ascend; where they are
             // broken the answer is not used (a smaller rule number wins)
             if (i > 0 && ids[i - 1] >= ids[i]) {
-                u64 lo = 0, hi = n_keys + 1;
-                while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (offs[mid] < i) lo = mid + 1; else hi = mid; }
+                const u64 lo = lower_bound(offs, 0ull, n_keys + 1, i);
                 if (!(lo <= n_keys && offs[lo] == i)) b = TV_ID_ORDER;
             }
             if (ids[i] >= n_records) b = TV_ID_RANGE;

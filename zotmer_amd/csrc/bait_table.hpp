@@ -1,7 +1,9 @@
-// bait_table.hpp -- the table behind the opaque zk_bait_table of the C-ABI, shared by the files that build it (capture.hip,
-// allele_tally.hip) and the kernels that look k-mers up in it.
+// bait_table.hpp -- the table behind the opaque zk_bait_table of the C-ABI: sorted keys, CSR offsets into record ids, and a
+// key directory (search.hpp) over the top key bits.
+// Built by capture.hip (from bait text) and allele_tally.hip (from arrays); k-mers are looked up in it by capture.hip,
+// pulldown.hip (through capture_lookup), allele_tally.hip, pileup.hip and seq_tally.hip.
 #pragma once
-#include "internal.hpp"
+#include "search.hpp"
 
 // device memory of its own, outlives the calls
 struct zk_bait_table {
@@ -16,13 +18,11 @@ struct zk_bait_table {
 
 namespace zk {
 
-struct BaitView {
-    const u64* keys; const u32* offs; const u32* ids; const u32* dir; u64 n_keys; int kbits, shift;
-};
+struct BaitView { const u64* keys; const u32* offs; const u32* ids; KeyDir dir; u64 n_keys; int kbits; };
 
 static inline BaitView view_of(const zk_bait_table* t) {
-    BaitView v{nullptr, nullptr, nullptr, nullptr, 0, 64, 0};
-    if (t && t->n_keys) v = BaitView{t->keys, t->offs, t->ids, t->dir, t->n_keys, t->kbits, t->kbits - t->bits};
+    BaitView v{nullptr, nullptr, nullptr, KeyDir{nullptr, 0}, 0, 64};
+    if (t && t->n_keys) v = BaitView{t->keys, t->offs, t->ids, KeyDir{t->dir, t->kbits - t->bits}, t->n_keys, t->kbits};
     return v;
 }
 
@@ -31,11 +31,9 @@ static inline BaitView view_of(const zk_bait_table* t) {
 __device__ __forceinline__ bool bait_index(const BaitView& t, u64 x, u32& i) {
     if (t.n_keys == 0) return false;
     if (t.kbits < 64 && (x >> t.kbits) != 0) return false;
-    const u64 bk = x >> t.shift;
-    u32 a = t.dir[bk];
-    const u32 end = t.dir[bk + 1];
-    u32 e = end;
-    while (a < e) { const u32 mid = (a + e) >> 1; if (t.keys[mid] < x) a = mid + 1; else e = mid; }
+    u32 a, end;
+    dir_bucket(t.dir, x, a, end);
+    a = lower_bound(t.keys, a, end, x);
     if (a < end && t.keys[a] == x) { i = a; return true; }
     return false;
 }

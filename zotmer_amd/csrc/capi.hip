@@ -2,6 +2,7 @@
 // small kernels that belong to no other file: read packing, synthetic reads, checksums.
 #include "internal.hpp"
 #include "encode_tile.hpp"
+#include "search.hpp"
 
 namespace zk {
 int kmerize(zk_ctx* c, const u8* stream, uint64_t n_bytes, int K, int flags, double p, uint64_t seed, u64* out_k, u32* out_c,
@@ -121,10 +122,7 @@ __global__ __launch_bounds__(CS_BLOCK) void stream_checksum_kernel(const u8* __r
 __global__ void lower_bound_kernel(const u64* __restrict__ a, u64 n, const u64* __restrict__ q, u32 m, u64* __restrict__ pos) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= m) return;
-    const u64 x = q[t];
-    u64 lo = 0, hi = n;
-    while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (a[mid] < x) lo = mid + 1; else hi = mid; }
-    pos[t] = lo;
+    pos[t] = lower_bound(a, 0ull, n, q[t]);
 }
 
 }  // namespace zk

@@ -18,73 +18,38 @@ namespace zk {
 
 
 // ---------------------------------------------------------------------------------------
-// predicates
+// predicates (compact.hpp: NewlinePos and the run heads)
 // ---------------------------------------------------------------------------------------
-
-struct NewlinePos {      // positions of the '\n' bytes
-    const u8* text; u64* out;
-    __device__ bool flag(u64 i) const { return text[i] == '\n'; }
-    __device__ void store(u64 pos, u64 i) const { out[pos] = i; }
-};
 
 // item i = window at position i >> 1 of the bait stream, strand i & 1 (basics.kmersList(K, seq, True): x then rc x)
 struct BaitWindow {
     const u8* stream; u64 n; int K; const u64* ends; u64 n_ends; u64* keys; u32* ids;
-    __device__ bool window(u64 pos, u64& x, u64& xb) const {
-        if (pos + K > n) return false;
-        x = 0; xb = 0;
-        for (int j = 0; j < K; j++) {
-            u32 ok;
-            const u32 b = base_code(stream[pos + j], ok);
-            if (!ok) return false;
-            x = (x << 2) | b;
-            xb |= (u64)(3u - b) << (2 * j);
-        }
-        return true;
-    }
-    __device__ bool flag(u64 i) const { u64 x, xb; return window(i >> 1, x, xb); }
+    __device__ bool flag(u64 i) const { u64 x, xb; return point_window(stream, n, K, i >> 1, x, xb); }
     __device__ void store(u64 pos, u64 i) const {
         u64 x, xb;
-        window(i >> 1, x, xb);
+        point_window(stream, n, K, i >> 1, x, xb);
         keys[pos] = (i & 1) ? xb : x;
-        u64 lo = 0, hi = n_ends;           // record = number of terminators before the window
-        while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (ends[mid] < (i >> 1)) lo = mid + 1; else hi = mid; }
-        ids[pos] = (u32)lo;
+        ids[pos] = record_of(ends, n_ends, i >> 1);
     }
 };
 
-struct DistinctPairs {   // first of each run of equal (key, id) in a key-sorted, id-stable array
-    const u64* k; const u32* v; u64* ok; u32* ov;
-    __device__ bool flag(u64 i) const { return i == 0 || k[i] != k[i - 1] || v[i] != v[i - 1]; }
+struct DistinctPairs : PairRunHead {   // (key, id) runs of a key-sorted, id-stable array -> (key, id)
+    u64* ok; u32* ov;
     __device__ void store(u64 pos, u64 i) const { ok[pos] = k[i]; ov[pos] = v[i]; }
 };
-
-struct DistinctKeys {    // first of each run of equal keys -> (key, CSR offset)
-    const u64* k; u64* ok; u32* offs;
-    __device__ bool flag(u64 i) const { return i == 0 || k[i] != k[i - 1]; }
+struct DistinctKeys : KeyRunHead {     // key runs -> (key, CSR offset)
+    u64* ok; u32* offs;
     __device__ void store(u64 pos, u64 i) const { ok[pos] = k[i]; offs[pos] = (u32)i; }
 };
-
-struct DistinctWords {   // first of each run of equal words
-    const u64* k; u64* out;
-    __device__ bool flag(u64 i) const { return i == 0 || k[i] != k[i - 1]; }
+struct DistinctWords : KeyRunHead {    // word runs -> the word
+    u64* out;
     __device__ void store(u64 pos, u64 i) const { out[pos] = k[i]; }
 };
 
 // ---------------------------------------------------------------------------------------
 // the table
 // ---------------------------------------------------------------------------------------
-// (the table itself, its view and the lookup: bait_table.hpp)
-
-__global__ void dir_kernel(const u64* __restrict__ keys, u64 n_keys, int shift, u64 nb, u32* __restrict__ dir) {
-    for (u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x; b <= nb; b += (u64)gridDim.x * blockDim.x) {
-        if (b == nb) { dir[b] = (u32)n_keys; continue; }
-        const u64 q = b << shift;
-        u64 lo = 0, hi = n_keys;
-        while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (keys[mid] < q) lo = mid + 1; else hi = mid; }
-        dir[b] = (u32)lo;
-    }
-}
+// (the table itself, its view and the lookup: bait_table.hpp; the directory: search.hpp)
 
 __global__ void put_u32_kernel(u32* p, u32 v) { *p = v; }
 
@@ -112,8 +77,7 @@ int bait_table_directory(zk_ctx* c, zk_bait_table* t) {
     t->bits = bits;
     const u64 nb = 1ull << bits;
     ZK_TRY(tmalloc(c, (void**)&t->dir, 4 * (nb + 1)));
-    hipLaunchKernelGGL(dir_kernel, dim3(grid_cap(c, div_up(nb + 1, 256), 16)), dim3(256), 0, c->stream, t->keys, (u64)t->n_keys, t->kbits - bits, nb, t->dir);
-    ZK_HIP(c, hipGetLastError());
+    ZK_TRY(key_dir_build(c, t->keys, (u64)t->n_keys, t->kbits - bits, nb, t->dir));
     ZK_HIP(c, hipStreamSynchronize(c->stream));
     return check_device_error(c);
 }
@@ -145,13 +109,13 @@ static int bait_table_build(zk_ctx* c, const u8* stream, uint64_t n, int K, zk_b
     if (nw) ZK_TRY(sort_pairs(c, keys, alt, ids, valt, nw, 2 * K, &rk, &rv));
     u64* k2 = (rk == keys) ? alt : keys;
     uint64_t n_ids = 0;
-    DistinctPairs dp{rk, rv, k2, nullptr};
+    DistinctPairs dp{{rk, rv}, k2, nullptr};
     ZK_TRY(compact_count(c, dp, nw, &cnt, &n_ids));
     ZK_TRY(tmalloc(c, (void**)&t->ids, 4 * n_ids));
     dp.ov = t->ids;
     ZK_TRY(compact_write(c, dp, nw, cnt));
     uint64_t n_keys = 0;
-    DistinctKeys dk{k2, nullptr, nullptr};
+    DistinctKeys dk{{k2}, nullptr, nullptr};
     ZK_TRY(compact_count(c, dk, n_ids, &cnt, &n_keys));
     ZK_TRY(tmalloc(c, (void**)&t->keys, 8 * n_keys));
     ZK_TRY(tmalloc(c, (void**)&t->offs, 4 * (n_keys + 1)));
@@ -167,57 +131,38 @@ static int bait_table_build(zk_ctx* c, const u8* stream, uint64_t n, int K, zk_b
 // window lookup: one wave per read
 // ---------------------------------------------------------------------------------------
 
-__device__ __forceinline__ u32 wave_min_u32(u32 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const u32 t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
-    return v;
-}
-
 // MARK: lane 0 of a wave whose read is vetoed says so in mark[r] (zk_pulldown_hits counts those reads and keeps them out of its
 // histogram); zk_capture_hits runs the instantiation without it
 template <bool MARK>
 __global__ __launch_bounds__(256) void capture_hits_kernel(BaitView bt, BaitView vt, int RK, Mate m1, Mate m2, u64 n_reads,
                                                            u64* __restrict__ pairs, u64 cap, u64* n_raw, u8* __restrict__ mark) {
-    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    const u64 nw = ((u64)gridDim.x * blockDim.x) >> 6;
-    const int mates = m2.text ? 2 : 1;
-    for (u64 r = wave; r < n_reads; r += nw) {
-        if (vt.n_keys) {      // a read with any window in the veto set is not captured
-            bool veto = false;
-            for (int m = 0; m < mates && !veto; m++) {
-                const Mate mt = m ? m2 : m1;
-                const u64 b = mt.lines[4 * r] + 1, e = mt.lines[4 * r + 1];
-                for (u64 c0 = b; c0 < e && !veto; c0 += 64) {
-                    u64 x; u32 lo, hi;
-                    const bool hit = chunk_window(mt.text, c0, e, RK, lane, x) && bait_find(vt, x, lo, hi);
-                    veto = __ballot(hit) != 0;
-                }
-            }
-            if (veto) {
-                if (MARK && lane == 0) mark[r] = 1;
-                continue;
-            }
+    const WaveIds w = wave_ids();
+    const int lane = w.lane;
+    for (u64 r = w.wave; r < n_reads; r += w.nw) {
+        // a read with any window in the veto set is not captured
+        const bool veto = vt.n_keys && for_each_mate_chunk(m1, m2, r, RK, lane, [&](u64, bool valid, u64 x) {
+            u32 lo, hi;
+            return __ballot(valid && bait_find(vt, x, lo, hi)) != 0;
+        });
+        if (veto) {
+            if (MARK && lane == 0) mark[r] = 1;
+            continue;
         }
-        for (int m = 0; m < mates; m++) {
-            const Mate mt = m ? m2 : m1;
-            const u64 b = mt.lines[4 * r] + 1, e = mt.lines[4 * r + 1];
-            for (u64 c0 = b; c0 < e; c0 += 64) {
-                u64 x;
-                u32 p = 0, pe = 0;
-                if (!(chunk_window(mt.text, c0, e, RK, lane, x) && bait_find(bt, x, p, pe))) p = pe = 0;
-                // the distinct ids of the chunk, smallest first: each lane's list ascends, the wave takes the minimum of the heads
-                while (__ballot(p < pe)) {
-                    const u32 my = p < pe ? bt.ids[p] : 0xffffffffu;
-                    const u32 mn = wave_min_u32(my);
-                    if (lane == 0) {
-                        const u64 q = atomicAdd(n_raw, 1ull);
-                        if (q < cap) pairs[q] = ((u64)mn << 32) | r;
-                    }
-                    if (p < pe && my == mn) p++;
+        for_each_mate_chunk(m1, m2, r, RK, lane, [&](u64, bool valid, u64 x) {
+            u32 p = 0, pe = 0;
+            if (!(valid && bait_find(bt, x, p, pe))) p = pe = 0;
+            // the distinct ids of the chunk, smallest first: each lane's list ascends, the wave takes the minimum of the heads
+            while (__ballot(p < pe)) {
+                const u32 my = p < pe ? bt.ids[p] : 0xffffffffu;
+                const u32 mn = wave_min_u32(my);
+                if (lane == 0) {
+                    const u64 q = atomicAdd(n_raw, 1ull);
+                    if (q < cap) pairs[q] = ((u64)mn << 32) | r;
                 }
+                if (p < pe && my == mn) p++;
             }
-        }
+            return false;
+        });
     }
 }
 
@@ -249,7 +194,7 @@ int capture_sort_dedupe(zk_ctx* c, const zk_bait_table* baits, u64* pairs, uint6
     while (bbits < 32 && (1ull << bbits) < baits->n_records) bbits++;
     ZK_TRY(sort_keys(c, pairs, alt, raw, 32 + bbits, &res));
     if (res == pairs) ZK_HIP(c, hipMemcpyAsync(alt, pairs, 8 * raw, hipMemcpyDeviceToDevice, c->stream));
-    DistinctWords dw{alt, pairs};
+    DistinctWords dw{{alt}, pairs};
     u64* cnt;
     uint64_t n = 0;
     ZK_TRY(compact_count(c, dw, raw, &cnt, &n));
@@ -279,21 +224,14 @@ static int capture_hits(zk_ctx* c, const zk_bait_table* baits, const zk_bait_tab
 // ---------------------------------------------------------------------------------------
 // record gather
 // ---------------------------------------------------------------------------------------
-// line i of the text, stripped: [s, e)
-__device__ __forceinline__ void stripped_line(const u8* __restrict__ text, const u64* __restrict__ lines, u64 i, u64& s, u64& e) {
-    s = i ? lines[i - 1] + 1 : 0;
-    e = lines[i];
-    while (s < e && is_space(text[s])) s++;
-    while (e > s && is_space(text[e - 1])) e--;
-}
-
+// (a record's lines are gathered stripped: line_at + strip of read_window.hpp)
 __global__ void record_len_kernel(const u64* __restrict__ pairs, u64 n, const u8* __restrict__ text, const u64* __restrict__ lines,
                                   u64 n_lines, u64* __restrict__ len, u32* err) {
     for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x) {
         const u64 r = pairs[j] & 0xffffffffull;
         u64 t = 0;
         if (4 * r + 3 < n_lines) {
-            for (int i = 0; i < 4; i++) { u64 s, e; stripped_line(text, lines, 4 * r + i, s, e); t += e - s + 1; }
+            for (int i = 0; i < 4; i++) { u64 s, e; line_at(lines, 4 * r + i, s, e); strip(text, s, e); t += e - s + 1; }
         } else {
             atomicOr(err, ZK_DERR_CAPACITY);
         }
@@ -304,16 +242,16 @@ __global__ void record_len_kernel(const u64* __restrict__ pairs, u64 n, const u8
 // one wave per record: its four stripped lines, each followed by '\n', at out + (exclusive prefix of the lengths)
 __global__ void record_copy_kernel(const u64* __restrict__ pairs, u64 n, const u8* __restrict__ text, const u64* __restrict__ lines,
                                    u64 n_lines, const u64* __restrict__ incl, u8* __restrict__ out) {
-    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    const u64 nw = ((u64)gridDim.x * blockDim.x) >> 6;
-    for (u64 j = wave; j < n; j += nw) {
+    const WaveIds w = wave_ids();
+    const int lane = w.lane;
+    for (u64 j = w.wave; j < n; j += w.nw) {
         const u64 r = pairs[j] & 0xffffffffull;
         if (4 * r + 3 >= n_lines) continue;
         u64 o = j ? incl[j - 1] : 0;
         for (int i = 0; i < 4; i++) {
             u64 s, e;
-            stripped_line(text, lines, 4 * r + i, s, e);
+            line_at(lines, 4 * r + i, s, e);
+            strip(text, s, e);
             for (u64 k = lane; k < e - s; k += 64) out[o + k] = text[s + k];
             if (lane == 0) out[o + (e - s)] = '\n';
             o += e - s + 1;
@@ -324,9 +262,7 @@ __global__ void record_copy_kernel(const u64* __restrict__ pairs, u64 n, const u
 // spans[b] = first pair of bait b, spans[nb + 1 + b] = its first output byte (b = 0 .. nb)
 __global__ void bait_spans_kernel(const u64* __restrict__ pairs, u64 n, const u64* __restrict__ incl, u32 nb, u64* __restrict__ spans) {
     for (u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x; b <= nb; b += (u64)gridDim.x * blockDim.x) {
-        const u64 q = b << 32;
-        u64 lo = 0, hi = n;
-        while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (pairs[mid] < q) lo = mid + 1; else hi = mid; }
+        const u64 lo = lower_bound(pairs, 0ull, n, b << 32);
         spans[b] = lo;
         spans[nb + 1 + b] = lo ? incl[lo - 1] : 0;
     }

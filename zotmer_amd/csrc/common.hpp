@@ -50,6 +50,21 @@ __device__ __forceinline__ u32 wave_sum_u32(u32 v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ u32 wave_min_u32(u32 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const u32 t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
+    return v;
+}
+__device__ __forceinline__ u32 wave_max_u32(u32 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const u32 t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
+    return v;
+}
+__device__ __forceinline__ u64 wave_or_u64(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
+    return v;
+}
 // inclusive prefix sum across the 64 lanes
 __device__ __forceinline__ u32 wave_incl_scan_u32(u32 v) {
     const int l = lane_id();
@@ -203,6 +218,47 @@ __device__ __forceinline__ u64 block_sum_u64(u64 v, u64* scratch) {
     if (threadIdx.x == 0) for (int w = 0; w < nw; w++) t += scratch[w];
     __syncthreads();
     return t;
+}
+
+// Sum of v over a workgroup of NW waves in a fixed order (the xor tree of a wave, then the waves by number: the same inputs
+// give the same bits), valid in thread 0 like block_sum_u64 (scratch: one double per wave).  Ends with a barrier.
+template <int NW>
+__device__ __forceinline__ double block_sum_f64(double v, double* scratch) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) scratch[wave] = v;
+    __syncthreads();
+    double t = 0;
+    if (threadIdx.x == 0) for (int w = 0; w < NW; w++) t += scratch[w];
+    __syncthreads();
+    return t;
+}
+
+// The largest v of a workgroup of NW waves, valid in EVERY thread, unlike the sums above (scratch: one u32 per wave).  Ends
+// with a barrier.
+template <int NW>
+__device__ __forceinline__ u32 block_max_u32(u32 v, u32* scratch) {
+    v = wave_max_u32(v);
+    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u32 m = 0;
+#pragma unroll
+    for (int w = 0; w < NW; w++) m = scratch[w] > m ? scratch[w] : m;
+    __syncthreads();
+    return m;
+}
+
+// the number of decimal digits of v
+__device__ __forceinline__ u32 dec_digits(u64 v) {
+    u32 d = 1;
+    while (v >= 10) { v /= 10; d++; }
+    return d;
+}
+// the decimal digits of v written backwards, the last one at end[-1]; returns the position of the first
+__device__ __forceinline__ u8* put_dec(u8* end, u64 v) {
+    do { *--end = (u8)('0' + (u32)(v % 10)); v /= 10; } while (v);
+    return end;
 }
 
 // reverse the 32 bit-pairs of a word (bits.rev, zotmer/library/bits.py:22-31)

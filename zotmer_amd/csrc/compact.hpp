@@ -1,8 +1,29 @@
-// compact.hpp -- the order-preserving compaction shared by capture.hip and strand_bias.hip.
+// compact.hpp -- the order-preserving compaction and the predicates that more than one command feeds it.
+// Users: capture.hip, contig_spectra.hip, pileup.hip, strand_bias.hip, vars_scan.hip.
 #pragma once
 #include "internal.hpp"
 
 namespace zk {
+
+// ---------------------------------------------------------------------------------------
+// shared predicates (flag / store: below)
+// ---------------------------------------------------------------------------------------
+struct NewlinePos {      // positions of the '\n' bytes
+    const u8* text; u64* out;
+    __device__ bool flag(u64 i) const { return text[i] == '\n'; }
+    __device__ void store(u64 pos, u64 i) const { out[pos] = i; }
+};
+
+// Run heads of a sorted array: item i is kept when it is the first of a run of equal keys, or of equal (key, value) in a
+// key-sorted, value-stable array.  What a head stores is its user's: derive, and add store.
+struct KeyRunHead {
+    const u64* k;
+    __device__ bool flag(u64 i) const { return i == 0 || k[i] != k[i - 1]; }
+};
+struct PairRunHead {
+    const u64* k; const u32* v;
+    __device__ bool flag(u64 i) const { return i == 0 || k[i] != k[i - 1] || v[i] != v[i - 1]; }
+};
 
 // ---------------------------------------------------------------------------------------
 // Order-preserving compaction: a count pass over tiles of 4096 items, an inclusive scan of the tile counts

@@ -20,52 +20,29 @@ namespace zk {
 static_assert(ZK_CONTIG_TILE == CP_TILE, "ZK_CONTIG_TILE is the tile of the compaction kernels that cut the runs");
 
 // ---------------------------------------------------------------------------------------
-// predicates (compact.hpp)
+// predicates (compact.hpp: NewlinePos cuts the records, KeyRunHead and PairRunHead the runs)
 // ---------------------------------------------------------------------------------------
-
-struct ContigEnds {      // positions of the '\n' bytes
-    const u8* stream; u64* out;
-    __device__ bool flag(u64 i) const { return stream[i] == '\n'; }
-    __device__ void store(u64 pos, u64 i) const { out[pos] = i; }
-};
 
 // item i = the window at position i of the stream: its key (min(x, rc x) with both strands, x with one) and its record
 struct ContigWindow {
     const u8* stream; u64 n; int K; int both; const u64* ends; u64 n_ends; u64* keys; u32* ids;
-    __device__ bool window(u64 pos, u64& x, u64& xb) const {
-        if (pos + K > n) return false;
-        x = 0; xb = 0;
-        for (int j = 0; j < K; j++) {
-            u32 ok;
-            const u32 b = base_code(stream[pos + j], ok);
-            if (!ok) return false;
-            x = (x << 2) | b;
-            xb |= (u64)(3u - b) << (2 * j);
-        }
-        return true;
-    }
-    __device__ bool flag(u64 i) const { u64 x, xb; return window(i, x, xb); }
+    __device__ bool flag(u64 i) const { u64 x, xb; return point_window(stream, n, K, i, x, xb); }
     __device__ void store(u64 pos, u64 i) const {
         u64 x, xb;
-        window(i, x, xb);
+        point_window(stream, n, K, i, x, xb);
         keys[pos] = (both && xb < x) ? xb : x;
-        u64 lo = 0, hi = n_ends;           // record = number of terminators before the window
-        while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (ends[mid] < i) lo = mid + 1; else hi = mid; }
-        ids[pos] = (u32)lo;
+        ids[pos] = record_of(ends, n_ends, i);
     }
 };
 
-struct RunHeads {        // first of each run of equal (key, record) in a key-sorted, record-stable array -> its index
-    const u64* k; const u32* v; u32* heads;
-    __device__ bool flag(u64 i) const { return i == 0 || k[i] != k[i - 1] || v[i] != v[i - 1]; }
+// the head of each run -> its index: RunHeads over (key, record) in a key-sorted, record-stable array, KeyHeads over the keys
+template <class H>
+struct HeadIndex : H {
+    u32* heads;
     __device__ void store(u64 pos, u64 i) const { heads[pos] = (u32)i; }
 };
-
-struct KeyHeads {        // first of each run of equal keys -> its index
-    const u64* k; u32* heads;
-    __device__ bool flag(u64 i) const { return i == 0 || k[i] != k[i - 1]; }
-    __device__ void store(u64 pos, u64 i) const { heads[pos] = (u32)i; }
-};
+using RunHeads = HeadIndex<PairRunHead>;
+using KeyHeads = HeadIndex<KeyRunHead>;
 
 struct LiveBins {        // the reduced (word, frequency) pairs whose frequency is not 0, the word widened to record << 32 | count
     const u64* w; const u32* f; int cbits; u64* ow; u64* of;
@@ -141,7 +118,7 @@ static int contig_spectra(zk_ctx* c, const u8* stream, uint64_t n, int K, int bo
     ZK_TRY(arena_require(c, need, need));
     u64* cnt;
     uint64_t n_rec = 0;
-    ContigEnds ce{stream, nullptr};
+    NewlinePos ce{stream, nullptr};
     ZK_TRY(compact_count(c, ce, n, &cnt, &n_rec));
     if (n_rec >= (1ull << 32)) return fail(c, ZK_ERANGE, "contig spectra: %llu records in one batch (fewer than 2^32)", (unsigned long long)n_rec);
     st->n_records = n_rec;
@@ -169,12 +146,12 @@ static int contig_spectra(zk_ctx* c, const u8* stream, uint64_t n, int K, int bo
     // the two cuts of the sorted array
     u32 *rheads, *kheads;
     uint64_t n_runs = 0, n_keys = 0;
-    RunHeads rh{rk, rv, nullptr};
+    RunHeads rh{{rk, rv}, nullptr};
     ZK_TRY(compact_count(c, rh, nw, &cnt, &n_runs));
     ZK_TRY(arena_alloc(c, 4 * n_runs, (void**)&rheads));
     rh.heads = rheads;
     ZK_TRY(compact_write(c, rh, nw, cnt));
-    KeyHeads kh{rk, nullptr};
+    KeyHeads kh{{rk}, nullptr};
     ZK_TRY(compact_count(c, kh, nw, &cnt, &n_keys));
     ZK_TRY(arena_alloc(c, 4 * n_keys, (void**)&kheads));
     kh.heads = kheads;

@@ -5,8 +5,8 @@
 // walk depends on its order and runs on the host (hostio.cpp: zk_contig_walk); what it reads per node is
 // computed here for all nodes at once, and what it keeps is turned into FASTA text here.
 //   * links_check_kernel: strictly ascending, below 4^K.  One plain store of 1 by whoever finds a fault.
-//   * links_dir_kernel: dir[b] = the number of keys below b << shift, for the top `bits` key bits (about 8 keys a bucket): every
-//     search below starts from two adjacent words of it (bait_table.hpp's idea, here in the call's workspace).
+//   * a key directory (search.hpp) over the top `bits` key bits, about 8 keys a bucket, in the call's workspace: every search
+//     below starts from two adjacent words of it.
 //   * links_next_kernel: one workgroup per tile of ZK_LINKS_TILE consecutive x.  Within one first base y0 ascends with x, so the
 //     successors of the tile's x of first base b lie in one ascending window of S: [the first entry >= y0 of the first such x,
 //     the last entry <= y0 | 3 of the last].  Four threads find the (at most four) windows, the workgroup stages them in LDS
@@ -22,30 +22,13 @@
 //     contig in the offsets by binary search.  No thread's work grows with a contig's length.
 // Nothing waits on another workgroup in the link kernels and there are no atomics; the scan of the render is codec.hip's.
 #include "internal.hpp"
+#include "search.hpp"
 
 namespace zk {
 
 constexpr int LK_BLOCK = 256, LK_ITEMS = 4, LK_TILE = LK_BLOCK * LK_ITEMS;
 static_assert(LK_TILE == ZK_LINKS_TILE, "the tile include/zotk.h publishes");
 constexpr int LK_STAGE = 5 * LK_TILE;          // staged window entries: 40 KiB, with the tile's 8 KiB three workgroups per CU
-
-// keys whose top bits x >> shift equal b are k[dir[b], dir[b + 1])
-struct LinkDir { const u32* dir; int shift; };
-
-// the number of keys < q (q < 4^K)
-__device__ __forceinline__ u32 lk_lower(const u64* __restrict__ k, const LinkDir& d, u64 q) {
-    const u64 b = q >> d.shift;
-    u32 lo = d.dir[b], hi = d.dir[b + 1];
-    while (lo < hi) { const u32 mid = lo + ((hi - lo) >> 1); if (k[mid] < q) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-// the number of keys <= q
-__device__ __forceinline__ u32 lk_upper(const u64* __restrict__ k, const LinkDir& d, u64 q) {
-    const u64 b = q >> d.shift;
-    u32 lo = d.dir[b], hi = d.dir[b + 1];
-    while (lo < hi) { const u32 mid = lo + ((hi - lo) >> 1); if (k[mid] <= q) lo = mid + 1; else hi = mid; }
-    return lo;
-}
 
 __global__ __launch_bounds__(256) void links_check_kernel(const u64* __restrict__ k, u64 n, int K, u64* __restrict__ bad) {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
@@ -54,17 +37,7 @@ __global__ __launch_bounds__(256) void links_check_kernel(const u64* __restrict_
     }
 }
 
-__global__ __launch_bounds__(256) void links_dir_kernel(const u64* __restrict__ k, u32 n, int shift, u64 nb, u32* __restrict__ dir) {
-    for (u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x; b <= nb; b += (u64)gridDim.x * blockDim.x) {
-        if (b == nb) { dir[b] = n; continue; }
-        const u64 q = b << shift;
-        u32 lo = 0, hi = n;
-        while (lo < hi) { const u32 mid = lo + ((hi - lo) >> 1); if (k[mid] < q) lo = mid + 1; else hi = mid; }
-        dir[b] = lo;
-    }
-}
-
-__global__ __launch_bounds__(LK_BLOCK) void links_next_kernel(const u64* __restrict__ k, u32 n, int K, LinkDir d, u32* __restrict__ next) {
+__global__ __launch_bounds__(LK_BLOCK) void links_next_kernel(const u64* __restrict__ k, u32 n, int K, KeyDir d, u32* __restrict__ next) {
     __shared__ u64 s_x[LK_TILE];
     __shared__ u64 s_win[LK_STAGE];
     __shared__ u32 s_seg[5];          // the tile's first x whose first base is >= b (tile-local)
@@ -87,18 +60,14 @@ __global__ __launch_bounds__(LK_BLOCK) void links_next_kernel(const u64* __restr
         if (i < cnt) s_x[i] = x[r];
     }
     __syncthreads();
-    if (tid < 5) {
-        u32 lo = 0, hi = cnt;
-        while (lo < hi) { const u32 mid = (lo + hi) >> 1; if ((s_x[mid] >> top) < (u64)tid) lo = mid + 1; else hi = mid; }
-        s_seg[tid] = lo;
-    }
+    if (tid < 5) s_seg[tid] = partition_point(0u, cnt, [&](u32 i) { return (s_x[i] >> top) < (u64)tid; });
     __syncthreads();
     if (tid < 4) {
         const u32 a = s_seg[tid], b = s_seg[tid + 1];
         u32 ws = 0, we = 0;
         if (a < b) {
-            ws = lk_lower(k, d, (s_x[a] << 2) & m);
-            we = lk_upper(k, d, ((s_x[b - 1] << 2) & m) | 3);
+            ws = dir_lower(k, d, (s_x[a] << 2) & m);
+            we = dir_upper(k, d, ((s_x[b - 1] << 2) & m) | 3);
         }
         s_ws[tid] = ws;
         s_we[tid] = we;
@@ -129,22 +98,20 @@ __global__ __launch_bounds__(LK_BLOCK) void links_next_kernel(const u64* __restr
         u32 res = ZK_NO_LINK;
         if (staged) {
             const u32 off = s_off[b], end = s_off[b + 1];
-            u32 lo = off, hi = end;
-            while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (s_win[mid] < y0) lo = mid + 1; else hi = mid; }
+            const u32 lo = lower_bound(s_win, off, end, y0);
             if (lo < end && s_win[lo] <= y1 && (lo + 1 >= end || s_win[lo + 1] > y1)) res = ws + (lo - off);
         } else {
             const u32 end = s_we[b];
-            u32 lo = ws, hi = end;
-            while (lo < hi) { const u32 mid = lo + ((hi - lo) >> 1); if (k[mid] < y0) lo = mid + 1; else hi = mid; }
+            const u32 lo = lower_bound(k, ws, end, y0);
             if (lo < end && k[lo] <= y1 && (lo + 1 >= end || k[lo + 1] > y1)) res = lo;
         }
         next[t0 + i] = res;
     }
 }
 
-__global__ __launch_bounds__(256) void links_rc_kernel(const u64* __restrict__ k, u32 n, int K, LinkDir d, u32* __restrict__ rcr) {
+__global__ __launch_bounds__(256) void links_rc_kernel(const u64* __restrict__ k, u32 n, int K, KeyDir d, u32* __restrict__ rcr) {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
-        rcr[i] = lk_lower(k, d, revcomp(K, k[i]));
+        rcr[i] = dir_lower(k, d, revcomp(K, k[i]));
 }
 
 static int debruijn_links(zk_ctx* c, const u64* k, uint64_t n, int K, u32* next, u32* rcr) {
@@ -165,9 +132,8 @@ static int debruijn_links(zk_ctx* c, const u64* k, uint64_t n, int K, u32* next,
     ZK_TRY(stream_sync(c));
     if (c->h_scalars->links_bad)
         return fail(c, ZK_EINVAL, "zk_debruijn_links: the k-mers are not strictly ascending, or not below 4^%d", K);
-    const LinkDir d{dir, 2 * K - bits};
-    hipLaunchKernelGGL(links_dir_kernel, dim3(grid_cap(c, div_up(nb + 1, 256), 16)), dim3(256), 0, c->stream, k, (u32)n, d.shift, nb, dir);
-    ZK_HIP(c, hipGetLastError());
+    const KeyDir d{dir, 2 * K - bits};
+    ZK_TRY(key_dir_build(c, k, (u32)n, d.shift, nb, dir));
     prof_begin(c, ZK_PROF_LINKS, 12 * n);
     hipLaunchKernelGGL(links_next_kernel, dim3((u32)div_up(n, LK_TILE)), dim3(LK_BLOCK), 0, c->stream, k, (u32)n, K, d, next);
     prof_end(c);
@@ -186,11 +152,6 @@ static int debruijn_links(zk_ctx* c, const u64* k, uint64_t n, int K, u32* next,
 constexpr u32 CR_HEAD = 8;                     // ">contig_"
 constexpr u32 CR_LETTERS = 0x54474341u;        // "ACGT", the first letter in the low byte
 
-__device__ __forceinline__ u32 cr_digits(u32 v) {
-    u32 d = 1;
-    while (v >= 10) { v /= 10; d++; }
-    return d;
-}
 __device__ __forceinline__ u8 cr_letter(u64 x, int base_from_last) { return (u8)(CR_LETTERS >> (8 * (u32)((x >> (2 * base_from_last)) & 3))); }
 
 // len[c] = the bytes of contig c; the offsets and the nodes are checked on the way
@@ -202,7 +163,7 @@ __global__ __launch_bounds__(256) void contig_len_kernel(const u32* __restrict__
         if (i < n_contigs) {
             const u64 a = offs[i], b = offs[i + 1];
             const bool ok = a < b && b <= n_nodes && (i > 0 || a == 0) && (i + 1 < n_contigs || b == n_nodes);
-            if (ok) len[i] = (b - a) + (u64)K + cr_digits(nodes[a]) + CR_HEAD + 1;
+            if (ok) len[i] = (b - a) + (u64)K + dec_digits(nodes[a]) + CR_HEAD + 1;
             else { len[i] = 0; *bad = 1; }
         }
     }
@@ -213,8 +174,8 @@ __global__ __launch_bounds__(256) void contig_write_kernel(const u64* __restrict
                                                            const u64* __restrict__ offs, u64 n_contigs, const u64* __restrict__ incl,
                                                            u8* __restrict__ out) {
     for (u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x; q < n_nodes; q += (u64)gridDim.x * blockDim.x) {
-        u64 lo = 0, hi = n_contigs - 1;          // the contig of node q: the first c with offs[c + 1] > q
-        while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (offs[mid + 1] <= q) lo = mid + 1; else hi = mid; }
+        // the contig of node q: the first c with offs[c + 1] > q
+        const u64 lo = partition_point(0ull, n_contigs - 1, [&](u64 c) { return offs[c + 1] <= q; });
         const u64 a = offs[lo], len = offs[lo + 1] - a, p = q - a;
         const u64 first = lo ? incl[lo - 1] : 0;
         const u64 body = incl[lo] - (len + (u64)K);          // the K bases of the first node start here
@@ -223,10 +184,8 @@ __global__ __launch_bounds__(256) void contig_write_kernel(const u64* __restrict
         if (p == 0) {
             u8* h = out + first;
             h[0] = '>'; h[1] = 'c'; h[2] = 'o'; h[3] = 'n'; h[4] = 't'; h[5] = 'i'; h[6] = 'g'; h[7] = '_';
-            u8* e = out + body;
-            *--e = '\n';
-            u32 v = node;
-            do { *--e = (u8)('0' + v % 10); v /= 10; } while (v);
+            out[body - 1] = '\n';
+            put_dec(out + body - 1, node);
             for (int j = 0; j < K; j++) out[body + j] = cr_letter(x, K - 1 - j);
         } else {
             out[body + (u64)K + p - 1] = cr_letter(x, 0);

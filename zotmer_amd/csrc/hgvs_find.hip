@@ -37,27 +37,15 @@ __global__ __launch_bounds__(256) void capkmers_mark_kernel(const u64* __restric
     }
 }
 
-// valid windows of the sequence line of record r in one text; called by the whole wave
-__device__ __forceinline__ u32 ck_line_windows(const Mate& m, u64 r, int K, int lane) {
-    const u64 b = m.lines[4 * r] + 1, e = m.lines[4 * r + 1];
-    u32 w = 0;
-    for (u64 c0 = b; c0 < e; c0 += 64) {
-        u64 x;
-        w += (u32)__popcll(__ballot(chunk_window(m.text, c0, e, K, lane, x)));
-    }
-    return w;
-}
-
+// wcount[r] = the valid windows of the sequence lines of a needed record r
 __global__ __launch_bounds__(256) void capkmers_count_kernel(Mate m1, Mate m2, u64 n_reads, int K, const u8* __restrict__ need,
                                                              u32* __restrict__ wcount) {
-    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    const u64 nw = ((u64)gridDim.x * blockDim.x) >> 6;
-    for (u64 r = wave; r < n_reads; r += nw) {
+    const WaveIds w = wave_ids();
+    for (u64 r = w.wave; r < n_reads; r += w.nw) {
         if (!need[r]) continue;
-        u32 w = ck_line_windows(m1, r, K, lane);
-        if (m2.text) w += ck_line_windows(m2, r, K, lane);
-        if (lane == 0) wcount[r] = w;
+        u32 n = 0;
+        for_each_mate_chunk(m1, m2, r, K, w.lane, [&](u64, bool valid, u64) { n += (u32)__popcll(__ballot(valid)); return false; });
+        if (w.lane == 0) wcount[r] = n;
     }
 }
 
@@ -69,31 +57,23 @@ __global__ __launch_bounds__(256) void capkmers_len_kernel(const u64* __restrict
 
 __global__ __launch_bounds__(256) void capkmers_emit_kernel(const u64* __restrict__ pairs, u64 n, Mate m1, Mate m2, int K,
                                                             const u64* __restrict__ incl, u32* __restrict__ baits, u64* __restrict__ kmers, u64 cap) {
-    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    const u64 nw = ((u64)gridDim.x * blockDim.x) >> 6;
-    const int mates = m2.text ? 2 : 1;
-    for (u64 j = wave; j < n; j += nw) {
+    const WaveIds w = wave_ids();
+    for (u64 j = w.wave; j < n; j += w.nw) {
         const u64 word = pairs[j];
         const u64 r = word & 0xffffffffull;
         const u32 bait = (u32)(word >> 32);
         u64 o = j ? incl[j - 1] : 0;
-        for (int m = 0; m < mates; m++) {
-            const Mate mt = m ? m2 : m1;
-            const u64 b = mt.lines[4 * r] + 1, e = mt.lines[4 * r + 1];
-            for (u64 c0 = b; c0 < e; c0 += 64) {
-                u64 x;
-                const bool valid = chunk_window(mt.text, c0, e, K, lane, x);
-                const u64 vm = __ballot(valid);
-                const u32 v = (u32)__popcll(vm);
-                const u64 p = o + popc_below(vm);
-                if (valid && p + v < cap) {           // (the host has checked the total against cap: never false)
-                    baits[p] = bait; kmers[p] = x;
-                    baits[p + v] = bait; kmers[p + v] = revcomp(K, x);
-                }
-                o += 2ull * v;
+        for_each_mate_chunk(m1, m2, r, K, w.lane, [&](u64, bool valid, u64 x) {
+            const u64 vm = __ballot(valid);
+            const u32 v = (u32)__popcll(vm);
+            const u64 p = o + popc_below(vm);
+            if (valid && p + v < cap) {           // (the host has checked the total against cap: never false)
+                baits[p] = bait; kmers[p] = x;
+                baits[p + v] = bait; kmers[p + v] = revcomp(K, x);
             }
-        }
+            o += 2ull * v;
+            return false;
+        });
     }
 }
 
@@ -160,25 +140,16 @@ struct PathWin { u64 value, mask, cell0; u32 bait, max_ham, min_count, t0, nt, p
 __global__ __launch_bounds__(256) void path_seg_kernel(const u32* __restrict__ baits, u64 n, const u32* __restrict__ wbait, u32 W, u32* __restrict__ seg) {
     for (u32 w = blockIdx.x * blockDim.x + threadIdx.x; w < W; w += gridDim.x * blockDim.x) {
         const u32 b = wbait[w];
-        u64 lo = 0, hi = n;
-        while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (baits[mid] < b) lo = mid + 1; else hi = mid; }
-        u64 lo2 = lo, hi2 = n;
-        while (lo2 < hi2) { const u64 mid = (lo2 + hi2) >> 1; if (baits[mid] <= b) lo2 = mid + 1; else hi2 = mid; }
+        const u64 lo = lower_bound(baits, 0ull, n, b);
         seg[2 * w] = (u32)lo;
-        seg[2 * w + 1] = (u32)lo2;
+        seg[2 * w + 1] = (u32)upper_bound(baits, lo, n, b);
     }
 }
 
 // first window whose bait is >= b (UPPER: > b)
 template <bool UPPER>
 __device__ __forceinline__ u32 ps_window_bound(const PathWin* __restrict__ win, u32 W, u32 b) {
-    u32 lo = 0, hi = W;
-    while (lo < hi) {
-        const u32 mid = lo + ((hi - lo) >> 1);
-        const u32 v = win[mid].bait;
-        if (UPPER ? v <= b : v < b) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    return partition_point(0u, W, [&](u32 i) { return UPPER ? win[i].bait <= b : win[i].bait < b; });
 }
 
 // EMIT false: cells[cell(w, t)] = the matches of window w in tile t.  EMIT true: cells holds the inclusive scan of those, and

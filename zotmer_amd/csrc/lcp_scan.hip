@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "internal.hpp"
+#include "search.hpp"
 
 namespace zk {
 
@@ -41,19 +42,6 @@ __device__ __forceinline__ u32 lcp_of(int K, u64 x, u64 y) {
     return z ? (u32)(K - 1 - ((63 - __clzll((long long)z)) >> 1)) : (u32)K;
 }
 
-// the largest v of the workgroup, valid in every thread.  Ends with a barrier.
-__device__ __forceinline__ u32 lcp_block_max(u32 v, u32* s_w) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const u32 t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u32 m = 0;
-#pragma unroll
-    for (int w = 0; w < LCP_NW; w++) m = s_w[w] > m ? s_w[w] : m;
-    __syncthreads();
-    return m;
-}
-
 __global__ __launch_bounds__(LCP_BLOCK) void lcp_pass1_kernel(const u64* __restrict__ S, u32 nS, const u64* __restrict__ X, u64 nX, int K,
                                                               u8* __restrict__ L, u64* __restrict__ Y, u32* __restrict__ tmax) {
     __shared__ u32 s_w[LCP_NW];
@@ -61,15 +49,14 @@ __global__ __launch_bounds__(LCP_BLOCK) void lcp_pass1_kernel(const u64* __restr
     u32 l = 0;
     if (i < nS) {
         const u64 s = S[i];
-        u64 lo = 0, hi = nX;
-        while (lo < hi) { const u64 mid = lo + ((hi - lo) >> 1); if (X[mid] < s) lo = mid + 1; else hi = mid; }
+        const u64 lo = lower_bound(X, 0ull, nX, s);
         u64 x = X[lo < nX ? lo : nX - 1];
         l = lcp_of(K, x, s);
         if (l == 0) x = 0;          // scan.py:102-104: L and Y are touched only where the lcp is above 0
         L[i] = (u8)l;
         Y[i] = x;
     }
-    const u32 m = lcp_block_max(l, s_w);
+    const u32 m = block_max_u32<LCP_NW>(l, s_w);
     if (threadIdx.x == 0) tmax[blockIdx.x] = m;
 }
 
@@ -77,7 +64,7 @@ __global__ __launch_bounds__(LCP_BLOCK) void lcp_pass1_kernel(const u64* __restr
 __global__ __launch_bounds__(LCP_BLOCK) void lcp_max_kernel(const u32* __restrict__ in, u32 n, u32* __restrict__ out) {
     __shared__ u32 s_w[LCP_NW];
     const u64 i = (u64)blockIdx.x * LCP_BLOCK + threadIdx.x;
-    const u32 m = lcp_block_max(i < n ? in[i] : 0u, s_w);
+    const u32 m = block_max_u32<LCP_NW>(i < n ? in[i] : 0u, s_w);
     if (threadIdx.x == 0) out[blockIdx.x] = m;
 }
 
@@ -125,7 +112,7 @@ __global__ __launch_bounds__(LCP_BLOCK) void lcp_jump_kernel(const u32* __restri
 __global__ __launch_bounds__(LCP_BLOCK) void lcp_last_kernel(const u8* __restrict__ mark, u32 nS, u32* __restrict__ last) {
     __shared__ u32 s_w[LCP_NW];
     const u64 i = (u64)blockIdx.x * LCP_BLOCK + threadIdx.x;
-    const u32 m = lcp_block_max(i < nS && mark[i] ? (u32)i + 1u : 0u, s_w);
+    const u32 m = block_max_u32<LCP_NW>(i < nS && mark[i] ? (u32)i + 1u : 0u, s_w);
     if (threadIdx.x == 0) last[blockIdx.x] = m;
 }
 
@@ -213,9 +200,7 @@ struct PlaceArgs {
 
 // the S index of entry j: the last i with T[i] <= j (T ascends from 0 to n_entries > j, so 0 <= i < nS)
 __device__ __forceinline__ u32 place_owner(const u32* __restrict__ T, u32 nS, u32 j) {
-    u32 lo = 0, hi = nS + 1;
-    while (lo < hi) { const u32 mid = lo + ((hi - lo) >> 1); if (T[mid] <= j) lo = mid + 1; else hi = mid; }
-    return lo - 1;
+    return upper_bound(T, 0u, nS + 1, j) - 1;
 }
 // the slot within its record that position p names (scan.py:297-300): p - 1, on the reverse strand -(p + 1)
 __device__ __forceinline__ u64 place_q(int p) { const long long q = p; return (u64)(q > 0 ? q : -q) - 1; }

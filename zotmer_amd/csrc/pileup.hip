@@ -28,13 +28,7 @@ static_assert(ZK_PILEUP_TILE == CP_TILE, "ZK_PILEUP_TILE is the tile of the comp
 // ---------------------------------------------------------------------------------------
 // zk_anchor_pileup
 // ---------------------------------------------------------------------------------------
-// the sequence line of record r (line 4r + 1 of the text), stripped: [s, e)
-__device__ __forceinline__ void pu_line(const u8* __restrict__ text, const u64* __restrict__ lines, u64 r, u64& s, u64& e) {
-    s = lines[4 * r] + 1;
-    e = lines[4 * r + 1];
-    while (s < e && is_space(text[s])) s++;
-    while (e > s && is_space(text[e - 1])) e--;
-}
+// (the sequence line of a record is read STRIPPED here: seq_line + strip of read_window.hpp)
 
 // window i of a line of L bytes as the list of orientation o holds it (basics.kmersWithPosLists; hits' p -= 1)
 __device__ __forceinline__ void pu_orient(int K, int o, u64 L, u64 i, u64 x, u64& key, u32& p) {
@@ -45,25 +39,8 @@ __device__ __forceinline__ void pu_orient(int K, int o, u64 L, u64 i, u64 x, u64
 __device__ __forceinline__ bool pu_has_anchor(const BaitView& bt, u64 key, u32 a) {
     u32 lo, end;
     if (!bait_find(bt, key, lo, end)) return false;
-    u32 hi = end;
-    while (lo < hi) { const u32 mid = lo + ((hi - lo) >> 1); if (bt.ids[mid] < a) lo = mid + 1; else hi = mid; }
+    lo = lower_bound(bt.ids, lo, end, a);
     return lo < end && bt.ids[lo] == a;
-}
-
-// The bytes [s, s + n_bytes) of a line rolled through one k-mer register by one lane: f(j, x) for every window j that lies
-// whole in them, ascending; f returns true to stop.
-template <class F>
-__device__ __forceinline__ void pu_roll(const u8* __restrict__ text, u64 s, u64 n_bytes, int K, F f) {
-    const u64 mask = K == 32 ? ~0ull : (1ull << (2 * K)) - 1;
-    u64 x = 0;
-    u32 run = 0;
-    for (u64 b = 0; b < n_bytes; b++) {
-        u32 ok;
-        const u32 code = base_code(text[s + b], ok);
-        if (!ok) { run = 0; x = 0; continue; }
-        x = ((x << 2) | code) & mask;
-        if (++run >= (u32)K && f(b + 1 - (u64)K, x)) return;
-    }
 }
 
 // diagonal number q (wave-uniform) of the wave's register list
@@ -77,31 +54,28 @@ __device__ __forceinline__ u32 pu_diag(const u32 (&reg)[PU_WORDS], u32 q) {
 // a line longer than pad that has a hit: its diagonals could reach the coordinates of another zone
 __global__ __launch_bounds__(256) void long_line_kernel(BaitView bt, const u8* __restrict__ text, const u64* __restrict__ lines, u64 n_reads, int K,
                                                         u64 pad, u64* __restrict__ bad) {
-    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    const u64 nw = ((u64)gridDim.x * blockDim.x) >> 6;
-    for (u64 r = wave; r < n_reads; r += nw) {
+    const WaveIds w = wave_ids();
+    for (u64 r = w.wave; r < n_reads; r += w.nw) {
         u64 s, e;
-        pu_line(text, lines, r, s, e);
+        seq_line(lines, r, s, e);
+        strip(text, s, e);
         if (e - s <= pad) continue;
-        for (u64 c0 = s; c0 < e; c0 += 64) {
-            u64 x;
+        const bool hit = for_each_chunk(text, s, e, K, w.lane, [&](u64, bool valid, u64 x) {
             u32 lo, hi;
-            const bool valid = chunk_window(text, c0, e, K, lane, x);
-            const bool hit = valid && (bait_find(bt, x, lo, hi) || bait_find(bt, revcomp(K, x), lo, hi));
-            if (__ballot(hit)) { if (lane == 0) *bad = 1; break; }
-        }
+            return __ballot(valid && (bait_find(bt, x, lo, hi) || bait_find(bt, revcomp(K, x), lo, hi))) != 0;
+        });
+        if (hit && w.lane == 0) *bad = 1;
     }
 }
 
 __global__ __launch_bounds__(256) void pileup_kernel(BaitView bt, const u8* __restrict__ text, const u64* __restrict__ lines, u64 n_reads, int K,
                                                      u32* __restrict__ coords, u64* __restrict__ kmers, u64 cap, u64* cursor) {
-    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    const u64 nw = ((u64)gridDim.x * blockDim.x) >> 6;
-    for (u64 r = wave; r < n_reads; r += nw) {
+    const WaveIds w = wave_ids();
+    const int lane = w.lane;
+    for (u64 r = w.wave; r < n_reads; r += w.nw) {
         u64 s, e;
-        pu_line(text, lines, r, s, e);
+        seq_line(lines, r, s, e);
+        strip(text, s, e);
         const u64 L = e - s;
         if (L < (u64)K) continue;
         for (int o = 0; o < 2; o++) {
@@ -111,12 +85,11 @@ __global__ __launch_bounds__(256) void pileup_kernel(BaitView bt, const u8* __re
             for (int j = 0; j < PU_WORDS; j++) reg[j] = 0;
             u32 nd = 0, W = 0;
             bool over = false;
-            for (u64 c0 = s; c0 < e; c0 += 64) {
-                u64 x, key;
+            for_each_chunk(text, s, e, K, lane, [&](u64 c0, bool valid, u64 x) {
+                u64 key;
                 u32 p, t = 0, te = 0;
-                const bool valid = chunk_window(text, c0, e, K, lane, x);
                 W += (u32)__popcll(__ballot(valid));
-                if (over) continue;
+                if (over) return false;
                 pu_orient(K, o, L, c0 - s + lane, x, key, p);
                 if (!(valid && bait_find(bt, key, t, te))) t = te = 0;
                 // the lowest lane with an anchor left names a diagonal; every lane whose next anchor gives the same one moves on
@@ -135,18 +108,18 @@ __global__ __launch_bounds__(256) void pileup_kernel(BaitView bt, const u8* __re
                     for (int j = 0; j < PU_WORDS; j++) if ((nd >> 6) == (u32)j && (nd & 63u) == (u32)lane) reg[j] = dd;
                     nd++;
                 }
-            }
-            if (W == 0) break;                 // no window: the other orientation has none either
+                return false;
+            });
+            if (W == 0) break;                // no window: the other orientation has none either
             if (!over) {
                 if (nd == 0) continue;
                 u64 base = 0;
                 if (lane == 0) base = atomicAdd((unsigned long long*)cursor, (unsigned long long)nd * W);
                 base = __shfl(base, 0, 64);
                 u32 done = 0;
-                for (u64 c0 = s; c0 < e; c0 += 64) {
-                    u64 x, key;
+                for_each_chunk(text, s, e, K, lane, [&](u64 c0, bool valid, u64 x) {
+                    u64 key;
                     u32 p;
-                    const bool valid = chunk_window(text, c0, e, K, lane, x);
                     pu_orient(K, o, L, c0 - s + lane, x, key, p);
                     const u64 vm = __ballot(valid);
                     const u32 rank = done + popc_below(vm);
@@ -156,16 +129,16 @@ __global__ __launch_bounds__(256) void pileup_kernel(BaitView bt, const u8* __re
                         if (valid && pos < cap) { coords[pos] = dd + p; kmers[pos] = key; }
                     }
                     done += (u32)__popcll(vm);
-                }
+                    return false;
+                });
                 continue;
             }
             // more diagonals than the registers hold: no list.  An anchor's diagonal is new iff no earlier window of the line
             // gives it too (a window's own anchors are distinct), which its lane finds out by rolling through those windows;
             // the lanes with a new one take W places each and write them one after the other.
-            for (u64 c0 = s; c0 < e; c0 += 64) {
-                u64 x, key;
+            for_each_chunk(text, s, e, K, lane, [&](u64 c0, bool valid, u64 x) {
+                u64 key;
                 u32 p, t = 0, te = 0;
-                const bool valid = chunk_window(text, c0, e, K, lane, x);
                 const u64 i = c0 - s + lane;
                 pu_orient(K, o, L, i, x, key, p);
                 if (!(valid && bait_find(bt, key, t, te))) t = te = 0;
@@ -174,7 +147,7 @@ __global__ __launch_bounds__(256) void pileup_kernel(BaitView bt, const u8* __re
                     const u32 d = has ? bt.ids[t] - p : 0u;
                     bool fresh = has;
                     if (has)
-                        pu_roll(text, s, i + (u64)K - 1, K, [&](u64 j, u64 xj) {
+                        roll_windows(text, s, i + (u64)K - 1, K, [&](u64 j, u64 xj) {
                             u64 kj; u32 pj;
                             pu_orient(K, o, L, j, xj, kj, pj);
                             if (pu_has_anchor(bt, kj, d + pj)) fresh = false;
@@ -186,7 +159,7 @@ __global__ __launch_bounds__(256) void pileup_kernel(BaitView bt, const u8* __re
                         if (lane == 0) base = atomicAdd((unsigned long long*)cursor, (unsigned long long)__popcll(fm) * W);
                         base = __shfl(base, 0, 64) + (u64)popc_below(fm) * W;
                         if (fresh)
-                            pu_roll(text, s, L, K, [&](u64 j, u64 xj) {
+                            roll_windows(text, s, L, K, [&](u64 j, u64 xj) {
                                 u64 kj; u32 pj;
                                 pu_orient(K, o, L, j, xj, kj, pj);
                                 if (base < cap) { coords[base] = d + pj; kmers[base] = kj; }
@@ -196,7 +169,8 @@ __global__ __launch_bounds__(256) void pileup_kernel(BaitView bt, const u8* __re
                     }
                     if (has) t++;
                 }
-            }
+                return false;
+            });
         }
     }
 }

@@ -19,6 +19,7 @@
 
 #include "internal.hpp"
 #include "encode_tile.hpp"
+#include "search.hpp"
 
 namespace zk {
 
@@ -814,8 +815,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void bait_hit_kernel(const u8* __restric
             u64 x;
             u8 h = 0;
             if (window_at(img, p, K, x)) {
-                u64 lo = 0, hi = n_baits;
-                while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (baits[mid] < x) lo = mid + 1; else hi = mid; }
+                const u64 lo = lower_bound(baits, 0ull, n_baits, x);
                 h = (lo < n_baits && baits[lo] == x) ? 1 : 0;
             }
             if (t0 + p < n_bytes) hit[t0 + p] = h;

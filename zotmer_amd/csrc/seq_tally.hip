@@ -31,12 +31,6 @@ constexpr int ST_SYM_WORDS = (ST_PAD + ST_TILE) / 16 + 1, ST_BRK_WORDS = (ST_PAD
 
 __device__ __forceinline__ bool is_break(u32 ch) { return ch == '\n' || ch == '\r'; }
 
-__device__ __forceinline__ u64 wave_or_u64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-    return v;
-}
-
 // The bases that end just before text[pos], at most `need` of them, back to the nearest breaker; where the walk reaches the
 // text's start the state (sv: bases, the last one lowest; sr of them) goes on.  -> val (the last base lowest), cnt.  Called by
 // a whole wave; every lane returns the same.

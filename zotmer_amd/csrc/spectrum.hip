@@ -171,19 +171,6 @@ static_assert(SP_TILE == MERGE_TILE, "the tiles of make_partition");
 // result words (device): 0 n_shared, 1 S_min, 2 X_shared, 3 Y_shared, 4 / 5 S_xy low / high, 6 S_sqrt, 7 S_js (doubles)
 constexpr int SP_WORDS = 8;
 
-// sum over the workgroup in a fixed order (the xor tree of a wave, then the waves by number), valid in thread 0
-__device__ __forceinline__ double block_sum_f64(double v, double* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) scratch[wave] = v;
-    __syncthreads();
-    double t = 0;
-    if (threadIdx.x == 0) for (int w = 0; w < SP_NW; w++) t += scratch[w];
-    __syncthreads();
-    return t;
-}
-
 // Workgroups stride over the tiles and add their integers ONCE at the end (intersect_kernel's comment has the cost of an atomic
 // per tile); the two doubles go to the workgroup's own slot, partial[2 * blockIdx.x], and are added up in slot order by
 // spectrum_combine_kernel: the same inputs give the same bits.  A key counts as shared when both sums are non-zero (a count
@@ -284,8 +271,8 @@ __global__ __launch_bounds__(SP_BLOCK) void spectrum_kernel(const u64* __restric
     const u64 l0 = block_sum_u64(xy_lo & 0xffffffffull, scratch);
     const u64 l1 = block_sum_u64(xy_lo >> 32, scratch);
     xy_hi = block_sum_u64(xy_hi, scratch);
-    s_sqrt = block_sum_f64(s_sqrt, fscratch);
-    s_js = block_sum_f64(s_js, fscratch);
+    s_sqrt = block_sum_f64<SP_NW>(s_sqrt, fscratch);
+    s_js = block_sum_f64<SP_NW>(s_js, fscratch);
     if (tid == 0) {
         partial[2 * blockIdx.x] = s_sqrt;
         partial[2 * blockIdx.x + 1] = s_js;

@@ -23,27 +23,26 @@ namespace zk {
 __global__ __launch_bounds__(256) void strand_keys_kernel(const u8* __restrict__ text, const u64* __restrict__ lines, u64 n_reads, int K,
                                                           int reverse, u64 seed, u64 M, u64 T, u64* __restrict__ keys, u64 cap,
                                                           u64* cursor) {
-    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    const u64 nw = ((u64)gridDim.x * blockDim.x) >> 6;
-    for (u64 r = wave; r < n_reads; r += nw) {
-        const u64 b = lines[4 * r] + 1, e = lines[4 * r + 1];          // the sequence line: line 4r + 1 of the text
-        for (u64 c0 = b; c0 < e; c0 += 64) {
-            u64 x;
-            const bool valid = chunk_window(text, c0, e, K, lane, x);
+    const WaveIds w = wave_ids();
+    const int lane = w.lane;
+    for (u64 r = w.wave; r < n_reads; r += w.nw) {
+        u64 b, e;
+        seq_line(lines, r, b, e);
+        for_each_chunk(text, b, e, K, lane, [&](u64, bool valid, u64 x) {
             const u64 y = revcomp(K, x);
             const u64 c = x < y ? x : y;
             const u64 oriented = reverse ? y : x;
             const bool keep = valid && (murmer(c, seed) & M) <= T;
             const u64 kept = __ballot(keep);
-            if (kept == 0) continue;
+            if (kept == 0) return false;
             // the kept keys of the step take consecutive places: one atomic for the wave, a ballot rank for the lane
             u64 base = 0;
             if (lane == 0) base = atomicAdd((unsigned long long*)cursor, (unsigned long long)__popcll(kept));
             base = __shfl(base, 0, 64);
             const u64 q = base + popc_below(kept);
             if (keep && q < cap) keys[q] = (c << 1) | (oriented != c ? 1ull : 0ull);
-        }
+            return false;
+        });
     }
 }
 
@@ -164,17 +163,7 @@ static int strand_pairs(zk_ctx* c, const u64* keys, const void* cnts, int count_
 // ---------------------------------------------------------------------------------------
 // zk_format_pairs
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ u32 dec_digits(u64 v) {
-    u32 d = 1;
-    while (v >= 10) { v /= 10; d++; }
-    return d;
-}
-// the decimal digits of v, the last one at p[-1]; returns the position of the first
-__device__ __forceinline__ u8* put_dec(u8* p, u64 v) {
-    do { *--p = (u8)('0' + (u32)(v % 10)); v /= 10; } while (v);
-    return p;
-}
-
+// (dec_digits, put_dec: common.hpp)
 __global__ __launch_bounds__(256) void line_len_kernel(const u64* __restrict__ a, const u64* __restrict__ b, u64 n, u64* __restrict__ len) {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
         len[i] = dec_digits(a[i]) + dec_digits(b[i]) + 2;

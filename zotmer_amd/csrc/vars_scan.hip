@@ -16,6 +16,7 @@
 
 #include "internal.hpp"
 #include "compact.hpp"
+#include "search.hpp"
 
 namespace zk {
 
@@ -131,12 +132,9 @@ __global__ __launch_bounds__(VS_BLOCK) void vars_join_kernel(VarsLists L, const 
         const int total = nAt + nBt;
         int d = tid * VS_ITEMS;
         if (d > total) d = total;
-        int lo = d > nBt ? d - nBt : 0, hi = d < nAt ? d : nAt;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ka[VS_HALO_A + mid] <= kb[VS_HALO_B + d - mid - 1]) lo = mid + 1; else hi = mid;
-        }
-        int i = lo, j = d - lo;
+        int i = partition_point(d > nBt ? d - nBt : 0, d < nAt ? d : nAt,
+                                [&](int mid) { return ka[VS_HALO_A + mid] <= kb[VS_HALO_B + d - mid - 1]; });
+        int j = d - i;
 #pragma unroll 1
         for (int s = 0; s < VS_ITEMS; s++) {
             if (d + s >= total) break;
@@ -218,8 +216,7 @@ struct VarsRows {
         for (int t = 0; t < 8; t++) row[t] = 0;
         ctx[pos] = c;
         for (u64 q = e; q < L.n_sam && q < e + 4 && (L.sk[q] >> 2) == c; q++) row[L.sk[q] & 3] = vs_count(L.sc, L.sbits, q);
-        u64 lo = 0, hi = L.n_ref;          // the first reference entry of the context
-        while (lo < hi) { const u64 mid = (lo + hi) >> 1; if ((L.rk[mid] >> 2) < c) lo = mid + 1; else hi = mid; }
+        const u64 lo = partition_point(0ull, L.n_ref, [&](u64 i) { return (L.rk[i] >> 2) < c; });          // the first reference entry of the context
         for (u64 q = lo; q < L.n_ref && q < lo + 4 && (L.rk[q] >> 2) == c; q++) row[4 + (L.rk[q] & 3)] = vs_count(L.rc, L.rbits, q);
     }
 };
