@@ -204,6 +204,11 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_SEQ_TALLY 34    /* zk_sequence_tally: the tile kernel (seq_tally.hip; bytes = the text read); the one-wave state kernel is not in it */
 #define ZK_PROF_SPIKE_PAIRS 35  /* zk_spike_pairs: the write pass, one wave per pair (spikein.hip; bytes = the two texts written) */
 #define ZK_PROF_SPIKE_SIZE 36   /* zk_spike_pairs: the size pass and the two scans behind it as one record (bytes = 16 per pair) */
+#define ZK_PROF_KSNP_FLANK 37   /* zk_ksnp_flank: the search pass (ksnp.hip; 8 B read per k-mer + one ballot word per 64 written; the
+                                   directory and the compaction are not in it) */
+#define ZK_PROF_KSNP_PAIRS 38   /* zk_ksnp_components: the pair kernels, one record per size class that occurs (the first carries the
+                                   bytes: 16 per k-mer, the key read and the parent and mask words written; the time grows with the
+                                   pair tests, not with the bytes) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -662,6 +667,38 @@ int zk_spike_pairs(zk_ctx* ctx, const uint8_t* d_text, uint64_t n_text, const ui
                    const uint8_t* d_heads, const uint64_t* d_head_offs, uint64_t n_heads, uint64_t seed, int L, int64_t I, int64_t sd_q,
                    uint64_t thr_v, uint64_t thr_e, uint64_t first, uint64_t count, uint8_t* d_out1, uint64_t cap1, uint8_t* d_out2,
                    uint64_t cap2, uint64_t n_bytes[2]);
+
+/* ---- `zot ksnp`: the candidate-SNP k-mers of a set (ksnp.hip) -------------------------------------------------------------------
+ * zotmer/commands/ksnp.py: ksnp, hamming, levenshtein.  With J = (K - 1) / 2 a k-mer x has the prefix x >> 2 (J + 1) (its top
+ * K - J - 1 bases), the middle base (x >> 2 J) & 3 and a tail of J bases; a group is the k-mers of one prefix, one contiguous range
+ * of the ascending list d_kmers.
+ *
+ * zk_ksnp_flank: x is kept iff another k-mer of the set differs from it in the middle base only.  Three searches per k-mer, no
+ * atomics.
+ * zk_ksnp_components: inside every group the pairs with ham(x, y) <= d (ZK_KSNP_HAMMING, basics.ham) or lev(K, x, y) <= d
+ * (ZK_KSNP_LEVENSHTEIN, basics.lev, unit costs) are joined, and a connected component is kept iff its members carry at least two
+ * different middle bases.  d = 0 keeps nothing; d >= K is d = K (everything of a group is joined).  Every unordered pair of a
+ * group is tested once: the work is quadratic in the group size, as the reference's is, and nothing is refused for it.
+ *
+ * Both: d_out[0 .. *n_out) = the kept k-mers, ascending (the kept entries in input order).  d_kmers is taken to be strictly
+ * ascending and below 4^K (unchecked: another input gives an unspecified list, and no access outside the arrays); it is not
+ * changed.  1 <= K <= 32 and n < 2^32 - 1 (32-bit parents and directory), else ZK_EINVAL before any launch.  n = 0: ZK_OK,
+ * *n_out = 0, nothing launched.  The capacity convention above: ZK_ENOSPC with *n_out = the length needed, nothing written at or
+ * beyond cap.  The partition does not depend on the schedule (a component's root is its smallest member): the same call returns
+ * the same list.  Workspace: a bit per k-mer and a directory of at most 256 MiB (flank), 12 bytes per k-mer (components).
+ *
+ * How zk_ksnp_components cuts its work (tests place group sizes around each): groups of 1 are skipped; groups of up to
+ * ZK_KSNP_WAVE_GROUP members take one wave each and up to ZK_KSNP_LDS_GROUP one workgroup each, members and parents in LDS;
+ * larger groups are cut into tiles of ZK_KSNP_PAIR_TILE members, one workgroup per (i-tile <= j-tile) pair, parents in global
+ * memory.  The flat passes over the list work on tiles of 4096 entries. */
+#define ZK_KSNP_HAMMING 0
+#define ZK_KSNP_LEVENSHTEIN 1
+#define ZK_KSNP_WAVE_GROUP 64
+#define ZK_KSNP_LDS_GROUP 1024
+#define ZK_KSNP_PAIR_TILE 256
+int zk_ksnp_flank(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, int K, uint64_t* d_out, uint64_t cap, uint64_t* n_out);
+int zk_ksnp_components(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, int K, int metric, uint64_t d, uint64_t* d_out, uint64_t cap,
+                       uint64_t* n_out);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

@@ -32,6 +32,8 @@ PILEUP_DIAGS, PILEUP_TILE = 256, 4096           # ZK_PILEUP_DIAGS, ZK_PILEUP_TIL
 PATH_TILE, PATH_CHUNK = 4096, 256               # ZK_PATH_TILE, ZK_PATH_CHUNK
 LCP_TILE = 256                                  # ZK_LCP_TILE
 SEQTALLY_TILE = 4096                            # ZK_SEQTALLY_TILE
+KSNP_HAMMING, KSNP_LEVENSHTEIN = 0, 1           # ZK_KSNP_HAMMING, ZK_KSNP_LEVENSHTEIN
+KSNP_WAVE_GROUP, KSNP_LDS_GROUP, KSNP_PAIR_TILE = 64, 1024, 256   # ZK_KSNP_WAVE_GROUP, ZK_KSNP_LDS_GROUP, ZK_KSNP_PAIR_TILE
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -194,6 +196,8 @@ SIGNATURES = {
     "zk_spike_zone_counts": (_i, [_vp, _vp, _u64, _u64, _u64, _u64, _vp]),
     "zk_spike_pairs": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _u64, _i, C.c_int64, C.c_int64, _u64, _u64, _u64, _u64,
                             _vp, _u64, _vp, _u64, _pu64]),
+    "zk_ksnp_flank": (_i, [_vp, _vp, _u64, _i, _vp, _u64, _pu64]),
+    "zk_ksnp_components": (_i, [_vp, _vp, _u64, _i, _i, _u64, _vp, _u64, _pu64]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
     "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
@@ -464,7 +468,7 @@ class Context:
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
                  "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26,
                  "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31, "lcp_resolve": 32, "scan_place": 33,
-                 "seq_tally": 34, "spike_pairs": 35, "spike_size": 36}
+                 "seq_tally": 34, "spike_pairs": 35, "spike_size": 36, "ksnp_flank": 37, "ksnp_pairs": 38}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -1201,6 +1205,31 @@ class Context:
             nb, fit = self.spike_pairs_into(*args, o1, o2)
             assert fit
         return o1.view(nb[0]), o2.view(nb[1])
+
+    # ---- candidate-SNP k-mers of a set (csrc/ksnp.hip) ---------------------------------------------------------------
+    def ksnp_into(self, kmers, K, out, metric=None, d=0):
+        """zk_ksnp_flank (metric None) or zk_ksnp_components (KSNP_HAMMING / KSNP_LEVENSHTEIN, distance d) into the uint64 array
+        given -> (k-mers written or, if they did not fit, needed; whether they fit)"""
+        assert kmers.dtype.itemsize == 8 and out.dtype.itemsize == 8
+        n = C.c_uint64(0)
+        if metric is None:
+            rc = self.lib.zk_ksnp_flank(self.h, kmers.ptr, kmers.n, int(K), out.ptr, out.n, C.byref(n))
+        else:
+            rc = self.lib.zk_ksnp_components(self.h, kmers.ptr, kmers.n, int(K), int(metric), min(int(d), 1 << 62), out.ptr, out.n, C.byref(n))
+        if rc != ZK_ENOSPC:
+            self._check(rc)
+        return n.value, rc == ZK_OK
+
+    def ksnp(self, kmers, K, metric=None, d=0, out=None):
+        """ascending k-mers of a set -> the candidate-SNP k-mers among them, ascending, as a uint64 DeviceArray view.  out: an
+        array to write into first; one retry with the length the entry reports when it is too small."""
+        o = out if out is not None else self.empty(max(kmers.n // 8, 1024), np.uint64)
+        n, fit = self.ksnp_into(kmers, K, o, metric, d)
+        if not fit:
+            o = self.empty(n, np.uint64)
+            n, fit = self.ksnp_into(kmers, K, o, metric, d)
+            assert fit
+        return o.view(n)
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
