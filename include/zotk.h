@@ -209,6 +209,11 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_KSNP_PAIRS 38   /* zk_ksnp_components: the pair kernels, one record per size class that occurs (the first carries the
                                    bytes: 16 per k-mer, the key read and the parent and mask words written; the time grows with the
                                    pair tests, not with the bytes) */
+#define ZK_PROF_STOP_FRAMES 39  /* zk_stop_frames: the lookup, draw and count kernel, one wave per read (stop_frames.hip; bytes = the
+                                   text read + 16 B written per read; the long-line pass and the scan are not in it) */
+#define ZK_PROF_STOP_EMIT 40    /* zk_stop_frames: the emit kernel (16 B read per read, 12 B written per stop + the text of the reads
+                                   that have one) */
+#define ZK_PROF_STOP_NEAREST 41 /* zk_stop_nearest: the one kernel (25 B per entry; the time grows with the pair tests) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -699,6 +704,56 @@ int zk_spike_pairs(zk_ctx* ctx, const uint8_t* d_text, uint64_t n_text, const ui
 int zk_ksnp_flank(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, int K, uint64_t* d_out, uint64_t cap, uint64_t* n_out);
 int zk_ksnp_components(zk_ctx* ctx, const uint64_t* d_kmers, uint64_t n, int K, int metric, uint64_t d, uint64_t* d_out, uint64_t cap,
                        uint64_t* n_out);
+
+/* ---- `zot stop`: in-frame stop codons of reads placed on transcripts (stop_frames.hip; commands/stop.py:112-158) ---------------
+ * The reference keeps frameAnchors[x] = {(name, q)} for every K-mer of its transcripts.  Per read (single reads) the windows
+ * (x_j, p = j) are orientation 0 and (rc x_j, p = L - j - K) orientation 1, as zk_anchor_pileup cuts them (the stripped
+ * sequence line, restarts after a byte outside AaCcGgTtUu).  Every pair (window (x, p) of orientation i, anchor (name, q) of x)
+ * is one vote for the frame (name, o = q - p, i), with multiplicity; n = the votes.  One frame is drawn with probability
+ * votes / n; every window (x, p) of the drawn orientation with (p + o + K - 3) mod 3 == 0 and x & 63 in {TAA, TAG, TGA} is
+ * one stop (name, x).
+ *
+ * The draw: the frames ascend by (name, o, i), names as bytes; read g (its 0-based ordinal over the whole run) draws the
+ * frame that holds the vote of rank r = mulhi64(rnd(seed, 24, g) & ~2047, n) = ((R >> 11) * n) >> 53 in that order, with rnd
+ * the counter-based generator of zotmer_amd/synth.py -- floor(u n) for the 53-bit fraction u = (R >> 11) / 2^53, which is the
+ * frame the reference's walk picks when its random.random() returns u.  Integers only.
+ *
+ * zk_stop_frames: `anchors` is a bait table whose ids are anchors on one u32 axis (zk_bait_table_from_arrays), the transcripts
+ * laid out in ascending byte order of their names, pad free coordinates before the first and at least 2 * pad between two;
+ * d_starts[0, n_tx) = the coordinate of position 0 of every transcript, ascending.  The transcript of a diagonal d = a - p is
+ * then the last t with d_starts[t] <= d + pad, o = d - d_starts[t] (negative where the read overhangs the start), and a frame's
+ * sort key is (d << 1) | i.  `first` = the ordinal g of the batch's first read: a run cut at any read numbers into several
+ * calls gives the multiset of one call.  Output: the stops as (transcript index, k-mer) in d_tx / d_kmers, in no specified
+ * order (zk_pileup_count sorts and counts them as they are).
+ *   - 3 <= K <= 32 and K equal to the table's, else ZK_EINVAL before any launch.
+ *   - A line longer than pad with a hit (in either orientation) is ZK_ERANGE, found by a pass of its own before anything is
+ *     written.  2^32 stops or more in one batch is ZK_ERANGE.
+ *   - The capacity convention: ZK_ENOSPC with *n_out = the stops when they exceed cap, nothing written at all, repeatable
+ *     with room.
+ *   - Exact for any number of votes.  A read whose votes share one key (the common one) needs no selection; otherwise the
+ *     drawn key is the smallest k with #(votes <= k) > r, found by bisection: over the keys of the read kept in LDS when there
+ *     are at most ZK_STOP_VOTES of them, and by walking the read's windows again for every probe when there are more (tests
+ *     straddle the bound).
+ *   - An empty table, n_tx = 0, n_reads = 0, lines shorter than K: nothing is emitted.  A count pass, a scan and an emit
+ *     pass: no atomics, no float, the same call returns the same pairs in the same places.  Workspace: 16 bytes per read.
+ *
+ * zk_stop_nearest: d_tx / d_kmers[0, m) = the counted stops ascending by (transcript, k-mer), as zk_pileup_count leaves them;
+ * d_tk[d_tk_offs[t], d_tk_offs[t + 1]) = the distinct k-mers of transcript t, ascending (n_tx + 1 offsets); d_known[0, n_known)
+ * = the known stops, ascending.  Per entry i: d_dist[i] = min over y of the transcript of ham(x >> 3, y >> 3) (basics.ham; the
+ * shift by three BITS is the reference's nearest3), d_near[i] = the y that gives it, the smallest among ties, d_flags[i] = 1
+ * iff x is in d_known.  A transcript without k-mers (or an index >= n_tx) gives d_dist = K + 1, d_near = x, nearest3's
+ * initial values.  m = 0: nothing launched.  3 <= K <= 32 else ZK_EINVAL.  m * |transcript| pair tests: a workgroup takes
+ * ZK_STOP_NEAR_ENTRIES entries, one per lane, and streams the k-mers of each of their transcripts through LDS in tiles of
+ * ZK_STOP_NEAR_TILE.  No atomics; the same call returns the same bits. */
+#define ZK_STOP_VOTES 512
+#define ZK_STOP_NEAR_ENTRIES 64
+#define ZK_STOP_NEAR_TILE 1024
+int zk_stop_frames(zk_ctx* ctx, const zk_bait_table* anchors, const uint32_t* d_starts, uint64_t n_tx, const uint8_t* d_text,
+                   const uint64_t* d_lines, uint64_t n_reads, int K, uint32_t pad, uint64_t seed, uint64_t first, uint32_t* d_tx,
+                   uint64_t* d_kmers, uint64_t cap, uint64_t* n_out);
+int zk_stop_nearest(zk_ctx* ctx, const uint32_t* d_tx, const uint64_t* d_kmers, uint64_t m, int K, const uint64_t* d_tk,
+                    const uint64_t* d_tk_offs, uint64_t n_tx, const uint64_t* d_known, uint64_t n_known, uint32_t* d_dist,
+                    uint64_t* d_near, uint8_t* d_flags);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

@@ -34,6 +34,7 @@ LCP_TILE = 256                                  # ZK_LCP_TILE
 SEQTALLY_TILE = 4096                            # ZK_SEQTALLY_TILE
 KSNP_HAMMING, KSNP_LEVENSHTEIN = 0, 1           # ZK_KSNP_HAMMING, ZK_KSNP_LEVENSHTEIN
 KSNP_WAVE_GROUP, KSNP_LDS_GROUP, KSNP_PAIR_TILE = 64, 1024, 256   # ZK_KSNP_WAVE_GROUP, ZK_KSNP_LDS_GROUP, ZK_KSNP_PAIR_TILE
+STOP_VOTES, STOP_NEAR_ENTRIES, STOP_NEAR_TILE = 512, 64, 1024    # ZK_STOP_VOTES, ZK_STOP_NEAR_ENTRIES, ZK_STOP_NEAR_TILE
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -198,6 +199,8 @@ SIGNATURES = {
                             _vp, _u64, _vp, _u64, _pu64]),
     "zk_ksnp_flank": (_i, [_vp, _vp, _u64, _i, _vp, _u64, _pu64]),
     "zk_ksnp_components": (_i, [_vp, _vp, _u64, _i, _i, _u64, _vp, _u64, _pu64]),
+    "zk_stop_frames": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _i, _u32, _u64, _u64, _vp, _vp, _u64, _pu64]),
+    "zk_stop_nearest": (_i, [_vp, _vp, _vp, _u64, _i, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
     "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
@@ -468,7 +471,8 @@ class Context:
                  "capture_hits": 15, "project_sum": 16, "spectrum": 17, "strand_keys": 18, "strand_pairs": 19, "format_pairs": 20,
                  "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26,
                  "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31, "lcp_resolve": 32, "scan_place": 33,
-                 "seq_tally": 34, "spike_pairs": 35, "spike_size": 36, "ksnp_flank": 37, "ksnp_pairs": 38}
+                 "seq_tally": 34, "spike_pairs": 35, "spike_size": 36, "ksnp_flank": 37, "ksnp_pairs": 38,
+                 "stop_frames": 39, "stop_emit": 40, "stop_nearest": 41}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -1230,6 +1234,43 @@ class Context:
             n, fit = self.ksnp_into(kmers, K, o, metric, d)
             assert fit
         return o.view(n)
+
+    # ---- in-frame stop codons of reads placed on transcripts (csrc/stop_frames.hip) ----------------------------------
+    def stop_frames_into(self, table, starts, text, lines, n_reads, K, pad, seed, first, out_tx, out_kmers):
+        """zk_stop_frames into the arrays given -> (stops written or, if they did not fit, needed; whether they fit)"""
+        assert 4 * n_reads <= lines.n and starts.dtype.itemsize == 4
+        assert out_tx.dtype.itemsize == 4 and out_kmers.dtype.itemsize == 8
+        n = C.c_uint64(0)
+        rc = self.lib.zk_stop_frames(self.h, table.h, starts.ptr, starts.n, text.ptr, lines.ptr, int(n_reads), int(K), int(pad),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), out_tx.ptr, out_kmers.ptr, min(out_tx.n, out_kmers.n), C.byref(n))
+        if rc != ZK_ENOSPC:
+            self._check(rc)
+        return n.value, rc == ZK_OK
+
+    def stop_frames(self, table, starts, text, lines, n_reads, K, pad, seed, first, out=None):
+        """a batch of single FASTQ reads, the first of which is read `first` of the run, against a table whose ids are anchors
+        on an axis of transcripts in name order (starts: u32, position 0 of each) -> (transcript indices u32 view, k-mers u64
+        view): the in-frame stops of the frame drawn for every read, in no order (zk_stop_frames).  out: (tx, kmers) arrays
+        to write into first; one retry with the length the entry reports when they are too small."""
+        ot, ok = out if out is not None else (self.empty(max(n_reads, 1024), np.uint32), self.empty(max(n_reads, 1024), np.uint64))
+        n, fit = self.stop_frames_into(table, starts, text, lines, n_reads, K, pad, seed, first, ot, ok)
+        if not fit:
+            ot, ok = self.empty(n, np.uint32), self.empty(n, np.uint64)
+            n, fit = self.stop_frames_into(table, starts, text, lines, n_reads, K, pad, seed, first, ot, ok)
+            assert fit
+        return ot.view(n), ok.view(n)
+
+    def stop_nearest(self, tx, kmers, K, tk, tk_offs, known):
+        """counted stops ascending by (transcript, k-mer) + every transcript's distinct k-mers (tk u64 ascending per transcript,
+        tk_offs u64[n_tx + 1]) + the known stops (u64 ascending) -> (distances u32, nearest k-mers u64, known flags u8)
+        (zk_stop_nearest)"""
+        assert tx.n == kmers.n and tx.dtype.itemsize == 4 and kmers.dtype.itemsize == 8
+        assert tk.dtype.itemsize == 8 and tk_offs.dtype.itemsize == 8 and known.dtype.itemsize == 8 and tk_offs.n >= 1
+        m = tx.n
+        dist, near, flags = self.empty(m, np.uint32), self.empty(m, np.uint64), self.empty(m, np.uint8)
+        self._check(self.lib.zk_stop_nearest(self.h, tx.ptr, kmers.ptr, m, int(K), tk.ptr, tk_offs.ptr, tk_offs.n - 1, known.ptr, known.n,
+                                             dist.ptr, near.ptr, flags.ptr))
+        return dist, near, flags
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)

@@ -200,3 +200,17 @@ def spike_zone_of(seed, n, cum):
     """the zone of draw n: rnd(seed, T_ZONE, n) % T looked up in the inclusive cumulative zone lengths"""
     import bisect
     return bisect.bisect_right(cum, rnd_int(seed, T_ZONE, n) % cum[-1])
+
+
+# ---- the frame draw of `zot stop`; the HIP version is csrc/stop_frames.hip -----------------------------------
+T_STOP = 24
+
+
+def stop_fraction(seed, g):
+    """the 53-bit numerator of read g's uniform draw: u = stop_fraction / 2^53 is an exact double in [0, 1)"""
+    return rnd_int(seed, T_STOP, g) >> 11
+
+
+def stop_draw(seed, g, n):
+    """the rank, among the n votes of read g ordered by frame, of the vote whose frame is drawn: floor(u * n)"""
+    return (stop_fraction(seed, g) * int(n)) >> 53
