@@ -105,7 +105,9 @@ int zk_host_alloc(zk_ctx* ctx, uint64_t bytes, void** ptr);
 int zk_host_free(zk_ctx* ctx, void* ptr);
 int zk_upload_async(zk_ctx* ctx, void* d_dst, const void* src, uint64_t bytes);
 
-/* Tuning knobs (performance only; results never depend on them). */
+/* Tuning knobs (performance only; results never depend on them: tests/test_gpu_knobs.py holds the library to it -- zk_kmerize under a
+ * covering array of every two knobs' values and under every sort geometry, every core entry under the knobs its own tests leave
+ * alone -- and tests/_knob_cases.py is the table of the knobs, their defaults and the values crossed). */
 #define ZK_TUNE_SORT_VARIANT 1   /* radix-sort geometry index for key arrays, see radix_sort.hip */
 #define ZK_TUNE_PAIRS_VARIANT 2  /* ... for (key, payload) pairs */
 #define ZK_TUNE_SHORT_SORT 3     /* zk_kmerize: 1 = sort only the top ~log2(n)+3 bits, finish in the mirror stage (default 0) */

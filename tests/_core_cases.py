@@ -238,11 +238,30 @@ def capture_case():
     return text.encode(), baits, pairs, raw, gathered, n_hit
 
 
-@functools.lru_cache(maxsize=None)
-def kmerize_reads(name):
+DENSE_PREFIX = "AAAAAAAAA"
+
+
+def dense_block(rnd, K, n=14000):
+    """n reads of K bases that share their first nine, each given twice (rnd(m): m random bases): n distinct canonical k-mers in ONE
+    block of the 18-bit plan of zk_kmerize, 1.7 times a tile of the block dedupe at 14 000 (their mirror images are spread over
+    random blocks).  Shared by tests/test_gpu_strand_blocks.py (`dense_block`) and the `dense` input below."""
+    return [DENSE_PREFIX + rnd(K - len(DENSE_PREFIX)) for _ in range(n)] * 2
+
+
+def kmerize_reads(name, K=None):
     """deep: ~60x over a genome of 12 000 bases, it repeats its k-mers; flat: random reads, no repeats.  Both end with 64 reads that
     hold a palindromic 24-mer each (a 12-mer and its reverse complement between random flanks; twenty copies of them in `deep`):
-    random reads have none, and at even K the table is shorter than twice the canonical list only where there are some"""
+    random reads have none, and at even K the table is shorter than twice the canonical list only where there are some.
+    dense (needs K): the first 3000 reads of `deep` and a dense_block of K-base reads -- a declined block on the forced block plans"""
+    return _kmerize_reads(name, K if name == "dense" else None)
+
+
+@functools.lru_cache(maxsize=None)
+def _kmerize_reads(name, K):
+    if name == "dense":
+        assert K is not None and K > len(DENSE_PREFIX), "the dense input is built for one K"
+        drng = random.Random(79 + K)
+        return _kmerize_reads("deep", None)[:3000] + dense_block(lambda m: "".join(drng.choice("ACGT") for _ in range(m)), K)
     rng = random.Random(78)
     comp = str.maketrans("ACGT", "TGCA")
 
@@ -260,9 +279,11 @@ def kmerize_reads(name):
 @functools.lru_cache(maxsize=None)
 def kmerize_want(name, K, flags):
     """(k-mers, counts, the capacity the call needs).  With ZK_KMERIZE_SUBSAMPLE the capacity is that of the table BEFORE the
-    subsample, which is applied to the counted table in the caller's arrays."""
-    reads = kmerize_reads(name)
-    full = zo.kmerize(K, reads)
+    subsample, which is applied to the counted table in the caller's arrays.  name: deep, flat or dense; flags: canonical, both (the
+    same table), canonical_only, subsample (p 0.5, seed 3)"""
+    assert flags in ("canonical", "both", "canonical_only", "subsample"), flags
+    reads = kmerize_reads(name, K)
+    full = _kmerize_full(name, K)
     wk, wc = full["kmers"], full["counts"]
     if flags == "subsample":
         sub = zo.kmerize(K, reads, 1, 0.5, 3)
@@ -274,3 +295,20 @@ def kmerize_want(name, K, flags):
         cc[ck == rc[keep]] //= 2
         return ck, cc, len(ck)
     return wk, wc, len(wk)
+
+
+@functools.lru_cache(maxsize=None)
+def _kmerize_full(name, K):
+    """the oracle's table of both strands, computed once per input and K"""
+    return zo.kmerize(K, kmerize_reads(name, K))
+
+
+@functools.lru_cache(maxsize=None)
+def kmerize_facts(name, K):
+    """what zk_kmerize_stats must say of the input on every plan: dict(n_windows, n_instances, n_canonical, acgt).  n_canonical: the
+    entries of the table that are not above their reverse complement (a palindrome is one entry, and canonical)"""
+    full = _kmerize_full(name, K)
+    wk = np.asarray(full["kmers"], dtype=U64)
+    inst = int(np.asarray(full["counts"], dtype=U64).sum())          # two emissions per valid window
+    assert inst % 2 == 0 and sum(full["acgt"]) == inst
+    return dict(n_windows=inst // 2, n_instances=inst, n_canonical=int(np.count_nonzero(wk <= revcomp(wk, K))), acgt=list(full["acgt"]))

@@ -861,13 +861,13 @@ def facts_of(reads, K):
 
 @functools.lru_cache(maxsize=None)
 def stream_facts(inp, K):
-    return facts_of(cc.kmerize_reads(inp), K)
+    return facts_of(cc.kmerize_reads(inp, K), K)
 
 
 def kmerize_spec(inp, K, flags, knobs, reads=None):
     if reads is None:
         wk, wc, needed = cc.kmerize_want(inp, K, flags)
-        reads = cc.kmerize_reads(inp)
+        reads = cc.kmerize_reads(inp, K)
         windows, acgt = stream_facts(inp, K)
     else:
         full = zo.kmerize(K, reads)

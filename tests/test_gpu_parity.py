@@ -11,11 +11,12 @@ import pytest
 
 from oracle import zkoracle as zo
 from tests import _golden as G
+from tests._knob_cases import DEFAULTS
 from zotmer_amd import native, synth
 
 pytestmark = pytest.mark.gpu
-DEFAULT_SORT_VARIANT = 3       # zk_ctx defaults (internal.hpp)
-DEFAULT_PAIRS_VARIANT = 7
+DEFAULT_SORT_VARIANT = DEFAULTS["sort_variant"]       # zk_ctx defaults (internal.hpp; tests/test_knob_cases_host.py compares them)
+DEFAULT_PAIRS_VARIANT = DEFAULTS["pairs_variant"]
 
 
 @pytest.fixture(scope="module")

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import zkoracle as zo
+from tests import _core_cases as cc
 from zotmer_amd import native, synth
 
 pytestmark = pytest.mark.gpu
@@ -38,8 +39,8 @@ def _inputs(K):
     def rnd(n):
         return "".join(rng.choice(list("ACGT"), size=n))
     # 14 000 distinct canonical k-mers under one 9-base prefix: one block of the counted list 1.7 times a tile (their mirror images
-    # spread over random blocks)
-    dense = deep + ["AAAAAAAAA" + rnd(K - 9) for _ in range(14000)] * 2
+    # spread over random blocks); the builder is shared with the `dense` input of tests/_core_cases.py
+    dense = deep + cc.dense_block(rnd, K)
     # 60 000 under one prefix: 7 times a tile
     big_c = deep + ["AAAAAAAAA" + rnd(K - 9) for _ in range(60000)] * 2
     # 60 000 canonical k-mers that end in GGGGGGGGG: their mirror images all sit in block CCCCCCCCC, 7 times a tile
