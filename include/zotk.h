@@ -48,6 +48,7 @@
  *         zk_format_pairs         d_out                             any address
  *         zk_contig_render        d_out                             any address
  *         zk_spike_pairs          d_text, d_heads, d_out1, d_out2   any address
+ *         zk_fizzle_votes         d_text1, d_text2                  any address
  *         zk_copy                 d_dst, d_src                      any address, any byte count
  *     An entry writes only the elements [0, result length) of its outputs and never more than [0, cap) -- nothing in front of the
  *     pointer, nothing behind the result but what the capacity convention below allows (the work space of zk_capture_hits and of
@@ -216,6 +217,10 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_STOP_EMIT 40    /* zk_stop_frames: the emit kernel (16 B read per read, 12 B written per stop + the text of the reads
                                    that have one) */
 #define ZK_PROF_STOP_NEAREST 41 /* zk_stop_nearest: the one kernel (25 B per entry; the time grows with the pair tests) */
+#define ZK_PROF_FIZZLE_COUNT 42 /* zk_fizzle_votes: the lookup-and-count kernel, one wave per pair (fizzle.hip; bytes = the two texts read
+                                   + 16 B written per record; the scan is not in it) */
+#define ZK_PROF_FIZZLE_EMIT 43  /* zk_fizzle_votes: the pass after the decision as one record, the adds of the one-class records and the
+                                   emit kernel (16 B read per record, 12 B written per entry + the text of the pairs that have one) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -756,6 +761,38 @@ int zk_stop_frames(zk_ctx* ctx, const zk_bait_table* anchors, const uint32_t* d_
 int zk_stop_nearest(zk_ctx* ctx, const uint32_t* d_tx, const uint64_t* d_kmers, uint64_t m, int K, const uint64_t* d_tk,
                     const uint64_t* d_tk_offs, uint64_t n_tx, const uint64_t* d_known, uint64_t n_known, uint32_t* d_dist,
                     uint64_t* d_near, uint8_t* d_flags);
+
+/* ---- `zot fizzle`: the exon-tuple classes that read pairs hit (fizzle.hip; commands/fizzle.py:354-371, 555-583) -----------------
+ * The reference keeps idx[x] = the ascending tuple of the exons that hold K-mer x (forward strand only).  Per read pair it makes
+ * two records -- orientation 0: the forward windows of mate 1 and the reverse-complement windows of mate 2, orientation 1: the
+ * reverse complements of mate 1 and the forward windows of mate 2 -- and recHits starts from sdx = {tuple: the windows of the
+ * record that have it, with multiplicity}.  The host numbers the distinct tuples as classes; this entry computes sdx.
+ *
+ * zk_fizzle_votes: `classes` is a bait table (zk_bait_table_from_arrays) in which every key lists exactly one id, its class;
+ * n_classes = its record count.  Texts and lines as zk_capture_hits takes them (FASTQ text, zk_line_ends, at least 4 * n_reads
+ * lines each); both mates are required.  Record 2 p + o is orientation o of pair p of the batch; its windows are cut as
+ * zk_anchor_pileup cuts them (the stripped sequence line, restarts after a byte outside AaCcGgTtUu).
+ *   - A record with hits in exactly one class c adds 1 to d_single[2 c], its hits to d_single[2 c + 1] and 1 to
+ *     d_hist[min(hits, n_hist - 1)], and writes nothing else.  A record with hits in two or more classes writes one entry
+ *     (record, class, hits) per class into d_rec / d_cls / d_cnt and adds nothing.  A record without hits does nothing.
+ *   - The entries ascend by record and, within a record, by class: a count pass, a scan, then the writes, every record at its own
+ *     offset, so the same call leaves the same bytes.  d_single (2 words a class) and d_hist (n_hist words) are ADDED TO with
+ *     64-bit integer atomics: totals do not depend on the schedule, and a batch cut anywhere into several calls gives the totals
+ *     of one call.  No float.
+ *   - The capacity convention, and more: ZK_ENOSPC with *n_out = the entries needed when they exceed cap; then nothing is written
+ *     to the three lists and nothing is added to d_single or d_hist -- the adds belong to the pass after the decision -- so the
+ *     repeat with room counts once.
+ *   - ZK_EINVAL before any launch: K outside 1..32, K other than the table's, n_classes other than the table's record count, a
+ *     null array that would be used, n_hist == 0 with n_reads > 0.  2 * n_reads >= 2^32 is ZK_ERANGE (record numbers are u32).
+ *   - An empty table, n_reads == 0, lines shorter than K: nothing is added or written, *n_out = 0.
+ *   - Exact for any number of distinct classes in a record: up to ZK_FIZZLE_CLASSES they are held in LDS; a record with more is
+ *     walked again once per class, the classes taken in ascending order (tests straddle the bound).
+ *   - Workspace: 32 bytes per read pair (16 per record: its entries, its class, its hits). */
+#define ZK_FIZZLE_CLASSES 512
+int zk_fizzle_votes(zk_ctx* ctx, const zk_bait_table* classes, int K, const uint8_t* d_text1, const uint64_t* d_lines1,
+                    const uint8_t* d_text2, const uint64_t* d_lines2, uint64_t n_reads, uint64_t n_classes, uint64_t* d_single,
+                    uint64_t* d_hist, uint64_t n_hist, uint32_t* d_rec, uint32_t* d_cls, uint32_t* d_cnt, uint64_t cap,
+                    uint64_t* n_out);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

@@ -35,6 +35,7 @@ SEQTALLY_TILE = 4096                            # ZK_SEQTALLY_TILE
 KSNP_HAMMING, KSNP_LEVENSHTEIN = 0, 1           # ZK_KSNP_HAMMING, ZK_KSNP_LEVENSHTEIN
 KSNP_WAVE_GROUP, KSNP_LDS_GROUP, KSNP_PAIR_TILE = 64, 1024, 256   # ZK_KSNP_WAVE_GROUP, ZK_KSNP_LDS_GROUP, ZK_KSNP_PAIR_TILE
 STOP_VOTES, STOP_NEAR_ENTRIES, STOP_NEAR_TILE = 512, 64, 1024    # ZK_STOP_VOTES, ZK_STOP_NEAR_ENTRIES, ZK_STOP_NEAR_TILE
+FIZZLE_CLASSES = 512                            # ZK_FIZZLE_CLASSES
 DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
@@ -201,6 +202,7 @@ SIGNATURES = {
     "zk_ksnp_components": (_i, [_vp, _vp, _u64, _i, _i, _u64, _vp, _u64, _pu64]),
     "zk_stop_frames": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _i, _u32, _u64, _u64, _vp, _vp, _u64, _pu64]),
     "zk_stop_nearest": (_i, [_vp, _vp, _vp, _u64, _i, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "zk_fizzle_votes": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _pu64]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
     "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
@@ -472,7 +474,7 @@ class Context:
                  "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26,
                  "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31, "lcp_resolve": 32, "scan_place": 33,
                  "seq_tally": 34, "spike_pairs": 35, "spike_size": 36, "ksnp_flank": 37, "ksnp_pairs": 38,
-                 "stop_frames": 39, "stop_emit": 40, "stop_nearest": 41}
+                 "stop_frames": 39, "stop_emit": 40, "stop_nearest": 41, "fizzle_count": 42, "fizzle_emit": 43}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -1271,6 +1273,33 @@ class Context:
         self._check(self.lib.zk_stop_nearest(self.h, tx.ptr, kmers.ptr, m, int(K), tk.ptr, tk_offs.ptr, tk_offs.n - 1, known.ptr, known.n,
                                              dist.ptr, near.ptr, flags.ptr))
         return dist, near, flags
+
+    # ---- exon-tuple classes hit by read pairs (csrc/fizzle.hip) -----------------------------------------------------
+    def fizzle_votes_into(self, table, K, text1, lines1, text2, lines2, n_reads, single, hist, out_rec, out_cls, out_cnt):
+        """zk_fizzle_votes: single (u64[2 * classes]) and hist (u64) are added to, the entries go into the three u32 arrays
+        given -> (entries written or, if they did not fit, needed; whether they fit -- if not, nothing was added either)"""
+        assert 4 * n_reads <= lines1.n and 4 * n_reads <= lines2.n and single.dtype.itemsize == 8 and hist.dtype.itemsize == 8
+        assert single.n >= 2 * table.n_records and out_rec.dtype.itemsize == 4 and out_cls.dtype.itemsize == 4 and out_cnt.dtype.itemsize == 4
+        n = C.c_uint64(0)
+        rc = self.lib.zk_fizzle_votes(self.h, table.h, int(K), text1.ptr, lines1.ptr, text2.ptr, lines2.ptr, int(n_reads), table.n_records,
+                                      single.ptr, hist.ptr, hist.n, out_rec.ptr, out_cls.ptr, out_cnt.ptr,
+                                      min(out_rec.n, out_cls.n, out_cnt.n), C.byref(n))
+        if rc != ZK_ENOSPC:
+            self._check(rc)
+        return n.value, rc == ZK_OK
+
+    def fizzle_votes(self, table, K, text1, lines1, text2, lines2, n_reads, single, hist, out=None):
+        """a batch of FASTQ read pairs against a table whose every key lists its class: the records with one class are added to
+        single and hist, the others come back as (records, classes, hits) u32 views, ascending by (record, class); record 2 p + o
+        = orientation o of pair p (zk_fizzle_votes).  out: (rec, cls, cnt) arrays to write into first; one retry with the length
+        the entry reports when they are too small."""
+        o = out if out is not None else tuple(self.empty(4 * n_reads + 1024, np.uint32) for _ in range(3))
+        n, fit = self.fizzle_votes_into(table, K, text1, lines1, text2, lines2, n_reads, single, hist, *o)
+        if not fit:
+            o = tuple(self.empty(n, np.uint32) for _ in range(3))
+            n, fit = self.fizzle_votes_into(table, K, text1, lines1, text2, lines2, n_reads, single, hist, *o)
+            assert fit
+        return tuple(a.view(n) for a in o)
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)
