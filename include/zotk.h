@@ -49,6 +49,8 @@
  *         zk_contig_render        d_out                             any address
  *         zk_spike_pairs          d_text, d_heads, d_out1, d_out2   any address
  *         zk_fizzle_votes         d_text1, d_text2                  any address
+ *         zk_hgvs_draw            d_text, d_pool                    any address
+ *         zk_hgvs_render          d_text, d_pool, d_accs, d_names, d_out   any address
  *         zk_copy                 d_dst, d_src                      any address, any byte count
  *     An entry writes only the elements [0, result length) of its outputs and never more than [0, cap) -- nothing in front of the
  *     pointer, nothing behind the result but what the capacity convention below allows (the work space of zk_capture_hits and of
@@ -221,6 +223,10 @@ int zk_tune(zk_ctx* ctx, int what, int value);
                                    + 16 B written per record; the scan is not in it) */
 #define ZK_PROF_FIZZLE_EMIT 43  /* zk_fizzle_votes: the pass after the decision as one record, the adds of the one-class records and the
                                    emit kernel (16 B read per record, 12 B written per entry + the text of the pairs that have one) */
+#define ZK_PROF_HGVS_DRAW 44    /* zk_hgvs_draw: the draw kernel and the scan behind it as one record (hgvs_gen.hip; bytes = 64 per variant) */
+#define ZK_PROF_HGVS_FILL 45    /* zk_hgvs_draw: the fill kernel (104 B per variant read and written + the pool bytes) */
+#define ZK_PROF_HGVS_SIZE 46    /* zk_hgvs_render: the size pass and the scan behind it as one record (bytes = 64 per row) */
+#define ZK_PROF_HGVS_RENDER 47  /* zk_hgvs_render: the write pass (56 B read per row + the text written) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -793,6 +799,75 @@ int zk_fizzle_votes(zk_ctx* ctx, const zk_bait_table* classes, int K, const uint
                     const uint8_t* d_text2, const uint64_t* d_lines2, uint64_t n_reads, uint64_t n_classes, uint64_t* d_single,
                     uint64_t* d_hist, uint64_t n_hist, uint32_t* d_rec, uint32_t* d_cls, uint32_t* d_cnt, uint64_t cap,
                     uint64_t* n_out);
+
+/* ---- `zot hgvs-gen`: random variants over zones, as HGVS lines (hgvs_gen.hip) ---------------------------------------------------
+ * zotmer/commands/hgvs-gen.py:120-171 and :257-271, zotmer/library/hgvs.py, with the draws of zotmer_amd/synth.py: rnd(seed, tag,
+ * index), integers only.  Variants are numbered v in output order; zk_spike_zone_counts spreads them over the zones.
+ *
+ * Shared tables.  d_zones holds 3 words a zone, {offset of its window in d_text, s, e}: the window is seq[s .. e] of the zone's
+ * chromosome, both ends inclusive, raw bytes of any case.  d_first: n_zones + 1 ascending variant numbers, variant v belongs to
+ * the zone z with d_first[z] <= v < d_first[z + 1].  A row is ZK_HGVS_ROW_WORDS words: {kind, zone, p, q, m, pool offset}, kind
+ * one of ZK_HGVS_SUB .. ZK_HGVS_AND, p and q 0-based positions on the chromosome (q = p for sub, ins and ani), m the inserted
+ * length (1 for a sub, 0 for del and dup); the pool holds the alternative base of a sub and the m bases of an ins or a delins.
+ *
+ * zk_hgvs_draw: the rows of the variants [first, first + count) to d_rows, their bases to d_pool (offsets from 0 in every call).
+ *   - kind: the first k with the low 32 bits of rnd(seed, 25, v) below type_thr[k] (7 ascending thresholds, the last 2^32).
+ *   - p = s + rnd(seed, 26, 64 v + t) % (e - s + 1) with t = 0; a sub takes the first of t = 0 .. 63 whose upper-cased base is one
+ *     of ACGT and, if none is, the first such base after try 63, going round the zone once; its alternative base is element
+ *     rnd(seed, 31, v) % 3 of the other three of ACGT.
+ *   - geom(k, r) = 1 + the entries above the low 32 bits of r of table k; the three descending tables (of -D, -I and -U, geom_n
+ *     entries each, at most ZK_HGVS_TABLE_MAX) stand one after the other in d_geom.  del: q = min(p + geom(0, rnd(seed, 27, v)),
+ *     e); dup: the same with table 2; ins and ani: m = geom(1, rnd(seed, 28, v)); delins and `and`: the low 32 bits of
+ *     rnd(seed, 29, v) below mix_thr give l = 1, m = 1 + geom(1, .), otherwise l = 1 + geom(0, .), m = geom(1, .), and q =
+ *     min(p + l, e).  Tables that do not descend give an unspecified law and no access outside the arrays.
+ *   - Base j of an insertion is bits 2 (j & 31) of rnd(seed, 30, v W + (j >> 5)) as ACGT, W = (geom_n[1] + 2 + 31) / 32.
+ *   - n_out[0] = count, n_out[1] = the pool bytes.  ZK_ENOSPC when either exceeds its capacity (cap_rows in rows): both are in
+ *     n_out, nothing is written beyond [0, cap) of either output, the call may be repeated with room; capacity 0 sizes.
+ *   - ZK_EINVAL, with nothing written to the outputs: a variant that no zone holds, e < s, a window outside d_text, a sub that
+ *     falls into a zone without a base of ACGT (all found by the first pass); a threshold above 2^32 or out of order, a last type
+ *     threshold other than 2^32, a table beyond ZK_HGVS_TABLE_MAX, first or count >= 2^40.
+ *   - count == 0 writes nothing.  A count pass, a scan and a fill pass, no atomics: the same call returns the same bits, and a run
+ *     cut at any variant numbers returns the rows of one call (the pool offsets restart).  Workspace: 56 bytes per variant.
+ *
+ * zk_hgvs_render: the lines of the rows [0, n_rows), in row order, each ended by '\n'.
+ *   - The spellings of str(v): `A:g.<p+1>R>B` (R the upper-cased base at p), `A:g.<p+1>_<q+1>del` / `dup` / `delinsBASES` /
+ *     `delins<m>`, with `<p+1>` alone when p = q, and `A:g.<p>_<p+1>insBASES` / `ins<m>`; A = d_accs[d_acc_offs[z], d_acc_offs[z +
+ *     1]).  ZK_HGVS_TABULAR puts `A \t r0 \t r1 \t size \t wt \t mut \t` in front: range() = (p, p) for the two insertions and (p, q
+ *     + 1) otherwise, size() = m, 0 for del and 2 (q - p + 1) for dup, wt = seq[r0:r1] upper-cased, mut = the bases, nothing for
+ *     del, wt twice for dup and m times 'N' for ani and `and`.
+ *   - ZK_HGVS_HEADERS: row i is variant `first` + i of the run; where that is d_first[z], the first of its zone, and the zone's
+ *     name d_names[d_name_offs[z], d_name_offs[z + 1]) is not empty, the line `# A : name` goes in front.  (The caller leaves a
+ *     name empty where it repeats the name before it.)  Without the flag d_names, d_name_offs and d_first are not read.
+ *   - *n_bytes = the bytes of the text.  The capacity convention: ZK_ENOSPC with *n_bytes = the bytes needed, nothing written
+ *     at or beyond cap; cap 0 sizes.
+ *   - ZK_EINVAL, with nothing written: a row of unknown kind or zone, not s <= p <= q <= e, q != p for a sub or an insertion, an
+ *     m that its kind does not allow (or >= 2^40), a pool range outside [0, n_pool), a zone with e < s or a window outside
+ *     d_text, prefix offsets out of order (all found by the size pass); flags other than the three; n_rows or first >= 2^40.
+ *   - A size pass, a scan and a write pass, no atomics.  A workgroup takes 256 rows.  A line longer than ZK_HGVS_LONG_LINE bytes
+ *     is written by a wave, lanes over its bases, a shorter one by a thread; a tile whose text is at most ZK_HGVS_TILE_BYTES is
+ *     put together in LDS and leaves in aligned 16-byte stores, a larger one is written in place (tests straddle both bounds).
+ *     ZK_HGVS_DIRECT writes every tile in place: the same bytes, kept for measurements.  Workspace: 8 bytes per row. */
+#define ZK_HGVS_SUB 0
+#define ZK_HGVS_DEL 1
+#define ZK_HGVS_INS 2
+#define ZK_HGVS_DELINS 3
+#define ZK_HGVS_DUP 4
+#define ZK_HGVS_ANI 5
+#define ZK_HGVS_AND 6
+#define ZK_HGVS_ROW_WORDS 6
+#define ZK_HGVS_TABLE_MAX 65536
+#define ZK_HGVS_TABULAR 1
+#define ZK_HGVS_HEADERS 2
+#define ZK_HGVS_DIRECT 4
+#define ZK_HGVS_LONG_LINE 256
+#define ZK_HGVS_TILE_BYTES 32768
+int zk_hgvs_draw(zk_ctx* ctx, const uint8_t* d_text, uint64_t n_text, const uint64_t* d_zones, const uint64_t* d_first, uint64_t n_zones,
+                 const uint64_t type_thr[7], const uint64_t* d_geom, const uint64_t geom_n[3], uint64_t mix_thr, uint64_t seed, uint64_t first,
+                 uint64_t count, uint64_t* d_rows, uint64_t cap_rows, uint8_t* d_pool, uint64_t cap_pool, uint64_t n_out[2]);
+int zk_hgvs_render(zk_ctx* ctx, const uint64_t* d_rows, uint64_t n_rows, const uint8_t* d_pool, uint64_t n_pool, const uint8_t* d_text,
+                   uint64_t n_text, const uint64_t* d_zones, uint64_t n_zones, const uint8_t* d_accs, const uint64_t* d_acc_offs, uint64_t n_accs,
+                   const uint8_t* d_names, const uint64_t* d_name_offs, uint64_t n_names, const uint64_t* d_first, uint64_t first, int flags,
+                   uint8_t* d_out, uint64_t cap, uint64_t* n_bytes);
 
 /* ---- K3/K4: sort and count ------------------------------------------------------------------ */
 

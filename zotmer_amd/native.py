@@ -203,6 +203,8 @@ SIGNATURES = {
     "zk_stop_frames": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _i, _u32, _u64, _u64, _vp, _vp, _u64, _pu64]),
     "zk_stop_nearest": (_i, [_vp, _vp, _vp, _u64, _i, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     "zk_fizzle_votes": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _pu64]),
+    "zk_hgvs_draw": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _pu64, _vp, _pu64, _u64, _u64, _u64, _u64, _vp, _u64, _vp, _u64, _pu64]),
+    "zk_hgvs_render": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _i, _vp, _u64, _pu64]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
     "zk_count_spectrum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _i, _u64, _d, _pu64, _pu64, _u64, _pu64]),
 }
@@ -474,7 +476,8 @@ class Context:
                  "probe_scan": 21, "bait_tally": 22, "vars_scan": 23, "links": 24, "links_rc": 25, "contig_render": 26,
                  "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31, "lcp_resolve": 32, "scan_place": 33,
                  "seq_tally": 34, "spike_pairs": 35, "spike_size": 36, "ksnp_flank": 37, "ksnp_pairs": 38,
-                 "stop_frames": 39, "stop_emit": 40, "stop_nearest": 41, "fizzle_count": 42, "fizzle_emit": 43}
+                 "stop_frames": 39, "stop_emit": 40, "stop_nearest": 41, "fizzle_count": 42, "fizzle_emit": 43,
+                 "hgvs_draw": 44, "hgvs_fill": 45, "hgvs_size": 46, "hgvs_render": 47}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -1300,6 +1303,67 @@ class Context:
             n, fit = self.fizzle_votes_into(table, K, text1, lines1, text2, lines2, n_reads, single, hist, *o)
             assert fit
         return tuple(a.view(n) for a in o)
+
+    # ---- random variants of `zot hgvs-gen` (csrc/hgvs_gen.hip) -----------------------------------------------------
+    HGVS_ROW_WORDS = 6
+    HGVS_TABULAR, HGVS_HEADERS, HGVS_DIRECT = 1, 2, 4
+
+    def hgvs_draw_into(self, text, zones, first_var, type_thr, geom, geom_n, mix_thr, seed, first, count, rows, pool):
+        """zk_hgvs_draw into the arrays given (rows: u64, 6 words a variant; pool: u8) -> ((rows, pool bytes) written or, if they
+        did not fit, needed; whether they fit).  zones: u64[3 * n_zones], first_var: u64[n_zones + 1], type_thr: 7 ints, geom: the
+        three tables in a row (u64), geom_n: their 3 lengths."""
+        nz = first_var.n - 1
+        assert zones.n == 3 * nz and zones.dtype.itemsize == 8 and first_var.dtype.itemsize == 8 and text.dtype.itemsize == 1
+        assert geom.dtype.itemsize == 8 and geom.n >= sum(geom_n) and rows.dtype.itemsize == 8 and pool.dtype.itemsize == 1
+        thr = (C.c_uint64 * 7)(*[int(t) for t in type_thr])
+        gn = (C.c_uint64 * 3)(*[int(t) for t in geom_n])
+        n = (C.c_uint64 * 2)(0, 0)
+        rc = self.lib.zk_hgvs_draw(self.h, text.ptr, text.n, zones.ptr, first_var.ptr, nz, thr, geom.ptr, gn, int(mix_thr),
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(count), rows.ptr, rows.n // self.HGVS_ROW_WORDS, pool.ptr, pool.n, n)
+        if rc != ZK_ENOSPC:
+            self._check(rc)
+        return (int(n[0]), int(n[1])), rc == ZK_OK
+
+    def hgvs_draw(self, text, zones, first_var, type_thr, geom, geom_n, mix_thr, seed, first, count, out=None):
+        """-> (rows u64 view of 6 * count words, pool u8 view).  out: (rows, pool) buffers to write into first; grown when too
+        small."""
+        rows, pool = out if out is not None else (self.empty(self.HGVS_ROW_WORDS * count, np.uint64), self.empty(2 * count + 64, np.uint8))
+        args = (text, zones, first_var, type_thr, geom, geom_n, mix_thr, seed, first, count)
+        n, fit = self.hgvs_draw_into(*args, rows, pool)
+        if not fit:
+            rows = rows if rows.n >= self.HGVS_ROW_WORDS * n[0] else self.empty(self.HGVS_ROW_WORDS * n[0], np.uint64)
+            pool = pool if pool.n >= n[1] else self.empty(n[1], np.uint8)
+            n, fit = self.hgvs_draw_into(*args, rows, pool)
+            assert fit
+        return rows.view(self.HGVS_ROW_WORDS * n[0]), pool.view(n[1])
+
+    def hgvs_render_into(self, rows, pool, text, zones, accs, acc_offs, names, name_offs, first_var, first, flags, out):
+        """zk_hgvs_render into the uint8 array given -> (bytes written or, if they did not fit, needed; whether they fit).  names,
+        name_offs and first_var may be None without HGVS_HEADERS."""
+        nz = zones.n // 3
+        assert rows.n % self.HGVS_ROW_WORDS == 0 and rows.dtype.itemsize == 8 and zones.dtype.itemsize == 8 and acc_offs.n == nz + 1
+        assert pool.dtype.itemsize == 1 and text.dtype.itemsize == 1 and accs.dtype.itemsize == 1 and out.dtype.itemsize == 1
+        if flags & self.HGVS_HEADERS:
+            assert name_offs.n == nz + 1 and first_var.n == nz + 1 and names.dtype.itemsize == 1
+        nb = C.c_uint64(0)
+        rc = self.lib.zk_hgvs_render(self.h, rows.ptr, rows.n // self.HGVS_ROW_WORDS, pool.ptr, pool.n, text.ptr, text.n, zones.ptr, nz, accs.ptr,
+                                     acc_offs.ptr, accs.n, names.ptr if names is not None else None, name_offs.ptr if name_offs is not None else None,
+                                     names.n if names is not None else 0, first_var.ptr if first_var is not None else None, int(first), int(flags),
+                                     out.ptr, out.n, C.byref(nb))
+        if rc != ZK_ENOSPC:
+            self._check(rc)
+        return nb.value, rc == ZK_OK
+
+    def hgvs_render(self, rows, pool, text, zones, accs, acc_offs, names=None, name_offs=None, first_var=None, first=0, flags=0, out=None):
+        """-> the lines as a uint8 DeviceArray view.  out: a buffer to write into first; grown when too small."""
+        o = out if out is not None else self.empty(48 * (rows.n // self.HGVS_ROW_WORDS) + 64, np.uint8)
+        args = (rows, pool, text, zones, accs, acc_offs, names, name_offs, first_var, first, flags)
+        nb, fit = self.hgvs_render_into(*args, o)
+        if not fit:
+            o = self.empty(nb, np.uint8)
+            nb, fit = self.hgvs_render_into(*args, o)
+            assert fit
+        return o.view(nb)
 
     def capture_filter(self, stream, K, baits):
         out = self.empty(stream.n, np.uint8)

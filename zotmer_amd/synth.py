@@ -214,3 +214,71 @@ def stop_fraction(seed, g):
 def stop_draw(seed, g, n):
     """the rank, among the n votes of read g ordered by frame, of the vote whose frame is drawn: floor(u * n)"""
     return (stop_fraction(seed, g) * int(n)) >> 53
+
+
+# ---- random variants (`zot hgvs-gen`); the HIP version is csrc/hgvs_gen.hip ----------------------------------
+# Variant v, numbered in output order, takes its zone from T_ZONE as a pair of `zot spikein` does, and every other draw from
+# rnd(seed, tag, an index made of v): the tables below are all the host computes in floating point, once per run.
+T_HG_TYPE, T_HG_POS, T_HG_LEN, T_HG_INS, T_HG_MIX, T_HG_BASES, T_HG_ALT = 25, 26, 27, 28, 29, 30, 31
+HG_KINDS = ("sub", "del", "ins", "delins", "dup", "ani", "and")       # a row's kind is the index
+HG_TRIES = 64                 # position draws of a substitution before the walk round the zone
+HG_TABLE_MAX = 65536          # entries of a geometric table: means up to 4574
+
+
+def hg_type_thresholds(probs):
+    """relative probabilities of the seven kinds, in HG_KINDS order -> cumulative thresholds on a 32-bit draw, the last 2^32:
+    the kind is the first whose threshold exceeds the draw"""
+    total = float(sum(probs))
+    out, t = [], 0.0
+    for p in probs:
+        t += p
+        out.append(min(frac32(t / total), 1 << 32))
+    last = max(i for i, p in enumerate(probs) if p > 0)
+    for i in range(last, len(out)):
+        out[i] = 1 << 32
+    return out
+
+
+def hg_geom_table(mean):
+    """Q[k] = floor-product approximations of 2^32 (1 - 1/mean)^(k + 1), descending, down to the last positive entry:
+    P(X > k) = Q[k - 1] / 2^32 for X = hg_geom(Q, a uniform 32-bit draw).  A mean of 1 gives the empty table.  ValueError
+    for a mean below 1, one that is not finite, and one whose table would exceed HG_TABLE_MAX entries."""
+    mean = float(mean)
+    if not (mean >= 1.0) or mean == float("inf"):
+        raise ValueError("a mean length of %r: it must be finite and at least 1" % mean)
+    q0 = frac32(1.0 - 1.0 / mean)
+    if q0 >= 1 << 32:
+        raise ValueError("a mean length of %r is too large" % mean)
+    out, q = [], q0
+    while q > 0:
+        if len(out) == HG_TABLE_MAX:
+            raise ValueError("a mean length of %r needs a table of more than %d entries" % (mean, HG_TABLE_MAX))
+        out.append(q)
+        q = (q * q0) >> 32
+    return out
+
+
+def hg_geom(table, r32):
+    """1 + the number of entries of the descending table above r32"""
+    lo, hi = 0, len(table)
+    while lo < hi:
+        mid = (lo + hi) >> 1
+        if table[mid] > r32:
+            lo = mid + 1
+        else:
+            hi = mid
+    return 1 + lo
+
+
+def hg_mix_thr(D, I):
+    """delins and `and`: the threshold below which a 32-bit draw gives l = 1.  The reference draws l ~ geom(pd), m ~ geom(pi)
+    until l > 1 or m > 1, with pd = 1/D, pi = 1/I: P(l = 1 | kept) = pd (1 - pi) / (1 - pd pi).  ValueError when pd pi = 1."""
+    pd, pi = 1.0 / float(D), 1.0 / float(I)
+    if pd * pi >= 1.0:
+        raise ValueError("-D 1 with -I 1 leaves delins nothing to draw: every pair (1, 1) is rejected")
+    return min(frac32(pd * (1.0 - pi) / (1.0 - pd * pi)), 1 << 32)
+
+
+def hg_words(table_ins):
+    """W: the 64-bit words that hold the bases of the longest insertion, 1 + hg_geom's largest value, at 32 bases a word"""
+    return max(1, (len(table_ins) + 2 + 31) // 32)
