@@ -18,8 +18,8 @@
 //   2. two passes of the key kernel over M's top 18 key bits (sort_keys_upper_counted): M grouped by block;
 //   3. strand_starts_kernel: where every block of M starts (a binary search per block);
 //   4. strand_block_union_kernel: one workgroup per block reads C_b (in place, where the dedupe wrote it) and M_b, sorts the two in
-//      LDS (tile_group.hpp: the counting sort and the in-group ranks of tilesort.hip) and writes keys and counts at place(b) + rank.
-//      No tile waits for another.
+//      LDS (tile_group.hpp: the counting sort and the in-group ranks of tilesort.hip; K <= 25: the same on 32-bit tags, see
+//      StrandTagSmem) and writes keys and counts at place(b) + rank.  No tile waits for another.
 //
 // Buffers: C's gapped words stay in the dedupe's work buffer until the union has read them; M and the ping-pong buffer of its passes
 // (2 x 8 U bytes for U distinct canonical k-mers) are the first and second half of the keys' buffer, which the dedupe has finished with.
@@ -119,10 +119,13 @@ struct StrandArgs {
     int pshift;             // the block bits of a word start here
     u32* n_declined;        // the declined blocks: how many ...
     u32* declined;          // ... and which
+    int below;              // the block-local form: the key bits below the block bits (at most 32) ...
+    int gshift;             // ... and how far down the top 11 of them are: max(below - 11, 0)
 };
 
 // does any group of the tile just grouped hold more than SB_GROUP_MAX entries?  (every thread looks at four groups; a barrier)
-__device__ __forceinline__ bool strand_crowded(const StrandSmem& sm, int tid) {
+template <class S>
+__device__ __forceinline__ bool strand_crowded(const S& sm, int tid) {
     static_assert(SB_GROUPS == 4 * TS_BLOCK, "four groups a thread");
     u32 big = 0;
 #pragma unroll
@@ -149,12 +152,144 @@ __device__ __forceinline__ void strand_write(const StrandSmem& sm, const TileMap
     }
 }
 
+// ---- a whole block in its own terms: 32-bit tags (2 K - 18 <= 32) -------------------------------------------------------------------
+// Inside block b every key is (b << below) | tag, so the tile needs none of tile_group's 64-bit work: an entry is the tag (the key bits
+// below the block's) and the count, in two u32 arrays of the same 64 KB; the group is the tag's top 11 bits, a shift; the ranks compare
+// tags.  And no LDS access stands under a per-entry branch (each would be waited for on its own, sixteen round trips one after the
+// other): a slot beyond the block's entries adds to a spare counter of its lane's and parks at its own index -- the places from m up
+// are exactly those slots', and nothing reads them.
+struct StrandTagSmem {
+    static constexpr int CAP = TS_BLOCK * SB_ITEMS;
+    alignas(16) u32 tags[CAP + 16];          // (+ 16: the neighbours read from a group's start on never leave the array)
+    u32 cnts[CAP];
+    // the groups' counts, then where they start (start[G] = the block's entries); from G + 8 on: what the slots beyond the block's
+    // entries count, one word a lane, never read
+    alignas(16) u32 start[SB_GROUPS + 8 + 64];
+    u32 wsum[TS_BLOCK / 64];
+};
+// strand_tag_write ranks E entries a thread and round and reads the first F tags of their groups at once.  Measured (profiles/r27):
+// E = 2, F = 4: 8.77 ms; E = 4, F = 4: 8.79; E = 2, F = 8: 8.12; E = 4, F = 8: 8.37 -- at ~3 entries a group nearly every wave has a lane
+// whose group holds more than four, and with F = 4 the whole wave waits for that lane's second round trip
+constexpr int SB_RANK_E = 2, SB_RANK_FIRST = 8;
+
+// The block's m entries (nc of c, then those of mm) into LDS, grouped: sm.tags and sm.cnts group by group, sm.start as tile_group
+// leaves it.  Ends with a barrier.
+__device__ __forceinline__ void strand_tag_group(StrandTagSmem& sm, const u64* __restrict__ c, const u64* __restrict__ mm, u32 nc, u32 m,
+                                                 int pack, int below, int gshift, int tid) {
+    constexpr int G = SB_GROUPS, NW = TS_BLOCK / 64;
+    static_assert(G == 4 * TS_BLOCK && StrandTagSmem::CAP <= 8192, "four groups a thread in the scan; group | place << 12 in a word");
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 tmask = below >= 32 ? ~0u : (1u << below) - 1u, cmask = (u32)((1ull << pack) - 1ull);
+    u32 tag[SB_ITEMS], cnt[SB_ITEMS];
+#pragma unroll
+    for (int j = 0; j < SB_ITEMS; j++) {
+        // (a slot beyond the block loads the last entry again: sixteen loads and no branch)
+        const u32 i = (u32)j * TS_BLOCK + tid, ic = i < m ? i : m - 1;
+        const u64 w = ic < nc ? c[ic] : mm[ic - nc];
+        tag[j] = __builtin_amdgcn_alignbit((u32)(w >> 32), (u32)w, (u32)pack) & tmask;          // (u32)(w >> pack): pack < 32
+        cnt[j] = (u32)w & cmask;
+    }
+    reinterpret_cast<uint4*>(sm.start)[tid] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    u32 gp[SB_ITEMS];          // group | place in the group << 12
+#pragma unroll
+    for (int j = 0; j < SB_ITEMS; j++) {
+        const u32 i = (u32)j * TS_BLOCK + tid;
+        gp[j] = i < m ? tag[j] >> gshift : (u32)(G + 8 + lane);
+    }
+#pragma unroll
+    for (int j = 0; j < SB_ITEMS; j++) gp[j] |= atomicAdd(&sm.start[gp[j]], 1u) << 12;
+    __syncthreads();
+    {
+        // counts -> starts: four groups a thread, the waves' sums through LDS
+        uint4* z = reinterpret_cast<uint4*>(sm.start);
+        const uint4 cq = z[tid];
+        const u32 sum = cq.x + cq.y + cq.z + cq.w;
+        const u32 inc = wave_incl_scan_u32(sum);
+        if (lane == 63) sm.wsum[wave] = inc;
+        __syncthreads();
+        u32 run = inc - sum;
+#pragma unroll
+        for (int w = 0; w < NW; w++) run += w < wave ? sm.wsum[w] : 0u;
+        uint4 sq;
+        sq.x = run; run += cq.x; sq.y = run; run += cq.y; sq.z = run; run += cq.z; sq.w = run;
+        z[tid] = sq;
+        if (tid == 0) sm.start[G] = m;
+    }
+    __syncthreads();
+    u32 p[SB_ITEMS];
+#pragma unroll
+    for (int j = 0; j < SB_ITEMS; j++) p[j] = sm.start[gp[j] & 4095u];
+#pragma unroll
+    for (int j = 0; j < SB_ITEMS; j++) {
+        const u32 i = (u32)j * TS_BLOCK + tid;
+        p[j] = i < m ? p[j] + (gp[j] >> 12) : i;
+    }
+#pragma unroll
+    for (int j = 0; j < SB_ITEMS; j++) { sm.tags[p[j]] = tag[j]; sm.cnts[p[j]] = cnt[j]; }
+    __syncthreads();
+}
+
+// the grouped entries ranked in their groups and written: keys ((hi | tag) at place) to ok, counts to oc.  A thread ranks E entries a
+// round, their three LDS round trips (entry, group bounds, the group's first SB_RANK_FIRST tags) overlapping.  The group is computed
+// again from the tag (one shift) instead of travelling with the entry.
+template <int E>
+__device__ __forceinline__ void strand_tag_write(const StrandTagSmem& sm, u32 m, u64 hi, int gshift, u64* __restrict__ ok, u32* __restrict__ oc, int tid) {
+    constexpr int F = SB_RANK_FIRST;
+    static_assert(F + 3 <= 16, "the padding of StrandTagSmem::tags");
+    // does the entry at q (tag to) of a group that ends at g1 go before the one at `at` (tag tm)?  No branch: a compare and a carry.
+    // (C and M share no key and neither holds one twice; the tie-break by index keeps the places a permutation all the same)
+    auto before = [](u32 to, u32 q, u32 g1, u32 tm, u32 at) -> u32 {
+        return (u32)(q < g1) & ((u32)(to < tm) | ((u32)(to == tm) & (u32)(q < at)));
+    };
+    for (u32 i0 = (u32)tid; i0 < m; i0 += E * TS_BLOCK) {
+        u32 at[E], mine[E], cnt[E], g0[E], g1[E], o[E][F], place[E];
+#pragma unroll
+        for (int e = 0; e < E; e++) {          // (an entry beyond the block: the first one again, its place is not used)
+            at[e] = i0 + e * TS_BLOCK < m ? i0 + e * TS_BLOCK : 0u;
+            mine[e] = sm.tags[at[e]];
+            cnt[e] = sm.cnts[at[e]];
+        }
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            const u32 g = mine[e] >> gshift;
+            g0[e] = sm.start[g]; g1[e] = sm.start[g + 1];
+        }
+#pragma unroll
+        for (int e = 0; e < E; e++)
+#pragma unroll
+            for (int r = 0; r < F; r++) o[e][r] = sm.tags[g0[e] + r];
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            u32 rank = 0;
+#pragma unroll
+            for (int r = 0; r < F; r++) rank += before(o[e][r], g0[e] + r, g1[e], mine[e], at[e]);
+            for (u32 q0 = g0[e] + F; q0 < g1[e]; q0 += 4) {          // (a group of more)
+                u32 p4[4];
+#pragma unroll
+                for (int r = 0; r < 4; r++) p4[r] = sm.tags[q0 + r];
+#pragma unroll
+                for (int r = 0; r < 4; r++) rank += before(p4[r], q0 + r, g1[e], mine[e], at[e]);
+            }
+            place[e] = g0[e] + rank;
+        }
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            if (i0 + e * TS_BLOCK >= m) break;
+            ok[place[e]] = hi | mine[e];
+            oc[place[e]] = cnt[e];
+        }
+    }
+}
+
 // One workgroup per block, two per CU.  Every entry of C_b and M_b is loaded once, grouped in LDS by the next 11 bits of its key, ranked
 // in its group, and written to its place: the 64 lanes of a wave hold neighbours of the grouped order, so what a wave writes is a
 // permutation of one contiguous run of the table (512 bytes of keys, 256 of counts).  Neither list needs to be sorted: the grouping
-// reads only the block's number.
+// reads only the block's number.  TAGS: the block-local form above (the launch takes it when the key bits below the block's fit 32,
+// K <= 25); else tile_group's whole words.
+template <bool TAGS>
 __global__ __launch_bounds__(TS_BLOCK, 2 * TS_BLOCK / 256) void strand_block_union_kernel(StrandArgs a) {
-    using S = StrandSmem;
+    using S = std::conditional_t<TAGS, StrandTagSmem, StrandSmem>;
     constexpr u32 CAP = S::CAP;
     static_assert(sizeof(S) <= 80 * 1024, "two workgroups per CU");
     __shared__ S sm;
@@ -169,13 +304,22 @@ __global__ __launch_bounds__(TS_BLOCK, 2 * TS_BLOCK / 256) void strand_block_uni
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
     const u32 m = (u32)n;
-    const TileMap tm = tile_group<SB_ITEMS, SB_GROUPS, false>(sm, a.cw, nullptr, a.cuts[b], m, a.pshift, tid, a.m, m0, (u32)nc);
-    if (strand_crowded(sm, tid)) {          // entries that crowd a few groups: the big blocks' kernel cuts the value range finer
-        if (tid == 0) a.declined[atomicAdd(a.n_declined, 1u)] = b;
-        return;
-    }
     const u64 out0 = a.incl[b] - nc + m0;
-    strand_write(sm, tm, m, a.ok + out0, a.oc + out0, a.pack, tid);
+    if constexpr (TAGS) {
+        strand_tag_group(sm, a.cw + a.cuts[b], a.m + m0, (u32)nc, m, a.pack, a.below, a.gshift, tid);
+        if (strand_crowded(sm, tid)) {
+            if (tid == 0) a.declined[atomicAdd(a.n_declined, 1u)] = b;
+            return;
+        }
+        strand_tag_write<SB_RANK_E>(sm, m, (u64)b << a.below, a.gshift, a.ok + out0, a.oc + out0, tid);
+    } else {
+        const TileMap tm = tile_group<SB_ITEMS, SB_GROUPS, false>(sm, a.cw, nullptr, a.cuts[b], m, a.pshift, tid, a.m, m0, (u32)nc);
+        if (strand_crowded(sm, tid)) {          // entries that crowd a few groups: the big blocks' kernel cuts the value range finer
+            if (tid == 0) a.declined[atomicAdd(a.n_declined, 1u)] = b;
+            return;
+        }
+        strand_write(sm, tm, m, a.ok + out0, a.oc + out0, a.pack, tid);
+    }
 }
 
 // ---- the declined blocks, cut by value into sub-tiles ----------------------------------------------------------------------------
@@ -401,13 +545,15 @@ int strand_blocks(zk_ctx* c, const DedupeResult& r, u64* keys_buf, uint64_t buf_
     StrandArgs a = {};
     a.cw = r.work; a.cuts = r.cuts; a.nwords = r.nwords; a.incl = r.incl; a.m = sk; a.mstart = mstart;
     a.ok = out_k; a.oc = out_c; a.pack = pk; a.pshift = lo_bit;
+    a.below = 2 * K - SB_BLOCK_BITS; a.gshift = a.below > 11 ? a.below - 11 : 0;
     a.n_declined = &c->d_scalars->strand.n_declined;
     a.declined = declined;
     u32* fail = &c->d_scalars->strand.fail;
     prof_begin(c, ZK_PROF_UNION, 8 * 2 * uc + 12 * 2 * uc);
     hipLaunchKernelGGL(strand_starts_kernel, dim3(((1u << SB_BLOCK_BITS) + 256) / 256), dim3(256), 0, c->stream, sk, (u64)uc, lo_bit, mstart);
     ZK_HIP(c, hipMemsetAsync(&c->d_scalars->strand, 0, sizeof(zk_strand_counters), c->stream));
-    hipLaunchKernelGGL(strand_block_union_kernel, dim3(r.chunks), dim3(TS_BLOCK), 0, c->stream, a);
+    if (a.below <= 32) hipLaunchKernelGGL(strand_block_union_kernel<true>, dim3(r.chunks), dim3(TS_BLOCK), 0, c->stream, a);
+    else hipLaunchKernelGGL(strand_block_union_kernel<false>, dim3(r.chunks), dim3(TS_BLOCK), 0, c->stream, a);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->strand));
