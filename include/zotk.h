@@ -227,6 +227,9 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_HGVS_FILL 45    /* zk_hgvs_draw: the fill kernel (104 B per variant read and written + the pool bytes) */
 #define ZK_PROF_HGVS_SIZE 46    /* zk_hgvs_render: the size pass and the scan behind it as one record (bytes = 64 per row) */
 #define ZK_PROF_HGVS_RENDER 47  /* zk_hgvs_render: the write pass (56 B read per row + the text written) */
+#define ZK_PROF_DUP_COVER 48    /* zk_dup_join: the cover pass, one search per occurrence (dup_join.hip; bytes = 16 per occurrence + 4 written) */
+#define ZK_PROF_DUP_JOIN 49     /* zk_dup_join: the count pass (16 B read per entry, 8 written) and the emit pass (... + 12 B written per row), one
+                                   record each; the time grows with the searches and the pairs, not with these bytes */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -799,6 +802,35 @@ int zk_fizzle_votes(zk_ctx* ctx, const zk_bait_table* classes, int K, const uint
                     const uint8_t* d_text2, const uint64_t* d_lines2, uint64_t n_reads, uint64_t n_classes, uint64_t* d_single,
                     uint64_t* d_hist, uint64_t n_hist, uint32_t* d_rec, uint32_t* d_cls, uint32_t* d_cnt, uint64_t cap,
                     uint64_t* n_out);
+
+/* ---- `zot vardyger`: candidate tandem duplications, joined (dup_join.hip; commands/vardyger.py:82-133, 403-431) -------------------
+ * With J = K / 2 (K even) a K-mer x is a first half x >> 2J and a second half x & (4^J - 1).  The reference's findDup + positions
+ * name, per sequence, the tuples (a, b, c, d) with ab and cd K-mers of the sequence at pa and pc > pa + J, a != c, b != d, and cb and
+ * cd among the K-mers counted for the sequence at least ten times.
+ *
+ * zk_dup_join: d_baits / d_kmers / d_counts[0, n) = the counted list as zk_pileup_count writes it, ascending by (bait, k-mer), a bait
+ * being a sequence.  d_rseq / d_rkmer / d_rpos[0, m) = the occurrence table of all sequences, one entry per window, ascending by
+ * (sequence, k-mer, position); d_by_second[0, m) = the indices of the same entries ascending by (sequence, second half, first half,
+ * position).
+ *   - d_cover[i] = the count of the entry (d_rseq[i], d_rkmer[i]), 0 if the list has none.  Written whenever m > 0, also by a call
+ *     that returns ZK_ENOSPC.
+ *   - A row is (e, i, j): the entry e is cb, the occurrence i is ab, the occurrence j is cd.  It exists iff d_counts[e] >= min_count,
+ *     d_rseq[i] == d_rseq[j] == d_baits[e], the second half of d_rkmer[i] and the first half of d_rkmer[j] are those of d_kmers[e],
+ *     the first half of d_rkmer[i] and the second half of d_rkmer[j] are not, d_cover[j] >= min_count and d_rpos[j] > d_rpos[i] + J.
+ *     The rows go to d_entry / d_left / d_right ascending by e, then by the place of i in d_by_second, then by j.
+ *   - The capacity convention: ZK_ENOSPC with *n_out = the rows needed when they exceed cap, nothing written to the three row
+ *     arrays, repeatable with room; cap 0 sizes.
+ *   - ZK_EINVAL before any launch: K odd or outside 2..32, n or m >= 2^32, a null array that would be used.  n == 0 or m == 0:
+ *     *n_out = 0 (with n == 0 < m the cover is all zeros).  Lists that are not in the orders above give unspecified rows and no
+ *     access outside the arrays (a value of d_by_second that is no index is read as m - 1).
+ *   - An entry costs two searches when either of its runs is empty, which is nearly always.  An entry whose runs have more than
+ *     ZK_DUP_WAVE_PAIRS pairs between them (low-complexity sequence) is done by a wave, 64 pairs a step, the others by a lane
+ *     each (tests straddle the bound).  A cover pass, a count pass, a scan and an emit pass; no atomics, integers only: the same
+ *     call returns the same bits.  Workspace: 8 bytes per entry. */
+#define ZK_DUP_WAVE_PAIRS 64
+int zk_dup_join(zk_ctx* ctx, const uint32_t* d_baits, const uint64_t* d_kmers, const uint32_t* d_counts, uint64_t n, const uint32_t* d_rseq,
+                const uint64_t* d_rkmer, const uint32_t* d_rpos, const uint32_t* d_by_second, uint64_t m, int K, uint32_t min_count,
+                uint32_t* d_cover, uint32_t* d_entry, uint32_t* d_left, uint32_t* d_right, uint64_t cap, uint64_t* n_out);
 
 /* ---- `zot hgvs-gen`: random variants over zones, as HGVS lines (hgvs_gen.hip) ---------------------------------------------------
  * zotmer/commands/hgvs-gen.py:120-171 and :257-271, zotmer/library/hgvs.py, with the draws of zotmer_amd/synth.py: rnd(seed, tag,

@@ -79,10 +79,11 @@ struct zk_scalars {
     u64 fizzle_total;        // landing: the end of the last record's entries
     u64 hgvs_bad;            // hgvs_gen.hip: a variant without a zone (1), a sub in a zone without ACGT (2); a row that breaks zk_hgvs_render's rules
     u64 hgvs_total;          // landing: the end of the last variant's pool bytes, of the last row's line
+    u64 dup_total;           // landing: the end of the last entry's rows (dup_join.hip)
 };
 // bytes of the fields first .. last (declared in that order, adjacent)
 #define ZK_SPAN(first, last) (offsetof(zk_scalars, last) + sizeof(zk_scalars::last) - offsetof(zk_scalars, first))
-static_assert(sizeof(zk_scalars) == 93 * sizeof(u64), "zk_scalars: u64 words only, no padding");
+static_assert(sizeof(zk_scalars) == 94 * sizeof(u64), "zk_scalars: u64 words only, no padding");
 static_assert(ZK_SPAN(rle_side, total) == 2 * sizeof(u64), "rle_prefix reads rle_side and total back as one range");
 static_assert(ZK_SPAN(total, acgt) == 5 * sizeof(u64), "the merges read total and acgt back as one range");
 static_assert(ZK_SPAN(acgt, n_keys) == 5 * sizeof(u64) && ZK_SPAN(acgt, sample_n) == 9 * sizeof(u64),

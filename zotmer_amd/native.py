@@ -36,7 +36,8 @@ KSNP_HAMMING, KSNP_LEVENSHTEIN = 0, 1           # ZK_KSNP_HAMMING, ZK_KSNP_LEVEN
 KSNP_WAVE_GROUP, KSNP_LDS_GROUP, KSNP_PAIR_TILE = 64, 1024, 256   # ZK_KSNP_WAVE_GROUP, ZK_KSNP_LDS_GROUP, ZK_KSNP_PAIR_TILE
 STOP_VOTES, STOP_NEAR_ENTRIES, STOP_NEAR_TILE = 512, 64, 1024    # ZK_STOP_VOTES, ZK_STOP_NEAR_ENTRIES, ZK_STOP_NEAR_TILE
 FIZZLE_CLASSES = 512                            # ZK_FIZZLE_CLASSES
-DEFAULT_TAG_WORDS = 2          # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
+DUP_WAVE_PAIRS = 64                             # ZK_DUP_WAVE_PAIRS
+DEFAULT_TAG_WORDS = 2         # zk_tune(ZK_TUNE_TAG_WORDS) as the library starts (csrc/internal.hpp)
 
 _ERRNAMES = {-1: "ZK_EINVAL", -2: "ZK_ENOMEM", -3: "ZK_EHIP", -4: "ZK_ENOSPC", -5: "ZK_EOVERFLOW",
              -6: "ZK_EINTERNAL", -7: "ZK_ERANGE"}
@@ -203,6 +204,7 @@ SIGNATURES = {
     "zk_stop_frames": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _i, _u32, _u64, _u64, _vp, _vp, _u64, _pu64]),
     "zk_stop_nearest": (_i, [_vp, _vp, _vp, _u64, _i, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     "zk_fizzle_votes": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _pu64]),
+    "zk_dup_join": (_i, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _i, _u32, _vp, _vp, _vp, _vp, _u64, _pu64]),
     "zk_hgvs_draw": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _pu64, _vp, _pu64, _u64, _u64, _u64, _u64, _vp, _u64, _vp, _u64, _pu64]),
     "zk_hgvs_render": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _i, _vp, _u64, _pu64]),
     "zk_contig_spectra": (_i, [_vp, _vp, _u64, _i, _i, _u64, _d, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(ContigStats)]),
@@ -477,7 +479,7 @@ class Context:
                  "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31, "lcp_resolve": 32, "scan_place": 33,
                  "seq_tally": 34, "spike_pairs": 35, "spike_size": 36, "ksnp_flank": 37, "ksnp_pairs": 38,
                  "stop_frames": 39, "stop_emit": 40, "stop_nearest": 41, "fizzle_count": 42, "fizzle_emit": 43,
-                 "hgvs_draw": 44, "hgvs_fill": 45, "hgvs_size": 46, "hgvs_render": 47}
+                 "hgvs_draw": 44, "hgvs_fill": 45, "hgvs_size": 46, "hgvs_render": 47, "dup_cover": 48, "dup_join": 49}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -1303,6 +1305,36 @@ class Context:
             n, fit = self.fizzle_votes_into(table, K, text1, lines1, text2, lines2, n_reads, single, hist, *o)
             assert fit
         return tuple(a.view(n) for a in o)
+
+    # ---- candidate tandem duplications of `zot vardyger` (csrc/dup_join.hip) ---------------------------------------
+    def dup_join_into(self, baits, kmers, counts, rseq, rkmer, rpos, by_second, K, min_count, cover, out_e, out_i, out_j):
+        """zk_dup_join into the arrays given -> (rows written or, if they did not fit, needed; whether they fit).  cover is
+        written either way."""
+        assert baits.n == kmers.n == counts.n and baits.dtype.itemsize == 4 and kmers.dtype.itemsize == 8 and counts.dtype.itemsize == 4
+        assert rseq.n == rkmer.n == rpos.n == by_second.n and cover.n >= rseq.n
+        assert rseq.dtype.itemsize == 4 and rkmer.dtype.itemsize == 8 and rpos.dtype.itemsize == 4 and by_second.dtype.itemsize == 4
+        assert cover.dtype.itemsize == 4 and out_e.dtype.itemsize == 4 and out_i.dtype.itemsize == 4 and out_j.dtype.itemsize == 4
+        n = C.c_uint64(0)
+        rc = self.lib.zk_dup_join(self.h, baits.ptr, kmers.ptr, counts.ptr, baits.n, rseq.ptr, rkmer.ptr, rpos.ptr, by_second.ptr, rseq.n,
+                                  int(K), int(min_count), cover.ptr, out_e.ptr, out_i.ptr, out_j.ptr, min(out_e.n, out_i.n, out_j.n), C.byref(n))
+        if rc != ZK_ENOSPC:
+            self._check(rc)
+        return n.value, rc == ZK_OK
+
+    def dup_join(self, baits, kmers, counts, rseq, rkmer, rpos, by_second, K, min_count, out=None):
+        """a counted (bait, k-mer) list as pileup_count gives it + the occurrence table of the baits' sequences (u32 sequence,
+        u64 k-mer, u32 position, ascending; by_second: its indices ascending by (sequence, second half, first half, position))
+        -> (cover, entries, lefts, rights) as numpy u32 arrays: every occurrence's count, and the rows (entry index of cb,
+        occurrence index of ab, occurrence index of cd) in the entry's fixed order (zk_dup_join).  out: three u32 arrays to
+        write the rows into first; one retry with the length the entry reports when they are too small."""
+        cover = self.empty(rseq.n, np.uint32)
+        o = out if out is not None else tuple(self.empty(1024, np.uint32) for _ in range(3))
+        n, fit = self.dup_join_into(baits, kmers, counts, rseq, rkmer, rpos, by_second, K, min_count, cover, *o)
+        if not fit:
+            o = tuple(self.empty(n, np.uint32) for _ in range(3))
+            n, fit = self.dup_join_into(baits, kmers, counts, rseq, rkmer, rpos, by_second, K, min_count, cover, *o)
+            assert fit
+        return (cover.to_host(),) + tuple(a.to_host(n) for a in o)
 
     # ---- random variants of `zot hgvs-gen` (csrc/hgvs_gen.hip) -----------------------------------------------------
     HGVS_ROW_WORDS = 6
