@@ -230,6 +230,8 @@ int zk_tune(zk_ctx* ctx, int what, int value);
 #define ZK_PROF_DUP_COVER 48    /* zk_dup_join: the cover pass, one search per occurrence (dup_join.hip; bytes = 16 per occurrence + 4 written) */
 #define ZK_PROF_DUP_JOIN 49     /* zk_dup_join: the count pass (16 B read per entry, 8 written) and the emit pass (... + 12 B written per row), one
                                    record each; the time grows with the searches and the pairs, not with these bytes */
+#define ZK_PROF_PILEUP_MERGE 50 /* zk_pileup_merge: the partition, the count pass, the scan and the emit pass as one record per call (pileup_merge.hip;
+                                   bytes = 12 per input element for the count pass, 20 per A element, 16 or 24 per B element, 20 per output element) */
 int zk_debug_buffer(zk_ctx* ctx, void* d_buf);   /* diagnostic builds (-DZK_STAMPS) only; NULL turns it off */
 int zk_profile(zk_ctx* ctx, int enable);   /* clears the records; enable != 0 starts recording */
 int zk_profile_read(zk_ctx* ctx, int tag, uint64_t* launches, double* total_ms, uint64_t* algorithmic_bytes);
@@ -543,6 +545,28 @@ int zk_anchor_pileup(zk_ctx* ctx, const zk_bait_table* anchors, const uint8_t* d
 #define ZK_PILEUP_TILE 4096
 int zk_pileup_count(zk_ctx* ctx, const uint32_t* d_coords, const uint64_t* d_kmers, uint64_t n, int K, uint32_t* d_oc, uint64_t* d_ok,
                     uint32_t* d_cnt, uint64_t cap, uint64_t* n_out);
+
+/* The union of two counted lists: A = d_ac / d_ak / d_an[0, na) and B = d_bc / d_bk / d_bn[0, nb), each strictly ascending by
+ * (coordinate, k-mer) as zk_pileup_count writes them or as an earlier call of this entry left them, into d_oc / d_ok / d_on:
+ * ascending, every pair once, the counts of a pair that both lists hold added modulo 2^64.  A's counts are u64; B's are u32 or
+ * u64 (b_count_bits), so a fresh zk_pileup_count list goes in as it is.  Inputs are left as they are; outputs may not overlap
+ * inputs.  The order of the inputs is not checked: on other input the output is unspecified, but no access leaves the arrays.
+ *   - b_count_bits outside {32, 64} is ZK_EINVAL before any launch.  na == 0 and nb == 0 are plain cases.
+ *   - The capacity convention: ZK_ENOSPC with *n_out = the length needed when it exceeds cap, nothing written at all,
+ *     repeatable with room.  Indices are 64 bits wide throughout.
+ *   - A merge-path cut of the merged order (coordinate, then k-mer, both unsigned; A before B on ties) into tiles of
+ *     ZK_PILEUP_MERGE_TILE merged inputs; a count pass over the keys, a scan of the tiles' counts by one workgroup, an emit
+ *     pass that writes each tile's survivors as one run.  A pair of equal keys belongs to the tile that holds its A element
+ *     (tests place pairs across every tile boundary).  No workgroup waits for another, no atomics: the same call returns
+ *     the same bits.  Work space: 16 bytes per tile. */
+#define ZK_PILEUP_MERGE_TILE 2048
+int zk_pileup_merge(zk_ctx* ctx, const uint32_t* d_ac, const uint64_t* d_ak, const uint64_t* d_an, uint64_t na,
+                    const uint32_t* d_bc, const uint64_t* d_bk, const void* d_bn, int b_count_bits, uint64_t nb,
+                    uint32_t* d_oc, uint64_t* d_ok, uint64_t* d_on, uint64_t cap, uint64_t* n_out);
+
+/* The counterpart of zk_widen_counts: d_out[i] = min(d_in[i], 2^32 - 1) for i < n, and *max_in = the largest d_in[i] (0 for
+ * n == 0) -- a caller whose next entry takes 32-bit counts refuses the list when *max_in says that one was clipped. */
+int zk_narrow_counts(zk_ctx* ctx, const uint64_t* d_in, uint32_t* d_out, uint64_t n, uint64_t* max_in);
 
 /* ---- variants called from captured read pairs, `zot hgvs-find` (commands/hgvs-find.py:917-1131) ---------------------------------
  * The reference hands every read pair to capture.addReadPairAndKmers (library/capture.py:99-135): ns = the baits that hold a

@@ -400,7 +400,10 @@ int zk_alloc(zk_ctx* c, uint64_t bytes, void** dptr) {
     *dptr = nullptr;
     if (bytes == 0) bytes = 256;
     hipError_t e = hipMalloc(dptr, bytes);
-    if (e != hipSuccess) return fail(c, ZK_ENOMEM, "hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();             // empties HIP's last-error slot: a caller that goes on without the memory (alufinder.DevicePileup) would meet this error in the check after its next launch
+        return fail(c, ZK_ENOMEM, "hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+    }
     return ZK_OK;
 }
 

@@ -80,10 +80,12 @@ struct zk_scalars {
     u64 hgvs_bad;            // hgvs_gen.hip: a variant without a zone (1), a sub in a zone without ACGT (2); a row that breaks zk_hgvs_render's rules
     u64 hgvs_total;          // landing: the end of the last variant's pool bytes, of the last row's line
     u64 dup_total;           // landing: the end of the last entry's rows (dup_join.hip)
+    u64 merge_total;         // pileup_merge.hip: pm_scan_kernel's total = the length of the union
+    u64 narrow_max;          // pileup_merge.hip: narrow_max_kernel's largest count
 };
 // bytes of the fields first .. last (declared in that order, adjacent)
 #define ZK_SPAN(first, last) (offsetof(zk_scalars, last) + sizeof(zk_scalars::last) - offsetof(zk_scalars, first))
-static_assert(sizeof(zk_scalars) == 94 * sizeof(u64), "zk_scalars: u64 words only, no padding");
+static_assert(sizeof(zk_scalars) == 96 * sizeof(u64), "zk_scalars: u64 words only, no padding");
 static_assert(ZK_SPAN(rle_side, total) == 2 * sizeof(u64), "rle_prefix reads rle_side and total back as one range");
 static_assert(ZK_SPAN(total, acgt) == 5 * sizeof(u64), "the merges read total and acgt back as one range");
 static_assert(ZK_SPAN(acgt, n_keys) == 5 * sizeof(u64) && ZK_SPAN(acgt, sample_n) == 9 * sizeof(u64),
@@ -402,4 +404,5 @@ int project_sum(zk_ctx* c, const u64* keys, const void* cnts, int count_bits, ui
                 uint64_t* n_out, uint64_t* total);
 int spectrum_sums(zk_ctx* c, const u64* A, const u64* sA, u64 nA, const u64* B, const u64* sB, u64 nB, double cx, double cy, zk_spectrum* out);
 // lcp_scan.hip: zk_lcp_resolve and zk_scan_place; nothing of it is called from another unit
+// pileup_merge.hip: zk_pileup_merge and zk_narrow_counts; nothing of it is called from another unit
 }  // namespace zk

@@ -8,8 +8,9 @@ that leave the reference (forwardSpurs / reverseSpurs, 164-218) -- printed raw, 
 
 Here the zones and the index are read on the host (load_zones); the index goes to the device as a bait table whose ids are
 anchors on one u32 axis (Layout, anchor_table); the reads stream through in batches (fastq_batches.record_batches), one
-zk_anchor_pileup and one zk_pileup_count per mate and batch; the counted lists are merged on the host (Pileup.merge: a
-lexsort and an add.reduceat over the concatenation) and decoded back to acc[zone][position][k-mer]; the filter runs on the merged list (filter_counted); the spurs,
+zk_anchor_pileup and one zk_pileup_count per mate and batch; the counted lists are merged on the device (DevicePileup: one
+zk_pileup_merge per list into a resident accumulator; Pileup is the host form: a lexsort and an add.reduceat over the
+concatenation) and decoded back to acc[zone][position][k-mer]; the filter runs on the merged list (filter_counted); the spurs,
 the shifts, the join and the printing are the reference's, restated.  What is printed does not depend on where the batches
 are cut.
 """
@@ -224,11 +225,139 @@ class Pileup:
             self.merges += 1
         self.waiting = 0
 
+    def add_device(self, oc, ok, cnt):
+        """the three views of Context.pileup_count"""
+        self.add(oc.to_host(), ok.to_host(), cnt.to_host())
+
     def result(self):
         self.merge()
         if not self.parts:
             return np.empty(0, np.uint32), np.empty(0, np.uint64), np.empty(0, np.uint64)
         return self.parts[0]
+
+
+class DevicePileup:
+    """Pileup with the list kept on the device: every counted list is merged straight into one accumulated list
+    (zk_pileup_merge), which lives in one of two array triples and is written into the other.  The triples grow geometrically
+    to na + nb before a merge, so a merge never needs a second try.  When the next pair of triples would take more than
+    `limit` bytes (default: half of the device memory free now), or an allocation fails, the list goes down into a host
+    Pileup once and the run continues there."""
+
+    DTYPES = (np.uint32, np.uint64, np.uint64)
+    ENTRY_BYTES = 20
+
+    def __init__(self, ctx, limit=None):
+        self.ctx = ctx
+        self.limit = int(limit) if limit is not None else ctx.mem_info()[0] // 2
+        self.cur, self.alt, self.n = None, None, 0
+        self.host, self._down = None, None
+        self._merge_seconds, self._merges, self.pairs = 0.0, 0, 0
+
+    @property
+    def merges(self):
+        return self._merges + (self.host.merges if self.host is not None else 0)
+
+    @property
+    def merge_seconds(self):
+        return self._merge_seconds + (self.host.merge_seconds if self.host is not None else 0.0)
+
+    @staticmethod
+    def _cap(triple):
+        return triple[0].n if triple is not None else 0
+
+    def _triple(self, need, other):
+        """a triple of need + need / 2 entries, or None: beside `other` it would pass the limit, or the device has no room"""
+        cap = need + need // 2
+        if self.ENTRY_BYTES * (cap + self._cap(other)) > self.limit:
+            cap = need
+            if self.ENTRY_BYTES * (cap + self._cap(other)) > self.limit:
+                return None
+        got = []
+        try:
+            for dt in self.DTYPES:
+                got.append(self.ctx.empty(cap, dt))
+        except native.ZotkError as e:
+            if e.code != native.ZK_ENOMEM:
+                raise
+            for a in got:
+                a.free()
+            return None
+        return tuple(got)
+
+    def _hand_over(self):
+        self.host = Pileup()
+        if self.n:
+            self.host.add(*[a.to_host(self.n) for a in self.cur])
+        for t in (self.cur, self.alt):
+            for a in t or ():
+                a.free()
+        self.cur, self.alt, self.n = None, None, 0
+
+    def add_device(self, oc, ok, cnt):
+        """the three views of Context.pileup_count, or any counted list on the device with u32 or u64 counts"""
+        nb = oc.n
+        assert ok.n == nb == cnt.n and oc.dtype.itemsize == 4 and ok.dtype.itemsize == 8 and cnt.dtype.itemsize in (4, 8)
+        if nb == 0:
+            return
+        self.pairs += nb
+        self._down = None
+        if self.host is not None:
+            return self.host.add(oc.to_host(), ok.to_host(), cnt.to_host())
+        ctx = self.ctx
+        if self.n == 0:
+            if self._cap(self.cur) < nb:
+                for a in self.cur or ():
+                    a.free()
+                self.cur = None
+                self.cur = self._triple(nb, self.alt)
+                if self.cur is None:
+                    self._hand_over()
+                    return self.host.add(oc.to_host(), ok.to_host(), cnt.to_host())
+            ctx._check(ctx.lib.zk_copy(ctx.h, self.cur[0].ptr, oc.ptr, 4 * nb))
+            ctx._check(ctx.lib.zk_copy(ctx.h, self.cur[1].ptr, ok.ptr, 8 * nb))
+            if cnt.dtype.itemsize == 8:                         # a list that was merged before, or one from the host
+                ctx._check(ctx.lib.zk_copy(ctx.h, self.cur[2].ptr, cnt.ptr, 8 * nb))
+            else:
+                ctx._check(ctx.lib.zk_widen_counts(ctx.h, cnt.ptr, self.cur[2].ptr, nb))
+            ctx.sync()
+            self.n = nb
+            return
+        t0 = time.perf_counter()
+        if self._cap(self.alt) < self.n + nb:
+            for a in self.alt or ():
+                a.free()
+            self.alt = None
+            self.alt = self._triple(self.n + nb, self.cur)
+            if self.alt is None:
+                self._hand_over()
+                return self.host.add(oc.to_host(), ok.to_host(), cnt.to_host())
+        n, fit = ctx.pileup_merge_into(tuple(a.view(self.n) for a in self.cur), (oc, ok, cnt), self.alt)
+        assert fit
+        self.cur, self.alt, self.n = self.alt, self.cur, n
+        self._merge_seconds += time.perf_counter() - t0
+        self._merges += 1
+
+    def add(self, coords, kmers, counts):
+        """a list from the host (as Pileup.add takes it)"""
+        if len(coords):
+            self.add_device(self.ctx.upload(coords, np.uint32), self.ctx.upload(kmers, np.uint64), self.ctx.upload(counts, np.uint64))
+
+    def result(self):
+        """the merged list on the host: one download"""
+        if self.host is not None:
+            return self.host.result()
+        if self._down is None:
+            self._down = tuple(a.to_host(self.n) if self.n else np.empty(0, dt) for a, dt in zip(self.cur or self.DTYPES, self.DTYPES))
+        return self._down
+
+    def device_result(self):
+        """the merged list as three DeviceArray views (u32, u64, u64 counts); uploaded after a handover.  The views lie in the
+        accumulator's own arrays: they are valid until the next add or add_device, which may write over them or free them."""
+        if self.host is not None:
+            return tuple(self.ctx.upload(a, dt) for a, dt in zip(self.host.result(), self.DTYPES))
+        if self.cur is None:
+            return tuple(self.ctx.empty(0, dt) for dt in self.DTYPES)
+        return tuple(a.view(self.n) for a in self.cur)
 
 
 def pile_inputs(ctx, table, K, pad, inputs, batch, pileup, verbose=False):
@@ -248,8 +377,7 @@ def pile_inputs(ctx, table, K, pad, inputs, batch, pileup, verbose=False):
                             raise
                         raise InputError("%s: %s" % (" & ".join(paths), str(e).split(": ", 1)[-1]))
                     bufs = (whole(coords), whole(kmers))
-                    oc, ok, cnt = ctx.pileup_count(coords, kmers, K)
-                    pileup.add(oc.to_host(), ok.to_host(), cnt.to_host())
+                    pileup.add_device(*ctx.pileup_count(coords, kmers, K))
                 n_reads += r
                 if verbose:
                     sys.stderr.write("%s: %d read pairs processed\n" % (" & ".join(os.path.basename(p) for p in paths), n_reads))
@@ -379,11 +507,11 @@ def report_lines(K, acc, zones, L, S, raw):
                     yield "%s\t%d\t%d\t%s\t%d\t%d\t%s\t%s\t%s\t%s" % (ch, p0, p0 + 1, z, av, bv, a_anc, b_anc, a_ins, b_ins)
 
 
-def run(ctx, zones, inputs, C, L, S, V, raw, batch, out, pad=PAD, verbose=False, stats=None):
-    """the whole command behind its argument checks"""
+def run(ctx, zones, inputs, C, L, S, V, raw, batch, out, pad=PAD, verbose=False, stats=None, pileup=None):
+    """the whole command behind its argument checks.  pileup: where the counted lists gather (None: a DevicePileup)"""
     K = zones.K
     layout = layout_of(zones, pad)
-    pileup = Pileup()
+    pileup = pileup if pileup is not None else DevicePileup(ctx)
     n_reads = 0
     t0 = time.perf_counter()
     if layout.names:

@@ -12,8 +12,8 @@ line printed per variant.
 
 Here the baits are a bait table on the device (library/capture.py), the mates stream through in batches
 (library/fastq_batches.py), and each batch is one zk_capture_hits, zk_capture_kmers over slices of the pair list whose
-entries stay within a budget, and one zk_pileup_count per slice; the counted lists are merged on the host
-(alufinder.Pileup).  After the last batch the merged list goes up once: one zk_path_scan answers every position of every
+entries stay within a budget, and one zk_pileup_count per slice; the counted lists are merged on the device
+(alufinder.DevicePileup: zk_pileup_merge).  After the last batch the merged list stays where it is: one zk_path_scan answers every position of every
 definite path, one more the anchors of the anonymous variants.  The pruning, the consensus, the paths, the scores and the
 table are the reference's, restated over the matches.  What is printed does not depend on where the batches or slices are
 cut.
@@ -29,7 +29,7 @@ import time
 import numpy as np
 
 from zotmer_amd.library import capture
-from zotmer_amd.library.alufinder import Pileup
+from zotmer_amd.library.alufinder import DevicePileup
 from zotmer_amd.library.fastq_batches import record_batches, whole
 
 EMIT_BUDGET = 1 << 25           # entries one zk_capture_kmers may write: 384 MiB of entries, 1.7 GiB of work space to count them
@@ -260,10 +260,9 @@ class Emitter:
             if n == 0:
                 continue
             t0 = time.perf_counter()
-            ob, ok, cnt = ctx.pileup_count(self.bufs[0].view(n), self.bufs[1].view(n), self.K)
-            hb, hk, hc = ob.to_host(), ok.to_host(), cnt.to_host()
+            counted = ctx.pileup_count(self.bufs[0].view(n), self.bufs[1].view(n), self.K)
             st["count_seconds"] += time.perf_counter() - t0
-            self.pileup.add(hb, hk, hc)
+            self.pileup.add_device(*counted)
 
 
 def capture_inputs(ctx, table, K, inputs, batch, budget, pileup, read_counts, stats, verbose=False):
@@ -537,11 +536,22 @@ def scan(ctx, dev, K, wins):
     return [e[cuts[i]:cuts[i + 1]] for i in range(len(wins))]
 
 
-def call_variants(ctx, items, variants, counted, read_counts, K, D, Q, V, fmt, out, err, stats):
-    """hgvs-find.py:969-1131 over the merged list"""
+def device_list(ctx, pileup, what):
+    """the merged list of a DevicePileup as the entries after it take it: (baits, k-mers, counts u32) on the device, None if
+    it is empty; a count beyond 32 bits is refused"""
+    baits, kmers, counts = pileup.device_result()
+    if baits.n == 0:
+        return None
+    narrow, mx = ctx.narrow_counts(counts)
+    if mx >= 1 << 32:
+        raise InputError("a k-mer was counted %d times, more than the %s's 32-bit counts hold" % (mx, what))
+    return baits, kmers, narrow
+
+
+def call_variants(ctx, items, variants, counted, read_counts, K, D, Q, V, fmt, out, err, stats, dev=None):
+    """hgvs-find.py:969-1131 over the merged list.  dev: the list on the device (device_list), else it is uploaded"""
     t0 = time.perf_counter()
-    dev = None
-    if len(counted.baits):
+    if dev is None and len(counted.baits):
         if int(counted.counts.max()) >= 1 << 32:
             raise InputError("a k-mer was counted %d times, more than the scan's 32-bit counts hold" % int(counted.counts.max()))
         dev = (ctx.upload(counted.baits), ctx.upload(counted.kmers), ctx.upload(counted.counts.astype(np.uint32)))
@@ -641,13 +651,13 @@ def new_stats():
                 path_scan_seconds=0.0, allele_seconds=0.0, distinct_entries=0, path_windows=0, path_matches=0, anchor_windows=0)
 
 
-def run(ctx, items, variants, inputs, K, D, Q, V, fmt, batch, out, budget=EMIT_BUDGET, verbose=False, err=None, stats=None):
-    """the whole command behind its argument checks"""
+def run(ctx, items, variants, inputs, K, D, Q, V, fmt, batch, out, budget=EMIT_BUDGET, verbose=False, err=None, stats=None, pileup=None):
+    """the whole command behind its argument checks.  pileup: where the counted lists gather (None: a DevicePileup)"""
     err = err or sys.stderr
     stats = stats if stats is not None else new_stats()
     for k, v in new_stats().items():
         stats.setdefault(k, v)
-    pileup = Pileup()
+    pileup = pileup if pileup is not None else DevicePileup(ctx)
     read_counts = np.zeros(len(items), dtype=np.int64)
     if items:
         if verbose:
@@ -661,7 +671,9 @@ def run(ctx, items, variants, inputs, K, D, Q, V, fmt, batch, out, budget=EMIT_B
             table.free()
     baits, kmers, counts = pileup.result()
     stats["merge_seconds"] = pileup.merge_seconds
+    stats["merges"] = pileup.merges
     stats["distinct_entries"] = len(baits)
     counted = Counted(baits, kmers, counts, len(items))
-    call_variants(ctx, items, variants, counted, read_counts, K, D, Q, V, fmt, out, err, stats)
+    dev = device_list(ctx, pileup, "scan") if isinstance(pileup, DevicePileup) else None
+    call_variants(ctx, items, variants, counted, read_counts, K, D, Q, V, fmt, out, err, stats, dev=dev)
     return 0

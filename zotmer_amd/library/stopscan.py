@@ -8,7 +8,7 @@ with a stop; each counted k-mer is printed with the nearest k-mer of its transcr
 Here the transcripts are read and indexed on the host (load_index); the index goes to the device as a bait table whose ids are
 anchors on one u32 axis, the transcripts in name order (alufinder.Layout, alufinder.anchor_arrays); the reads stream through in
 batches (fastq_batches.record_batches), one zk_stop_frames and one zk_pileup_count per batch, the ordinal of a batch's first
-read carried across batches and files; the counted lists are merged on the host (alufinder.Pileup); one zk_stop_nearest after
+read carried across batches and files; the counted lists are merged on the device (alufinder.DevicePileup); one zk_stop_nearest after
 the last batch gives the distance, the nearest k-mer and the known flag of every line.  What is printed does not depend on
 where the batches are cut: the draw of a read is a function of (seed, ordinal) (synth.stop_draw).
 """
@@ -22,7 +22,7 @@ import numpy as np
 
 from zotmer_amd import native
 from zotmer_amd.library import seqio
-from zotmer_amd.library.alufinder import InputError, Layout, Pileup, anchor_arrays, kmers_with_pos
+from zotmer_amd.library.alufinder import DevicePileup, InputError, Layout, anchor_arrays, kmers_with_pos
 from zotmer_amd.library.fastq_batches import record_batches, whole
 
 PAD = 1 << 12                   # free coordinates on either side of a transcript: the longest sequence line that may hit one
@@ -114,8 +114,7 @@ def scan_inputs(ctx, table, starts, K, pad, seed, inputs, batch, pileup, verbose
                     raise InputError("%s: %s" % (path, str(e).split(": ", 1)[-1]))
                 bufs = (whole(tx), whole(kmers))
                 if tx.n:
-                    ot, ok, cnt = ctx.pileup_count(tx, kmers, K)
-                    pileup.add(ot.to_host(), ok.to_host(), cnt.to_host())
+                    pileup.add_device(*ctx.pileup_count(tx, kmers, K))
                 first += r
                 if verbose:
                     sys.stderr.write("%s: %d reads processed\n" % (os.path.basename(path), first))
@@ -142,11 +141,11 @@ def report_lines(K, names, tx, kmers, counts, dist, near, flags):
         yield "%s\t%s\t%d\t%d\t%s\t%s" % (kinds[f], x, c, d, y, names[t])
 
 
-def run(ctx, index, inputs, seed, batch, out, pad=PAD, verbose=False, stats=None):
-    """the whole command behind its argument checks"""
+def run(ctx, index, inputs, seed, batch, out, pad=PAD, verbose=False, stats=None, pileup=None):
+    """the whole command behind its argument checks.  pileup: where the counted lists gather (None: a DevicePileup)"""
     K = index.K
     layout = layout_of(index, pad)
-    pileup = Pileup()
+    pileup = pileup if pileup is not None else DevicePileup(ctx)
     n_reads = 0
     t0 = time.perf_counter()
     if index.names:
@@ -159,8 +158,8 @@ def run(ctx, index, inputs, seed, batch, out, pad=PAD, verbose=False, stats=None
     t1 = time.perf_counter()
     if len(tx):
         tk, offs = index.transcript_kmers()
-        dist, near, flags = ctx.stop_nearest(ctx.upload(tx, np.uint32), ctx.upload(kmers, np.uint64), K, ctx.upload(tk), ctx.upload(offs),
-                                             ctx.upload(index.known_stops()))
+        d_tx, d_kmers = pileup.device_result()[:2] if isinstance(pileup, DevicePileup) else (ctx.upload(tx, np.uint32), ctx.upload(kmers, np.uint64))
+        dist, near, flags = ctx.stop_nearest(d_tx, d_kmers, K, ctx.upload(tk), ctx.upload(offs), ctx.upload(index.known_stops()))
         dist, near, flags = dist.to_host(), near.to_host(), flags.to_host()
     else:
         dist, near, flags = np.empty(0, np.uint32), np.empty(0, np.uint64), np.empty(0, np.uint8)
@@ -168,6 +167,6 @@ def run(ctx, index, inputs, seed, batch, out, pad=PAD, verbose=False, stats=None
     for line in report_lines(K, index.names, tx, kmers, counts, dist, near, flags):
         out.write(line + "\n")
     if stats is not None:
-        stats.update(reads=n_reads, stops=int(np.sum(counts)) if len(counts) else 0, lines=len(tx), merges=pileup.merges,
+        stats.update(reads=n_reads, stops=int(np.sum(counts)) if len(counts) else 0, lines=len(tx), merges=pileup.merges, merge_seconds=pileup.merge_seconds,
                      scan_seconds=t1 - t0, nearest_seconds=t2 - t1, report_seconds=time.perf_counter() - t2)
     return 0

@@ -9,7 +9,7 @@ findDup (lines 82-94) then names the tuples (a, b, c, d) of half-mers with ab an
 a != c and b != d, and positions (lines 115-133) places ab and cd on the record, cd more than J behind ab.
 
 Here the reads go through `zot hgvs-find`'s capture on single reads (zk_capture_hits with read_K = K against a both-strand
-bait table, zk_capture_kmers, zk_pileup_count, the host merge), and one zk_dup_join (csrc/dup_join.hip) turns the merged list
+bait table, zk_capture_kmers, zk_pileup_count, zk_pileup_merge into alufinder.DevicePileup), and one zk_dup_join (csrc/dup_join.hip) turns the merged list
 and the records' occurrence table into the rows of findDup + positions and the coverage of every window.  The same kernel,
 given the records' own K-mers as the counted list, gives the phantom warnings of line 332.  The filters, the strict path check
 (hgvsfind.paths) and the table are the reference's, restated over the rows.  What is printed does not depend on where the
@@ -23,7 +23,7 @@ import time
 import numpy as np
 
 from zotmer_amd.library import capture, hgvsfind, seqio
-from zotmer_amd.library.alufinder import Pileup
+from zotmer_amd.library.alufinder import DevicePileup
 from zotmer_amd.library.fastq_batches import record_batches, whole
 from zotmer_amd.library.hgvsfind import EMIT_BUDGET, InputError, render
 
@@ -111,8 +111,15 @@ def join(ctx, dev, index, baits, kmers, counts, min_count, bufs=None):
     of cd) in ascending (record, c, b, d, a, pa, pc) order.  The kernel's order is (record, c, b, a, pa, d, pc)."""
     if index.m == 0:
         return np.zeros(0, np.uint32), np.zeros((0, 3), np.int64)
-    cover, e, i, j = ctx.dup_join(ctx.upload(baits.astype(np.uint32)), ctx.upload(kmers.astype(np.uint64)), ctx.upload(counts.astype(np.uint32)),
-                                  *dev.arrays, index.K, min_count, out=bufs)
+    return join_device(ctx, dev, index, (ctx.upload(baits.astype(np.uint32)), ctx.upload(kmers.astype(np.uint64)), ctx.upload(counts.astype(np.uint32))),
+                       min_count, bufs)
+
+
+def join_device(ctx, dev, index, counted, min_count, bufs=None):
+    """join with the counted list on the device already: (baits u32, k-mers u64, counts u32) DeviceArrays"""
+    if index.m == 0:
+        return np.zeros(0, np.uint32), np.zeros((0, 3), np.int64)
+    cover, e, i, j = ctx.dup_join(*counted, *dev.arrays, index.K, min_count, out=bufs)
     return cover, order_rows(index, e, i, j)
 
 
@@ -215,15 +222,15 @@ def new_stats():
                 phantoms=0)
 
 
-def run(ctx, index, inputs, min_cov, report_all, strict, batch, out, budget=EMIT_BUDGET, verbose=False, err=None, stats=None):
-    """the whole command behind its argument checks"""
+def run(ctx, index, inputs, min_cov, report_all, strict, batch, out, budget=EMIT_BUDGET, verbose=False, err=None, stats=None, pileup=None):
+    """the whole command behind its argument checks.  pileup: where the counted lists gather (None: a DevicePileup)"""
     err = err or sys.stderr
     stats = stats if stats is not None else new_stats()
     for k, v in new_stats().items():
         stats.setdefault(k, v)
     K, N = index.K, len(index.names)
     stats["occurrences"] = index.m
-    pileup = Pileup()
+    pileup = pileup if pileup is not None else DevicePileup(ctx)
     read_counts = np.zeros(N, dtype=np.int64)
     dev = DeviceIndex(ctx, index)
     t0 = time.perf_counter()
@@ -240,12 +247,16 @@ def run(ctx, index, inputs, min_cov, report_all, strict, batch, out, budget=EMIT
             table.free()
     baits, kmers, counts = pileup.result()
     stats["merge_seconds"] = pileup.merge_seconds
+    stats["merges"] = pileup.merges
     stats["distinct_entries"] = len(baits)
-    if len(counts) and int(counts.max()) >= 1 << 32:
+    on_device = None
+    if isinstance(pileup, DevicePileup):
+        on_device = hgvsfind.device_list(ctx, pileup, "join")
+    elif len(counts) and int(counts.max()) >= 1 << 32:
         raise InputError("a k-mer was counted %d times, more than the join's 32-bit counts hold" % int(counts.max()))
     counted = hgvsfind.Counted(baits, kmers, counts, N)
     t0 = time.perf_counter()
-    cover, rows = join(ctx, dev, index, baits, kmers, counts, THRESHOLD)
+    cover, rows = join_device(ctx, dev, index, on_device, THRESHOLD) if on_device is not None else join(ctx, dev, index, baits, kmers, counts, THRESHOLD)
     stats["join_seconds"] += time.perf_counter() - t0
     stats["candidate_rows"] = len(rows)
     t0 = time.perf_counter()

@@ -29,6 +29,7 @@ VARS_TILE = 4096                                # ZK_VARS_TILE
 LINKS_TILE = 1024                               # ZK_LINKS_TILE
 NO_LINK = 0xFFFFFFFF                            # ZK_NO_LINK
 PILEUP_DIAGS, PILEUP_TILE = 256, 4096           # ZK_PILEUP_DIAGS, ZK_PILEUP_TILE
+PILEUP_MERGE_TILE = 2048                        # ZK_PILEUP_MERGE_TILE
 PATH_TILE, PATH_CHUNK = 4096, 256               # ZK_PATH_TILE, ZK_PATH_CHUNK
 LCP_TILE = 256                                  # ZK_LCP_TILE
 SEQTALLY_TILE = 4096                            # ZK_SEQTALLY_TILE
@@ -191,6 +192,8 @@ SIGNATURES = {
     "zk_contig_render": (_i, [_vp, _vp, _u64, _i, _vp, _u64, _vp, _u64, _vp, _u64, _pu64]),
     "zk_anchor_pileup": (_i, [_vp, _vp, _vp, _vp, _u64, _i, _u32, _vp, _vp, _u64, _pu64]),
     "zk_pileup_count": (_i, [_vp, _vp, _vp, _u64, _i, _vp, _vp, _vp, _u64, _pu64]),
+    "zk_pileup_merge": (_i, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _i, _u64, _vp, _vp, _vp, _u64, _pu64]),
+    "zk_narrow_counts": (_i, [_vp, _vp, _vp, _u64, _pu64]),
     "zk_capture_kmers": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _i, _vp, _vp, _u64, _pu64]),
     "zk_path_scan": (_i, [_vp, _vp, _vp, _vp, _u64, _i, C.POINTER(PathWindow), _u32, _vp, _vp, _u64, _pu64]),
     "zk_lcp_resolve": (_i, [_vp, _vp, _u64, _vp, _u64, _i, _vp, _vp]),
@@ -479,7 +482,8 @@ class Context:
                  "pileup": 27, "pileup_cut": 28, "pulldown_tally": 29, "capture_kmers": 30, "path_scan": 31, "lcp_resolve": 32, "scan_place": 33,
                  "seq_tally": 34, "spike_pairs": 35, "spike_size": 36, "ksnp_flank": 37, "ksnp_pairs": 38,
                  "stop_frames": 39, "stop_emit": 40, "stop_nearest": 41, "fizzle_count": 42, "fizzle_emit": 43,
-                 "hgvs_draw": 44, "hgvs_fill": 45, "hgvs_size": 46, "hgvs_render": 47, "dup_cover": 48, "dup_join": 49}
+                 "hgvs_draw": 44, "hgvs_fill": 45, "hgvs_size": 46, "hgvs_render": 47, "dup_cover": 48, "dup_join": 49,
+                 "pileup_merge": 50}
 
     # zk_tune's knob ids (independent assignments in the library: the order they are applied in does not matter)
     TUNE_IDS = dict(sort_variant=1, pairs_variant=2, short_sort=3, side_div=4, xcd_group=5, comm_chunk=6, early_collapse=7,
@@ -1108,6 +1112,44 @@ class Context:
         oc, ok, cnt = self.empty(cap, np.uint32), self.empty(cap, np.uint64), self.empty(cap, np.uint32)
         self._check(self.lib.zk_pileup_count(self.h, coords.ptr, kmers.ptr, coords.n, int(K), oc.ptr, ok.ptr, cnt.ptr, cap, C.byref(n)))
         return oc.view(n.value), ok.view(n.value), cnt.view(n.value)
+
+    # ---- counted lists made one on the device (csrc/pileup_merge.hip) -------------------------------------------
+    def pileup_merge_into(self, a, b, out):
+        """zk_pileup_merge of two counted lists, each (coordinates u32, k-mers u64, counts) ascending by (coordinate, k-mer) --
+        a's counts u64, b's u32 or u64 -- into the three arrays of out (u32, u64, u64) -> (pairs written or, if they did not
+        fit, needed; whether they fit)"""
+        assert a[0].n == a[1].n == a[2].n and b[0].n == b[1].n == b[2].n
+        assert a[0].dtype.itemsize == 4 and a[1].dtype.itemsize == 8 and a[2].dtype.itemsize == 8
+        assert b[0].dtype.itemsize == 4 and b[1].dtype.itemsize == 8 and b[2].dtype.itemsize in (4, 8)
+        assert out[0].dtype.itemsize == 4 and out[1].dtype.itemsize == 8 and out[2].dtype.itemsize == 8
+        n = C.c_uint64(0)
+        rc = self.lib.zk_pileup_merge(self.h, a[0].ptr, a[1].ptr, a[2].ptr, a[0].n, b[0].ptr, b[1].ptr, b[2].ptr, 8 * b[2].dtype.itemsize, b[0].n,
+                                      out[0].ptr, out[1].ptr, out[2].ptr, min(o.n for o in out), C.byref(n))
+        if rc != ZK_ENOSPC:
+            self._check(rc)
+        return n.value, rc == ZK_OK
+
+    def pileup_merge(self, a, b, out=None):
+        """the union of two counted lists as (coordinates u32, k-mers u64, counts u64) views, the counts of a pair that both
+        hold added (zk_pileup_merge).  out: three arrays to write into first; one retry with the length the entry reports when
+        they are too small."""
+        o = out if out is not None else (self.empty(a[0].n + b[0].n, np.uint32), self.empty(a[0].n + b[0].n, np.uint64),
+                                         self.empty(a[0].n + b[0].n, np.uint64))
+        n, fit = self.pileup_merge_into(a, b, o)
+        if not fit:
+            o = (self.empty(n, np.uint32), self.empty(n, np.uint64), self.empty(n, np.uint64))
+            n, fit = self.pileup_merge_into(a, b, o)
+            assert fit
+        return tuple(x.view(n) for x in o)
+
+    def narrow_counts(self, counts):
+        """u64 counts -> (u32 DeviceArray of min(count, 2^32 - 1), the largest count): the counterpart of widen
+        (zk_narrow_counts)"""
+        assert counts.dtype.itemsize == 8
+        out = self.empty(counts.n, np.uint32)
+        mx = C.c_uint64(0)
+        self._check(self.lib.zk_narrow_counts(self.h, counts.ptr, out.ptr, counts.n, C.byref(mx)))
+        return out, mx.value
 
     # ---- variants called from captured read pairs (csrc/hgvs_find.hip) -----------------------------------------
     def capture_kmers_into(self, pairs, text1, lines1, n_reads, K, text2, lines2, out_baits, out_kmers):
