@@ -11,7 +11,9 @@
 //   * side lists of 128 entries a wave, drained 64 at a time as soon as 64 are there (full wavefronts, no worst-case tile to hold);
 // -- 11 K entries in 76 KB, and while one workgroup of the CU sorts and writes its block the other one inserts.
 // UNSORTED (the strand route at odd K, strand_blocks.hip, which sorts every block again with its mirror image): the block's distinct
-// words are written compacted in table order instead -- no counting sort, no ranks (12.1 -> 9.4 ms at config 2, profiles/r08).
+// words are written compacted in table order instead -- no counting sort, no ranks (12.1 -> 9.4 ms at config 2, profiles/r08).  Every
+// wave compacts the entries of its own table rows in LDS, in place and without a barrier, and writes them in dense rounds of 64
+// (see dedupe2_block; with the mirror words 11.12 -> 10.39 ms, profiles/r29).
 // MIRROR (that route, 32-bit tags in): every word's mirror image, rc(k-mer) << pack | count, is written as well, from the registers
 // that hold the word -- densely into DedupeArgs::m_out, in no order the route needs: a block takes the place of its words with one add
 // on a global cursor, the waves theirs inside it from the LDS add that places the words themselves.  The digits of the two passes
@@ -215,23 +217,54 @@ __device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, S& sm, Dedupe
     }
     if constexpr (UNSORTED) {
         // ---- the block's entries in table order, compacted (the strand route sorts every block again: strand_blocks.hip) ------
-        // thread t owns the entries t, t + BLOCK, ...; a wave counts what its lanes hold (one ballot per round), takes its share of
-        // the block's words with one LDS add and writes them, every round a run of consecutive words
+        // A wave owns the table rows (j, wave) = the 64 entries j * BLOCK + wave * 64 + lane, j < SPT, from the barrier above to the one
+        // at the block's end.  It compacts them in place: the rows are read SPT / 2 at a time (no access under a branch, one wait a
+        // batch), and the live entry of rank p in the wave's stream -- rows in order, lanes in order -- goes back to lane p & 63 of the
+        // wave's row p >> 6.  p never exceeds the place read and a wave's LDS operations complete in order, so a write lands only in a
+        // row the wave has read already: no barrier, no second buffer.  The last rank is what the wave adds to nout.  Then
+        // ceil(wn / 64) dense rounds, lane l of round r taking entry 64 r + l: every lane of a round but the last one's builds a word
+        // (and its mirror image), and a round's stores are whole runs of 512 bytes.  About 27 % of a table is in use at config 2, so
+        // six or seven dense rounds do what took SPT = 22 rounds of mostly idle lanes, each with two dependent LDS reads under its
+        // branch (the kernel 11.12 -> 10.39 ms, profiles/r29; reading rows and tags ahead into registers alone, 22 rounds kept: 10.99;
+        // with both dense rounds of a pair always run and the slot from shifts and masks: 10.80).
         // MIRROR: the block takes the place of its mirror words in m_out with ONE add on the global cursor, once every wave's share is
         // in nout (a barrier); the answer travels while the next block's bounds are fetched, and a second barrier hands it to the waves,
         // whose words lie in m_out as they lie in the block.  (An add per wave needs neither barrier, but 2 M adds a step on one word
         // that every XCD shares pass through one place: the step took 87-90 ms against 72-73.)
         if constexpr (!MIRROR) next_block(nchunk);          // the next block's first tile travels while this one is written
         const u16* cnt16 = reinterpret_cast<const u16*>(sm.cnt);
-        u32 wn = 0;
+        static_assert(SPT % 2 == 0, "two batches of rows; dense rounds are read two at a time");
+        constexpr int RB = SPT / 2;
+        u32* const wkeys = sm.keys + wave * 64;          // the wave's rows: entry s of row j at [j * BLOCK + s]
+        u16* const wcnt = reinterpret_cast<u16*>(sm.cnt) + wave * 64;
+        u32 wn = 0;          // the wave's entries so far (the same in every lane)
 #pragma unroll
-        for (int j = 0; j < SPT; j++) wn += (u32)__popcll(__ballot(cnt16[tid + j * BLOCK] != 0));
+        for (int j0 = 0; j0 < SPT; j0 += RB) {
+            u32 rt[RB], rc[RB];
+#pragma unroll
+            for (int r = 0; r < RB; r++) {
+                rt[r] = sm.keys[tid + (j0 + r) * BLOCK];
+                rc[r] = cnt16[tid + (j0 + r) * BLOCK];
+            }
+#pragma unroll
+            for (int r = 0; r < RB; r++) asm volatile("" : "+v"(rt[r]));          // (opaque: or a tag's read sinks under its entry's branch)
+#pragma unroll
+            for (int r = 0; r < RB; r++) {
+                const u64 bal = __ballot(rc[r] != 0);
+                if (rc[r]) {
+                    const u32 p = __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, wn));          // < SPT * 64
+                    const u32 s = p + (p >> 6) * (u32)(BLOCK - 64);          // row p >> 6, lane p & 63
+                    wkeys[s] = rt[r];
+                    wcnt[s] = (u16)rc[r];
+                }
+                wn += (u32)__popcll(bal);
+            }
+        }
         u32 wbase = 0;
         if (lane == 0 && wn) wbase = atomicAdd(&sm.nout, wn);
         wbase = (u32)__shfl((int)wbase, 0, 64);
-        u32 mrun = 0;          // the wave's mirror words written so far
-        u64* mp = nullptr;          // ... from here on; null: none are written
-        u64* op = nullptr;          // (MIRROR: the wave's words from here on, both places from the one count)
+        u64* mp = nullptr;          // the wave's mirror words from here on; null: none are written
+        u64* op = nullptr;          // the wave's words from here on (MIRROR: both places from the one count)
         if constexpr (MIRROR) {
             __syncthreads();
             u64 g = 0;
@@ -248,33 +281,43 @@ __device__ __forceinline__ void dedupe2_block(const DedupeArgs& a, S& sm, Dedupe
         }
         DD_PHASE(3);          // entries counted, the wave's words placed
         const u64 hi_part = (u64)chunk << a.tag_bits;
-#pragma unroll
-        for (int j = 0; j < SPT; j++) {
-            const u32 c = cnt16[tid + j * BLOCK];
-            const u64 bal = __ballot(c != 0);          // (again: 22 ballots kept from the count above spill 34 scalar registers)
-            if (c) {
-                const u64 k = hi_part | (u64)sm.keys[tid + j * BLOCK];
+        if constexpr (!MIRROR) op = a.out + lo + wbase;
+        // entry i = 64 r + lane of the wave's stream, its tag and count read beforehand; beyond wn the lane holds whatever lies there
+        auto dense = [&](u32 i, u32 t, u32 c) {
+            const bool live = i < wn;
+            const u64 k = hi_part | (u64)t;
+            const u64 cw = (u64)(c > maxc ? 0u : c);
+            if (live) {
                 if (c > maxc) {
                     const u32 at = atomicAdd(a.n_big, 1u);
                     if (at < a.big_cap) { a.big[2 * (u64)at] = k; a.big[2 * (u64)at + 1] = c; }
                     atomicOr(a.flags, 2u);
                 }
-                const u64 cw = (u64)(c > maxc ? 0u : c);
-                if constexpr (MIRROR) op[mrun + popc_below(bal)] = (k << a.pack) | cw;
-                else a.out[lo + wbase + popc_below(bal)] = (k << a.pack) | cw;
-                if constexpr (MIRROR) {
-                    if (mp) {          // (the block's place + wbase + mrun + popc_below(bal) < the block's place + nout <= m_cap)
-                        const u64 mw = (revcomp(a.m_K, k) << a.pack) | cw;
-                        mp[mrun + popc_below(bal)] = mw;
-                        // the digits are the word's top bits: the second one is all there is above the first (one pass: 0, never read)
-                        const u32 top = (u32)(mw >> a.m_shift[0]);
-                        atomicAdd(&sm.bins[0][top & ((1u << a.m_bits[0]) - 1u)], 1u);
-                        atomicAdd(&sm.bins[1][(top >> a.m_bits[0]) & (MIRROR_RADIX - 1)], 1u);
-                    }
+                op[i] = (k << a.pack) | cw;
+            }
+            if constexpr (MIRROR) {
+                if (mp) {          // (the block's place + wbase + i < the block's place + nout <= m_cap)
+                    const u64 mw = (revcomp(a.m_K, k) << a.pack) | cw;
+                    if (live) mp[i] = mw;
+                    // the digits are the word's top bits: the second one is all there is above the first (one pass: 0, never read);
+                    // a lane beyond wn adds 0, wherever: no LDS access under a per-entry branch
+                    const u32 top = (u32)(mw >> a.m_shift[0]);
+                    atomicAdd(&sm.bins[0][top & ((1u << a.m_bits[0]) - 1u)], live ? 1u : 0u);
+                    atomicAdd(&sm.bins[1][(top >> a.m_bits[0]) & (MIRROR_RADIX - 1)], live ? 1u : 0u);
                 }
             }
-            if constexpr (MIRROR) mrun += (u32)__popcll(bal);
-            else wbase += (u32)__popcll(bal);
+        };
+        for (u32 r = 0; r * 64 < wn; r += 2) {          // (wn <= SPT * 64 and SPT is even: row r + 1 exists)
+            u32 rt[2], rc[2];
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                rt[e] = sm.keys[tid + (r + e) * BLOCK];
+                rc[e] = cnt16[tid + (r + e) * BLOCK];
+            }
+#pragma unroll
+            for (int e = 0; e < 2; e++) asm volatile("" : "+v"(rt[e]));          // (opaque: both rounds read together, ahead of any branch)
+            dense(r * 64 + (u32)lane, rt[0], rc[0]);
+            if ((r + 1) * 64 < wn) dense((r + 1) * 64 + (u32)lane, rt[1], rc[1]);
         }
         __syncthreads();
         if (tid == 0) a.nwords[chunk] = sm.nout;          // (read before the caller's barrier; the next block clears it after)
