@@ -135,3 +135,32 @@ def write_case(case, d):
             f.write(case["pop"])
         words += ["-m", os.path.join(d, "pop.txt")]
     return words
+
+
+# ---- builders of the device tests ----------------------------------------------------------------------------------------------
+ALPHABET = np.frombuffer(b"ACGTACGTACGTacgtNn*-RyU.", dtype=np.uint8)      # upper and lower case, N, and bytes that are no base
+
+
+def allele_text(seed, n):
+    """n bytes of ALPHABET as a str (latin-1)"""
+    return ALPHABET[(synth.rnd(seed, 1, np.arange(n, dtype=np.uint64)) % np.uint64(len(ALPHABET))).astype(np.intp)].tobytes().decode("latin-1")
+
+
+def tables(zones, windows=None):
+    """the restatement's zones [(head, pairs, [(text, s0, e0)] * 2)] as the arrays of zk_spike_pairs; windows: {(zone, allele):
+    (lo, hi)} where the window is not the whole allele"""
+    texts, rows, at = [], [], 0
+    for zi, (head, n, als) in enumerate(zones):
+        for ai, (text, s0, e0) in enumerate(als):
+            lo, hi = (windows or {}).get((zi, ai), (0, len(text)))
+            t = text[lo:hi].encode("latin-1")
+            rows += [at, lo, len(t), len(text), s0, e0]
+            texts.append(t)
+            at += len(t)
+    first = np.zeros(len(zones) + 1, dtype=np.uint64)
+    first[1:] = np.cumsum([z[1] for z in zones])
+    heads = [z[0].encode("latin-1") for z in zones]
+    offs = np.zeros(len(zones) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(h) for h in heads])
+    return (np.frombuffer(b"".join(texts), dtype=np.uint8), np.asarray(rows, dtype=np.int64).view(np.uint64), first,
+            np.frombuffer(b"".join(heads), dtype=np.uint8), offs)

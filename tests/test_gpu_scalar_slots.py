@@ -3,18 +3,30 @@
 by one entry point read as the fresh result of another.  So: ONE context, every entry point that reads scalars back, on
 inputs just past one tile of its scheme, each result against numpy / the host restatements -- and then the same list
 again in reverse order, when every host word holds what some other call left there."""
+import random
+
 import numpy as np
 import pytest
 
 from oracle import zkoracle as zo
+from tests import _contigs_restatement as CR
+from tests import _ksnp_brute as KB
+from tests import _ksnp_cases as KC
 from tests import _spectrum_host as H
+from tests import _spikein_restatement as SR
+from tests import _stop_cases as SC
+from tests import _stop_restatement as ST
 from tests import _strand_restatement as R
+from tests import _vardyger_cases as VC
+from tests import _vardyger_restatement as VR
+from tests._spikein_cases import allele_text, tables as spike_tables
 from zotmer_amd import native, synth
 
 pytestmark = pytest.mark.gpu
 
 N_RLE = 8192 + 1 + 100          # csrc/select.hip RLE_TILE: 8 192 keys
 N_CP = 4096 + 1 + 50            # csrc/compact.hpp CP_TILE, select / merge tiles: 4 096 items
+N_SCAN = 2048 + 1 + 60          # csrc/codec.hip SCAN_TILE: 2 048 items
 M64 = (1 << 64) - 1
 
 
@@ -235,6 +247,106 @@ def make_cases():
         assert np.array_equal(a.to_host(), np.array(wa, dtype=np.uint64)) and np.array_equal(b.to_host(), np.array(wb, dtype=np.uint64))
         assert ctx.format_pairs(a, b).to_host().tobytes() == want_lines
 
+    # ---- the entries whose total lands in the one shared word (csrc/codec.hip scan_total): sizes just past one 2 048-item scan tile
+    totals = dict(line_ends=int((text == 10).sum()), strand_pairs=wst["pairs"], format_pairs=len(want_lines),
+                  project_sum_a=len(want_pa[0]), project_sum_b=len(want_pb[0]))
+
+    # spike_pairs: the only entry with two landings
+    a1, a2 = allele_text(1, 3000), allele_text(2, 3100)
+    sp_zones = [("chr1:100-900 a ", 1000, [(a1, 100, 900), (a2, 100, 905)]), ("chr1:901-901 None ", 0, [(a1, 901, 901), (a2, 901, 901)]),
+                ("chr2:1000-2999 b ", N_SCAN - 1000, [(a2, 1000, 2999), (a1, 1000, 2899)])]
+    sp_scalars = (77, 20, 60, SR.sd_q(60, 0.1), SR.frac32(0.3), SR.frac32(0.05))
+    sp_tables = spike_tables(sp_zones)
+    want_m1, want_m2, _ = SR.records(*sp_scalars, sp_zones)
+    totals.update(spike_mate1=len(want_m1), spike_mate2=len(want_m2))
+
+    @case
+    def spike_pairs(ctx):
+        o1, o2 = ctx.spike_pairs(*[ctx.upload(t) for t in sp_tables], *sp_scalars, 0, N_SCAN)
+        assert (o1.n, o2.n) == (len(want_m1), len(want_m2))
+        assert o1.to_host().tobytes() == want_m1.encode("latin-1") and o2.to_host().tobytes() == want_m2.encode("latin-1")
+
+    # contig_render: one offset more than a scan tile of contigs of one to three nodes
+    CK = 25
+    cr_keys = distinct_sorted(rng, 3000, 2 * CK)
+    cr_paths = [rng.integers(0, len(cr_keys), size=1 + i % 3).tolist() for i in range(N_SCAN)]
+    want_fasta = CR.text_of(CK, cr_keys.tolist(), cr_paths).encode()
+    totals.update(contig_render=len(want_fasta))
+
+    @case
+    def contig_render(ctx):
+        nodes = np.array([j for p in cr_paths for j in p], dtype=np.uint32)
+        offs = np.cumsum([0] + [len(p) for p in cr_paths]).astype(np.uint64)
+        assert ctx.contig_render(ctx.upload(cr_keys), CK, ctx.upload(nodes), ctx.upload(offs)).to_host().tobytes() == want_fasta
+
+    # ksnp: groups of one, a group for the workgroup kernel and one past ZK_KSNP_LDS_GROUP for the tile-pair kernel (its tile pairs are scanned too)
+    KK = 13
+    ks = sum((KC.group(KK, p, KC.random_lows(KK, 1, 50 + p)) for p in range(1100)), [])
+    ks += KC.group(KK, 1100, KC.planted_lows(KK, native.KSNP_LDS_GROUP + 6, 3)) + KC.group(KK, 1101, KC.planted_lows(KK, 40, 4))
+    ks = np.array(sorted(ks), dtype=np.uint64)
+    assert len(ks) > N_SCAN
+    want_snps = KB.run(KK, KC.HAMMING, 1, ks)
+    # (the entry scans twice more on its way: the groups of two or more, and the tile pairs of the groups past ZK_KSNP_LDS_GROUP)
+    ks_sizes = [b - a for a, b in KB.group_slices(KK, ks) if b - a >= 2]
+    ks_tiles = [-(-s // native.KSNP_PAIR_TILE) for s in ks_sizes if s > native.KSNP_LDS_GROUP]
+    totals.update(ksnp=len(want_snps), ksnp_groups=len(ks_sizes), ksnp_tile_pairs=sum(t * (t + 1) // 2 for t in ks_tiles))
+
+    @case
+    def ksnp_components(ctx):
+        assert np.array_equal(ctx.ksnp(ctx.upload(ks), KK, native.KSNP_HAMMING, 1).to_host(), want_snps)
+
+    # dup_join: more entries than a scan tile, a duplication in every sequence
+    from zotmer_amd.library import vardyger
+    DK = 8
+    py = random.Random(9)
+    dj_records, dj_counts = [], []
+    for r in range(24):
+        seq = VC.rand_seq(py, 70 + r % 13)
+        dj_records.append(("s%03d" % r, seq))
+        dj_counts.append({x: py.choice((9, 10, 40)) for x in VR.kmers_list(DK, VC.duplicated(seq, 20, 5 + r % 9), True)})
+    dj_index = vardyger.Index(DK, dj_records)
+    dj_lists = VC.counted_from(dj_counts)
+    dj_tables = [np.asarray(t) for t in (dj_index.rseq, dj_index.rkmer, dj_index.rpos, dj_index.by_second)]
+    assert len(dj_lists[0]) > N_SCAN
+    want_cover, want_rows = VC.join_by_its_contract(*dj_lists, *[t.tolist() for t in dj_tables], DK, 10)
+    totals.update(dup_join=len(want_rows))
+
+    @case
+    def dup_join(ctx):
+        lists = [ctx.upload(np.array(a, dtype=dt)) for a, dt in zip(dj_lists, (np.uint32, np.uint64, np.uint32))]
+        cover, e, i, j = ctx.dup_join(*lists, *[ctx.upload(t) for t in dj_tables], DK, 10)
+        assert cover.tolist() == want_cover and list(zip(e.tolist(), i.tolist(), j.tolist())) == want_rows
+
+    # stop_frames: more reads than a scan tile, cut from transcripts with a stop codon every few bases
+    from zotmer_amd.library import stopscan
+    TK, PAD, SEED = 25, 128, 17
+    sf_records = [("tx%d" % t, "".join(VC.rand_seq(py, py.randrange(2, 9)) + py.choice(("TAA", "TAG", "TGA", "TTA", "CTA", "TCA")) for _ in range(40)))
+                  for t in range(3)]
+    sf_reads = []
+    for g in range(N_SCAN):
+        seq = sf_records[g % 3][1]
+        p = py.randrange(0, len(seq) - 60)
+        sf_reads.append(seq[p:p + 60] if g % 2 else SC.rc(seq[p:p + 60]))
+    sf_ref = ST.Index(TK, sf_records)
+    sf_index = stopscan.Index(TK, [(nm, seq.encode("latin-1")) for nm, seq in sf_records])
+    t_of = {nm: t for t, nm in enumerate(sf_index.names)}
+    want_stops = sorted((t_of[nm], x) for g, seq in enumerate(sf_reads) for nm, x in ST.read_stops(sf_ref, seq, SEED, g)[0])
+    sf_fastq = np.frombuffer(SC.fastq_text(sf_reads).encode(), dtype=np.uint8)
+    totals.update(stop_frames=len(want_stops), stop_lines=int((sf_fastq == 10).sum()))          # (the case calls line_ends on its text)
+
+    @case
+    def stop_frames(ctx):
+        layout = stopscan.layout_of(sf_index, PAD)
+        table = stopscan.anchor_table(ctx, sf_index, layout)
+        try:
+            d = ctx.upload(sf_fastq)
+            tx, kmers = ctx.stop_frames(table, ctx.upload(stopscan.starts_of(layout)), d, ctx.line_ends(d), N_SCAN, TK, PAD, SEED, 0)
+            assert sorted(zip(tx.to_host().tolist(), kmers.to_host().tolist())) == want_stops
+        finally:
+            table.free()
+
+    # a word left in the shared landing by one entry can pass for the total of another only if the two totals are equal
+    assert len(set(totals.values()) | {0}) == len(totals) + 1, totals
     return cases
 
 

@@ -137,7 +137,6 @@ int zk_bait_table_from_arrays(zk_ctx* c, int K, const uint64_t* d_keys, uint64_t
                            2 * K, d_offs, d_ids, (u64)n_ids, (u64)n_records, verdict);
         ZK_HIP(c, hipGetLastError());
         ZK_TRY(fetch(c, &c->h_scalars->table_verdict));
-        ZK_TRY(stream_sync(c));
         ZK_TRY(check_device_error(c));
         const u32 v = (u32)c->h_scalars->table_verdict;
         if (v != 0xffffffffu)
@@ -160,7 +159,6 @@ int zk_bait_record_sizes(zk_ctx* c, const zk_bait_table* t, uint32_t* d_sizes) {
         hipLaunchKernelGGL(record_sizes_kernel, dim3(grid_cap(c, div_up(t->n_ids, 256), 16)), dim3(256), 0, c->stream, t->ids, (u64)t->n_ids, d_sizes);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
     return check_device_error(c);
 }
 
@@ -178,7 +176,6 @@ int zk_bait_tally(zk_ctx* c, const zk_bait_table* t, const uint64_t* d_kmers, ui
         prof_end(c);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
     return check_device_error(c);
 }
 

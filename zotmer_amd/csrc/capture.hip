@@ -78,7 +78,6 @@ int bait_table_directory(zk_ctx* c, zk_bait_table* t) {
     const u64 nb = 1ull << bits;
     ZK_TRY(tmalloc(c, (void**)&t->dir, 4 * (nb + 1)));
     ZK_TRY(key_dir_build(c, t->keys, (u64)t->n_keys, t->kbits - bits, nb, t->dir));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
     return check_device_error(c);
 }
 
@@ -181,7 +180,6 @@ int capture_lookup(zk_ctx* c, const zk_bait_table* baits, const zk_bait_table* v
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->capture_raw));
-    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     *raw = c->h_scalars->capture_raw;
     return ZK_OK;
@@ -211,13 +209,11 @@ static int capture_hits(zk_ctx* c, const zk_bait_table* baits, const zk_bait_tab
     ZK_TRY(capture_lookup(c, baits, veto, RK, m1, m2, n_reads, pairs, cap, nullptr, &raw));
     if (raw > cap) {
         *n_pairs = raw;
-        return fail(c, ZK_ENOSPC, "capture: %llu (bait, read) pairs before deduplication, room for %llu", (unsigned long long)raw,
-                    (unsigned long long)cap);
+        return no_room(c, "capture", "(bait, read) pairs before deduplication", raw, cap);
     }
     if (raw == 0) return ZK_OK;
     ZK_TRY(arena_require(c, capture_sort_bytes(raw), capture_sort_bytes(raw)));
     ZK_TRY(capture_sort_dedupe(c, baits, pairs, raw, n_pairs));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
     return check_device_error(c);
 }
 
@@ -284,17 +280,14 @@ static int capture_gather(zk_ctx* c, const u64* pairs, uint64_t n, uint32_t nb, 
     hipLaunchKernelGGL(bait_spans_kernel, dim3(grid_cap(c, div_up((u64)nb + 1, 256), 16)), dim3(256), 0, c->stream, pairs, (u64)n, len, nb, d_spans);
     ZK_HIP(c, hipGetLastError());
     ZK_HIP(c, hipMemcpyAsync(spans, d_spans, 16ull * (nb + 1), hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
     ZK_TRY(check_device_error(c));
     const uint64_t total = spans[2ull * nb + 1];
     *n_bytes = total;
-    if (total > cap)
-        return fail(c, ZK_ENOSPC, "capture gather: %llu bytes of records, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    if (total > cap) return no_room(c, "capture gather", "bytes of records", total, cap);
     if (n) {
         hipLaunchKernelGGL(record_copy_kernel, dim3(grid_cap(c, div_up(n, 4), 16)), dim3(256), 0, c->stream, pairs, (u64)n, text, lines, (u64)n_lines, len, out);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
     return check_device_error(c);
 }
 
@@ -332,10 +325,9 @@ int zk_line_ends(zk_ctx* c, const uint8_t* d_text, uint64_t n, uint64_t* d_out, 
     uint64_t total = 0;
     ZK_TRY(compact_count(c, nl, n, &cnt, &total));
     *n_lines = total;
-    if (total > cap) return fail(c, ZK_ENOSPC, "zk_line_ends: %llu lines, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    if (total > cap) return no_room(c, "zk_line_ends", "lines", total, cap);
     if (total && !d_out) return fail(c, ZK_EINVAL, "bad argument: d_out");
     ZK_TRY(compact_write(c, nl, n, cnt));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
     return check_device_error(c);
 }
 

@@ -157,6 +157,18 @@ int scan64_inclusive(zk_ctx* c, u64* d_v, uint64_t n) {
     return ZK_OK;
 }
 
+// ... and its last sum on the host: *total (0 when n == 0), after one synchronisation that also reports a device error
+int scan_total(zk_ctx* c, u64* v, uint64_t n, uint64_t* total) {
+    *total = 0;
+    if (n) {
+        ZK_TRY(scan64_inclusive(c, v, n));
+        ZK_TRY(fetch(c, &c->h_scalars->scan_landing[0], v + n - 1));
+    }
+    ZK_TRY(check_device_error(c));
+    if (n) *total = c->h_scalars->scan_landing[0];
+    return ZK_OK;
+}
+
 __global__ void add_u64_kernel(u64* __restrict__ v, u64 n, u64 x) {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) v[i] += x;
 }

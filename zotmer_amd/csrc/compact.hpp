@@ -78,13 +78,8 @@ static int compact_count(zk_ctx* c, const P& p, uint64_t n, u64** tile_incl, uin
     ZK_TRY(arena_alloc(c, 8 * tiles, (void**)&cnt));
     hipLaunchKernelGGL((compact_count_kernel<P>), dim3((u32)tiles), dim3(CP_BLOCK), 0, c->stream, p, (u64)n, cnt);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(scan64_inclusive(c, cnt, tiles));
-    ZK_TRY(fetch(c, &c->h_scalars->compact_total, cnt + tiles - 1));
-    ZK_TRY(stream_sync(c));
-    ZK_TRY(check_device_error(c));
     *tile_incl = cnt;
-    *total = c->h_scalars->compact_total;
-    return ZK_OK;
+    return scan_total(c, cnt, tiles, total);
 }
 
 template <class P>

@@ -18,6 +18,10 @@ int fail(zk_ctx* c, int code, const char* fmt, ...) {
     return code;
 }
 
+int no_room(zk_ctx* c, const char* entry, const char* noun, uint64_t needed, uint64_t cap) {
+    return fail(c, ZK_ENOSPC, "%s: %llu %s, room for %llu", entry, (unsigned long long)needed, noun, (unsigned long long)cap);
+}
+
 void arena_reset(zk_ctx* c) { c->arena_off = 0; }
 
 int arena_alloc(zk_ctx* c, uint64_t bytes, void** p) {

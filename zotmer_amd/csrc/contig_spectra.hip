@@ -187,7 +187,6 @@ static int contig_spectra(zk_ctx* c, const u8* stream, uint64_t n, int K, int bo
     st->n_bins = n_bins;
     const bool bins_fit = n_bins <= cap_bins;
     if (bins_fit) ZK_TRY(compact_write(c, lb, n_uniq, cnt));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
     ZK_TRY(check_device_error(c));
     if (!keys_fit || !bins_fit)
         return fail(c, ZK_ENOSPC, "contig spectra: %llu bins and %llu keys, room for %llu and %llu", (unsigned long long)n_bins,
@@ -206,7 +205,6 @@ static int count_spectrum(zk_ctx* c, const u64* keys, const void* cnts, int coun
     SpectrumEntries se{keys, cnts, count_bits, K, both, seed, p, (u64*)room, c->d_err};
     ZK_TRY(compact_count(c, se, 2 * n, &cnt, &m));
     ZK_TRY(compact_write(c, se, 2 * n, cnt));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
     ZK_TRY(check_device_error(c));
     return count_hist(c, room, 64, m, vals, freq, cap_bins, n_bins);
 }

@@ -142,7 +142,6 @@ static int debruijn_links(zk_ctx* c, const u64* k, uint64_t n, int K, u32* next,
     hipLaunchKernelGGL(links_rc_kernel, dim3(grid_cap(c, div_up(n, 256), 16)), dim3(256), 0, c->stream, k, (u32)n, K, d, rcr);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 
@@ -210,22 +209,18 @@ static int contig_render(zk_ctx* c, const u64* k, uint64_t n, int K, const u32* 
                        (u64)n_contigs, (u64)n, K, len, bad);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(scan64_inclusive(c, len, n_contigs));
     ZK_TRY(fetch(c, &c->h_scalars->render_bad));
-    ZK_TRY(fetch(c, &c->h_scalars->render_bytes, len + n_contigs - 1));
-    ZK_TRY(stream_sync(c));
-    ZK_TRY(check_device_error(c));
+    uint64_t total;
+    ZK_TRY(scan_total(c, len, n_contigs, &total));
     if (c->h_scalars->render_bad)
         return fail(c, ZK_EINVAL, "zk_contig_render: the offsets do not ascend from 0 to n_nodes, or a node is not below n");
-    *n_bytes = c->h_scalars->render_bytes;
-    if (*n_bytes > cap)
-        return fail(c, ZK_ENOSPC, "zk_contig_render: %llu bytes of text, room for %llu", (unsigned long long)*n_bytes, (unsigned long long)cap);
+    *n_bytes = total;
+    if (total > cap) return no_room(c, "zk_contig_render", "bytes of text", total, cap);
     prof_begin(c, ZK_PROF_CONTIG_RENDER, 12 * n_nodes + *n_bytes);
     hipLaunchKernelGGL(contig_write_kernel, dim3(grid_cap(c, div_up(n_nodes, 256), 16)), dim3(256), 0, c->stream, k, K, nodes, (u64)n_nodes,
                        offs, (u64)n_contigs, len, out);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 

@@ -175,10 +175,7 @@ static int dup_join(zk_ctx* c, const DupList& L, const DupOcc& R, int K, u32 min
     hipLaunchKernelGGL(dup_cover_kernel, dim3(grid_cap(c, div_up(m, DJ_BLOCK), 16)), dim3(DJ_BLOCK), 0, c->stream, L, R, cover);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    if (n == 0) {
-        ZK_TRY(stream_sync(c));
-        return check_device_error(c);
-    }
+    if (n == 0) return check_device_error(c);
     const uint64_t room = 8 * n + (4 << 20);
     ZK_TRY(arena_require(c, room, room));
     u64* cells;
@@ -189,20 +186,15 @@ static int dup_join(zk_ctx* c, const DupList& L, const DupOcc& R, int K, u32 min
                        (u32*)nullptr, (u32*)nullptr, (u32*)nullptr, (u64)0);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(scan64_inclusive(c, cells, n));
-    ZK_TRY(fetch(c, &c->h_scalars->dup_total, cells + n - 1));
-    ZK_TRY(stream_sync(c));
-    ZK_TRY(check_device_error(c));
-    const uint64_t total = c->h_scalars->dup_total;
-    *n_out = total;
-    if (total > cap) return fail(c, ZK_ENOSPC, "zk_dup_join: %llu rows, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    ZK_TRY(scan_total(c, cells, n, n_out));
+    const uint64_t total = *n_out;
+    if (total > cap) return no_room(c, "zk_dup_join", "rows", total, cap);
     if (total == 0) return ZK_OK;
     prof_begin(c, ZK_PROF_DUP_JOIN, 16 * n + 12 * total);
     hipLaunchKernelGGL(dup_join_kernel<true>, dim3(grid), dim3(DJ_BLOCK), 0, c->stream, L, R, (const u32*)cover, K, min_count, cells, out_e,
                        out_i, out_j, (u64)cap);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 

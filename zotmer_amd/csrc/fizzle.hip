@@ -203,14 +203,9 @@ static int fizzle_votes(zk_ctx* c, const zk_bait_table* classes, int K, Mate m1,
     hipLaunchKernelGGL(fizzle_count_kernel, dim3(grid), dim3(FZ_BLOCK), 0, c->stream, bt, m1, m2, (u64)n_reads, K, ent, one, hits);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(scan64_inclusive(c, ent, n_rec));
-    ZK_TRY(fetch(c, &c->h_scalars->fizzle_total, ent + n_rec - 1));
-    ZK_TRY(stream_sync(c));
-    ZK_TRY(check_device_error(c));
-    const uint64_t total = c->h_scalars->fizzle_total;
-    *n_out = total;
-    if (total > cap)
-        return fail(c, ZK_ENOSPC, "zk_fizzle_votes: %llu entries, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    ZK_TRY(scan_total(c, ent, n_rec, n_out));
+    const uint64_t total = *n_out;
+    if (total > cap) return no_room(c, "zk_fizzle_votes", "entries", total, cap);
     prof_begin(c, ZK_PROF_FIZZLE_EMIT, 16 * n_rec + 12 * total);
     hipLaunchKernelGGL(fizzle_single_kernel, dim3(grid_cap(c, div_up(n_rec, FZ_BLOCK), 16)), dim3(FZ_BLOCK), 0, c->stream, ent, one, hits, (u64)n_rec,
                        (u64)n_classes, single, hist, (u64)n_hist);
@@ -219,7 +214,6 @@ static int fizzle_votes(zk_ctx* c, const zk_bait_table* classes, int K, Mate m1,
                            (u64)cap);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 

@@ -104,23 +104,17 @@ static int capture_kmers(zk_ctx* c, const u64* pairs, uint64_t n, Mate m1, Mate 
     ZK_HIP(c, hipGetLastError());
     hipLaunchKernelGGL(capkmers_len_kernel, dim3(gp), dim3(256), 0, c->stream, pairs, (u64)n, wcount, len);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(scan64_inclusive(c, len, n));
-    ZK_TRY(fetch(c, &c->h_scalars->capkmers_total, len + n - 1));
-    ZK_TRY(stream_sync(c));
-    ZK_TRY(check_device_error(c));
-    const uint64_t total = c->h_scalars->capkmers_total;
-    *n_out = total;
+    ZK_TRY(scan_total(c, len, n, n_out));
+    const uint64_t total = *n_out;
     if (total >= (1ull << 32))
         return fail(c, ZK_ERANGE, "zk_capture_kmers: %llu entries in one call (at most 2^32 - 1); pass fewer pairs", (unsigned long long)total);
-    if (total > cap)
-        return fail(c, ZK_ENOSPC, "zk_capture_kmers: %llu entries, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    if (total > cap) return no_room(c, "zk_capture_kmers", "entries", total, cap);
     if (total == 0) return ZK_OK;
     prof_begin(c, ZK_PROF_CAPTURE_KMERS, 12 * total);
     hipLaunchKernelGGL(capkmers_emit_kernel, dim3(grid_cap(c, div_up(n, 4), 16)), dim3(256), 0, c->stream, pairs, (u64)n, m1, m2, K, len, baits, kmers,
                        (u64)cap);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 
@@ -300,21 +294,15 @@ static int path_scan(zk_ctx* c, const u32* baits, const u64* kmers, const u32* c
                        (u32*)nullptr, (u32*)nullptr, (u64)0);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(scan64_inclusive(c, cells, n_cells));
-    ZK_TRY(fetch(c, &c->h_scalars->path_total, cells + n_cells - 1));
-    ZK_TRY(stream_sync(c));               // (plan is read until here)
-    ZK_TRY(check_device_error(c));
-    const uint64_t total = c->h_scalars->path_total;
-    *n_out = total;
-    if (total > cap)
-        return fail(c, ZK_ENOSPC, "zk_path_scan: %llu matches, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    ZK_TRY(scan_total(c, cells, n_cells, n_out));               // (plan is read until here)
+    const uint64_t total = *n_out;
+    if (total > cap) return no_room(c, "zk_path_scan", "matches", total, cap);
     if (total == 0) return ZK_OK;
     prof_begin(c, ZK_PROF_PATH_SCAN, 16 * n + 8 * total);
     hipLaunchKernelGGL(path_scan_kernel<true>, dim3(tiles), dim3(PS_BLOCK), 0, c->stream, baits, kmers, counts, (u64)n, d_plan, (u32)W, cells, out_w,
                        out_e, (u64)cap);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 

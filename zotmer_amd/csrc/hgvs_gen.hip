@@ -170,12 +170,10 @@ static int hgvs_draw(zk_ctx* c, DrawArgs a, u64* rows, uint64_t cap_rows, u8* po
         hipLaunchKernelGGL(hgvs_draw_kernel, dim3(grid), dim3(256), 0, c->stream, a, i0, ws, need, d_bad);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_TRY(scan64_inclusive(c, need, n));
     prof_end(c);
     ZK_TRY(fetch(c, &c->h_scalars->hgvs_bad));
-    ZK_TRY(fetch(c, &c->h_scalars->hgvs_total, need + n - 1));
-    ZK_TRY(stream_sync(c));
-    ZK_TRY(check_device_error(c));
+    uint64_t total;
+    ZK_TRY(scan_total(c, need, n, &total));
     if (c->h_scalars->hgvs_bad == HG_BAD_ACGT)
         return fail(c, ZK_EINVAL, "zk_hgvs_draw: a substitution of [%llu, %llu) falls into a zone without a base of ACGT",
                     (unsigned long long)a.v0, (unsigned long long)(a.v0 + n));
@@ -183,7 +181,7 @@ static int hgvs_draw(zk_ctx* c, DrawArgs a, u64* rows, uint64_t cap_rows, u8* po
         return fail(c, ZK_EINVAL, "zk_hgvs_draw: a variant of [%llu, %llu) has no zone in the tables, or its zone is empty or leaves the text",
                     (unsigned long long)a.v0, (unsigned long long)(a.v0 + n));
     n_out[0] = n;
-    n_out[1] = c->h_scalars->hgvs_total;
+    n_out[1] = total;
     if (n_out[0] > cap_rows || n_out[1] > cap_pool)
         return fail(c, ZK_ENOSPC, "zk_hgvs_draw: %llu rows and %llu pool bytes, room for %llu and %llu", (unsigned long long)n_out[0],
                     (unsigned long long)n_out[1], (unsigned long long)cap_rows, (unsigned long long)cap_pool);
@@ -195,7 +193,6 @@ static int hgvs_draw(zk_ctx* c, DrawArgs a, u64* rows, uint64_t cap_rows, u8* po
         ZK_HIP(c, hipGetLastError());
     }
     prof_end(c);
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 
@@ -417,18 +414,15 @@ static int hgvs_render(zk_ctx* c, RenderArgs a, u8* out, uint64_t cap, uint64_t*
         hipLaunchKernelGGL(hgvs_size_kernel, dim3(grid), dim3(256), 0, c->stream, a, i0, len, d_bad);
         ZK_HIP(c, hipGetLastError());
     }
-    ZK_TRY(scan64_inclusive(c, len, n));
     prof_end(c);
     ZK_TRY(fetch(c, &c->h_scalars->hgvs_bad));
-    ZK_TRY(fetch(c, &c->h_scalars->hgvs_total, len + n - 1));
-    ZK_TRY(stream_sync(c));
-    ZK_TRY(check_device_error(c));
+    uint64_t total;
+    ZK_TRY(scan_total(c, len, n, &total));
     if (c->h_scalars->hgvs_bad)
         return fail(c, ZK_EINVAL, "zk_hgvs_render: a row of unknown kind, outside its zone (s <= p <= q <= e), with a pool range outside the pool, "
                                   "or a zone that leaves the text or whose prefix offsets are out of order");
-    *n_bytes = c->h_scalars->hgvs_total;
-    if (*n_bytes > cap)
-        return fail(c, ZK_ENOSPC, "zk_hgvs_render: %llu bytes of lines, room for %llu", (unsigned long long)*n_bytes, (unsigned long long)cap);
+    *n_bytes = total;
+    if (*n_bytes > cap) return no_room(c, "zk_hgvs_render", "bytes of lines", *n_bytes, cap);
     prof_begin(c, ZK_PROF_HGVS_RENDER, 8 * HG_ROW * n + 8 * n + *n_bytes);
     const u64 tiles = div_up(n, HR_TILE);
     for (u64 t = 0; t < tiles; t += HG_LAUNCH / HR_TILE) {
@@ -437,7 +431,6 @@ static int hgvs_render(zk_ctx* c, RenderArgs a, u8* out, uint64_t cap, uint64_t*
         ZK_HIP(c, hipGetLastError());
     }
     prof_end(c);
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 

@@ -11,7 +11,8 @@
 #include "common.hpp"
 
 // Small results (a total, a flag, a few sums) travel from the kernels to the host through one block of device words and its
-// pinned mirror.  One field per purpose: a new kernel adds a field here, it never borrows one.  Kernels only ever get raw
+// pinned mirror.  One field per purpose: a new kernel adds a field here, it never borrows one -- except a pure landing, a word
+// that no kernel writes and the host only copies the end of a scan into: those share scan_landing.  Kernels only ever get raw
 // pointers into the device block, so the layout is free to change -- except where a comment below says that fields are
 // adjacent: those are written through one pointer or copied as one range (ZK_SPAN), and the static_asserts after the struct
 // hold them in place.  A u32 counter keeps a whole u64 word (kernels take (u32*)&field, the host reads the low half).
@@ -29,6 +30,8 @@ struct zk_scalars {
     u64 dedupe_flags, dedupe_n_retry, dedupe_counter, dedupe_n_big, dedupe_n_bad;   // (u32 each) DedupeArgs
     u64 dedupe_m_cursor;     // DedupeArgs::m_cursor: mirror words placed (dedupe2_kernel, then strand_mirror_kernel over the declined blocks)
     // -- no order below this line --
+    u64 scan_landing[2];     // SHARED BY DESIGN: landing of scan_total's last sum (and of zk_spike_pairs' two), always fetched and read inside one
+                             // call, never read across calls; the device copy is not used
     u64 dedupe_n_in;         // landing: cuts[chunks]
     u64 dedupe_n_out;        // landing: incl[chunks - 1]
     zk_strand_counters strand;
@@ -50,42 +53,29 @@ struct zk_scalars {
     u64 tile_declined;       // (u32) tilesort.hip: a tile declined
     u64 strand_cursor;       // strand_keys: keys written
     u64 strand_sums[2];      // strand_pairs: orphans, palindromes
-    u64 strand_n_pairs;      // landing: strand_pairs' last tile total
-    u64 format_bytes;        // landing: format_pairs' last line end
-    u64 compact_total;       // landing: compact_count's last tile total
-    u64 project_heads;       // landing: project_sum's last tile total
     u64 project_total;       // project_sum: column_sum of the tiles' sums
     u64 spectrum[8];         // landing: spectrum_sums' partial sums (SP_WORDS)
     u64 table_verdict;       // (u32) allele_tally.hip: the first rule that the arrays of zk_bait_table_from_arrays break
     u64 vars[4];             // vars_scan.hip: sample groups, missing contexts, mixed reference groups, the smallest missing context
     u64 links_bad;           // debruijn.hip: links_check_kernel found a key out of order or of 4^K and above
     u64 render_bad;          // debruijn.hip: contig_len_kernel found an offset out of order or a node that is no index
-    u64 render_bytes;        // landing: the end of the last contig's text
     u64 pileup_cursor;       // pileup.hip: pairs emitted (or that would have been)
     u64 pileup_long;         // pileup.hip: long_line_kernel found a line longer than pad with a hit
     u64 pulldown_vetoed;     // pulldown.hip: reads with a window in the veto table
     u64 capkmers_bad;        // hgvs_find.hip: capkmers_mark_kernel found a pair whose read is no record of the batch
-    u64 capkmers_total;      // landing: the end of the last pair's entries
-    u64 path_total;          // landing: the end of the last (window, tile) cell's matches
     u64 place_bad;           // lcp_scan.hip: scan_check_kernel found an array that breaks zk_scan_place's rules
     u64 place_slots;         // landing: the last record offset = the slots of P and Q
     u64 seqtally[4];         // seq_tally.hip: windows met, the first header start (all ones: none), the state's value and its length (one pointer)
     u64 spike_bad;           // spikein.hip: a pair without a zone or a fragment outside its window; zones without length
-    u64 spike_total[2];      // landing: the ends of the last pair's records, mate 1 and mate 2
     u64 ksnp_lists[2];       // (u32 each) ksnp.hip: groups handed to the workgroup kernel, to the tile-pair kernel (one range)
-    u64 ksnp_tiles;          // landing: the tile pairs of all large groups
     u64 stop_long;           // stop_frames.hip: stop_long_kernel found a line longer than pad with a hit
-    u64 stop_total;          // landing: the end of the last read's stops
-    u64 fizzle_total;        // landing: the end of the last record's entries
     u64 hgvs_bad;            // hgvs_gen.hip: a variant without a zone (1), a sub in a zone without ACGT (2); a row that breaks zk_hgvs_render's rules
-    u64 hgvs_total;          // landing: the end of the last variant's pool bytes, of the last row's line
-    u64 dup_total;           // landing: the end of the last entry's rows (dup_join.hip)
     u64 merge_total;         // pileup_merge.hip: pm_scan_kernel's total = the length of the union
     u64 narrow_max;          // pileup_merge.hip: narrow_max_kernel's largest count
 };
 // bytes of the fields first .. last (declared in that order, adjacent)
 #define ZK_SPAN(first, last) (offsetof(zk_scalars, last) + sizeof(zk_scalars::last) - offsetof(zk_scalars, first))
-static_assert(sizeof(zk_scalars) == 96 * sizeof(u64), "zk_scalars: u64 words only, no padding");
+static_assert(sizeof(zk_scalars) == 84 * sizeof(u64), "zk_scalars: u64 words only, no padding");
 static_assert(ZK_SPAN(rle_side, total) == 2 * sizeof(u64), "rle_prefix reads rle_side and total back as one range");
 static_assert(ZK_SPAN(total, acgt) == 5 * sizeof(u64), "the merges read total and acgt back as one range");
 static_assert(ZK_SPAN(acgt, n_keys) == 5 * sizeof(u64) && ZK_SPAN(acgt, sample_n) == 9 * sizeof(u64),
@@ -181,6 +171,7 @@ struct zk_ctx {
 namespace zk {
 
 int fail(zk_ctx* c, int code, const char* fmt, ...);
+int no_room(zk_ctx* c, const char* entry, const char* noun, uint64_t needed, uint64_t cap);   // ZK_ENOSPC, "<entry>: <needed> <noun>, room for <cap>"
 // HIP's current device is per host thread and other code in the process (torch.cuda.set_device, another ctx) may have
 // changed it: every C-ABI entry makes the context's device current before it allocates or launches.
 static inline void enter(zk_ctx* c) {
@@ -372,6 +363,8 @@ int fastq_mask(zk_ctx* c, const u8* d_text, uint64_t n, uint32_t line_phase, u8*
 int codec_encode(zk_ctx* c, const u64* d_vals, uint64_t n, int delta, u64* d_words, uint64_t cap, uint64_t* n_words);
 int codec_encode_u32(zk_ctx* c, const u32* d_vals, uint64_t n, u64* d_words, uint64_t cap, uint64_t* n_words);
 int scan64_inclusive(zk_ctx* c, u64* d_v, uint64_t n);   // in place, asynchronous
+// v[0 .. n) -> its inclusive sums, in place; *total = the last one (0 when n == 0).  Synchronises the stream and reports a device error.
+int scan_total(zk_ctx* c, u64* v, uint64_t n, uint64_t* total);
 int add_u64(zk_ctx* c, u64* d_v, uint64_t n, u64 x);     // v[i] += x, asynchronous
 // ingest.hip
 void ring_destroy(zk_ctx* c);

@@ -71,9 +71,8 @@ template <class P>
 static int ksnp_emit(zk_ctx* c, const P& p, uint64_t n, uint64_t cap, uint64_t* n_out, const char* who) {
     u64* cnt;
     ZK_TRY(compact_count(c, p, n, &cnt, n_out));
-    if (*n_out > cap) return fail(c, ZK_ENOSPC, "%s: %llu k-mers, room for %llu", who, (unsigned long long)*n_out, (unsigned long long)cap);
+    if (*n_out > cap) return no_room(c, who, "k-mers", *n_out, cap);
     ZK_TRY(compact_write(c, p, n, cnt));
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 
@@ -352,10 +351,8 @@ static int ksnp_pairs(zk_ctx* c, const u64* k, uint64_t n, int m, u32 d, const u
     if (n_big) {
         hipLaunchKernelGGL(ksnp_tiles_kernel, dim3(grid_cap(c, div_up(n_big, 256), 16)), dim3(256), 0, c->stream, L.big_size, n_big, tiles);
         ZK_HIP(c, hipGetLastError());
-        ZK_TRY(scan64_inclusive(c, tiles, n_big));
-        ZK_TRY(fetch(c, &c->h_scalars->ksnp_tiles, tiles + n_big - 1));
-        ZK_TRY(stream_sync(c));
-        const u64 total = c->h_scalars->ksnp_tiles;
+        uint64_t total;
+        ZK_TRY(scan_total(c, tiles, n_big, &total));
         prof_begin(c, ZK_PROF_KSNP_PAIRS, 0);
         hipLaunchKernelGGL(ksnp_pair_kernel<LEV>, dim3(grid_cap(c, total, 32)), dim3(KS_PAIR_TILE), 0, c->stream, k, m, d, L.big_start,
                            L.big_size, tiles, n_big, total, parent);

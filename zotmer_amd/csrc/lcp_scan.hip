@@ -185,7 +185,6 @@ static int lcp_resolve(zk_ctx* c, const u64* S, uint64_t nS, const u64* X, uint6
     hipLaunchKernelGGL(lcp_fill_kernel, dim3(tiles), dim3(LCP_BLOCK), 0, c->stream, S, n, K, (const u8*)mark, (const u32*)prev, L, Y);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 
@@ -254,7 +253,6 @@ static int scan_place(zk_ctx* c, const PlaceArgs& a, u64* P, u8* Q, u32* cnt) {
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->place_bad));
     ZK_TRY(fetch(c, &c->h_scalars->place_slots, a.rec_off + a.n_rec));
-    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     if (c->h_scalars->place_bad)
         return fail(c, ZK_EINVAL, "zk_scan_place: T does not ascend from 0 to n_entries, the record offsets do not ascend from 0, an L is above K, "
@@ -276,7 +274,6 @@ static int scan_place(zk_ctx* c, const PlaceArgs& a, u64* P, u8* Q, u32* cnt) {
                        (u64)n_slots, P, Q);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 

@@ -188,7 +188,6 @@ static int anchor_pileup(zk_ctx* c, const zk_bait_table* anchors, const u8* text
     hipLaunchKernelGGL(long_line_kernel, dim3(grid), dim3(256), 0, c->stream, bt, text, lines, (u64)n_reads, K, (u64)pad, d_long);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->pileup_long));
-    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     if (c->h_scalars->pileup_long)
         return fail(c, ZK_ERANGE, "zk_anchor_pileup: a sequence line longer than pad = %u has a hit: its coordinates could name another zone", pad);
@@ -199,15 +198,13 @@ static int anchor_pileup(zk_ctx* c, const zk_bait_table* anchors, const u8* text
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->pileup_cursor));
-    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     const uint64_t total = c->h_scalars->pileup_cursor;
     *n_out = total;
     prof_add_bytes(c, ZK_PROF_PILEUP, 12 * (total < cap ? total : cap));
     if (total >= (1ull << 32))
         return fail(c, ZK_ERANGE, "zk_anchor_pileup: %llu pairs in one batch (at most 2^32 - 1); use smaller batches", (unsigned long long)total);
-    if (total > cap)
-        return fail(c, ZK_ENOSPC, "zk_anchor_pileup: %llu pairs, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    if (total > cap) return no_room(c, "zk_anchor_pileup", "pairs", total, cap);
     return ZK_OK;
 }
 
@@ -266,15 +263,13 @@ static int pileup_count(zk_ctx* c, const u32* coords, const u64* kmers, uint64_t
     uint64_t m = 0;
     ZK_TRY(compact_count(c, ph, n, &tiles, &m));
     *n_out = m;
-    if (m > cap)
-        return fail(c, ZK_ENOSPC, "zk_pileup_count: %llu distinct pairs, room for %llu", (unsigned long long)m, (unsigned long long)cap);
+    if (m > cap) return no_room(c, "zk_pileup_count", "distinct pairs", m, cap);
     ph.heads = rv == va ? vb : va;          // m <= n words, free since the first sort
     prof_begin(c, ZK_PROF_PILEUP_CUT, 16 * n + 20 * m);
     ZK_TRY(compact_write(c, ph, n, tiles));
     prof_end(c);
     hipLaunchKernelGGL(pileup_runs_kernel, dim3(grid_cap(c, div_up(m, 256), 16)), dim3(256), 0, c->stream, ph.heads, (u64)m, (u64)n, cnt);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 

@@ -174,11 +174,10 @@ static int pileup_merge(zk_ctx* c, const PmLists& l, const u64* an, const void* 
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->merge_total));
-    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     const uint64_t m = c->h_scalars->merge_total;
     *n_out = m;
-    if (m > cap) return fail(c, ZK_ENOSPC, "zk_pileup_merge: %llu pairs in the union, room for %llu", (unsigned long long)m, (unsigned long long)cap);
+    if (m > cap) return no_room(c, "zk_pileup_merge", "pairs in the union", m, cap);
     prof_add_bytes(c, ZK_PROF_PILEUP_MERGE, 20 * l.na + (b_bits == 64 ? 24 : 16) * l.nb + 20 * m);
     if (b_bits == 64)
         hipLaunchKernelGGL((pm_tile_kernel<2>), dim3(grid), dim3(PM_BLOCK), 0, c->stream, l, an, bn, (u64)tiles, part, counts, oc, ok, on);
@@ -186,7 +185,6 @@ static int pileup_merge(zk_ctx* c, const PmLists& l, const u64* an, const void* 
         hipLaunchKernelGGL((pm_tile_kernel<1>), dim3(grid), dim3(PM_BLOCK), 0, c->stream, l, an, bn, (u64)tiles, part, counts, oc, ok, on);
     prof_end(c);                                 // the record's end moves behind the emit pass
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 
@@ -232,7 +230,6 @@ static int narrow_counts(zk_ctx* c, const u64* in, u32* out, uint64_t n, uint64_
     hipLaunchKernelGGL(narrow_max_kernel, dim3(1), dim3(64), 0, c->stream, block_max, grid, &c->d_scalars->narrow_max);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->narrow_max));
-    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     *max_in = c->h_scalars->narrow_max;
     return ZK_OK;

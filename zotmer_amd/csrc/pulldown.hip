@@ -75,8 +75,7 @@ static int pulldown_hits(zk_ctx* c, const zk_bait_table* baits, const zk_bait_ta
         ZK_TRY(capture_lookup(c, baits, veto, RK, m1, m2, n_reads, pairs, cap, mark, &raw));
         if (raw > cap) {
             *n_pairs = raw;
-            return fail(c, ZK_ENOSPC, "pulldown: %llu (bait, read) pairs before deduplication, room for %llu", (unsigned long long)raw,
-                        (unsigned long long)cap);
+            return no_room(c, "pulldown", "(bait, read) pairs before deduplication", raw, cap);
         }
         room = side + capture_sort_bytes(raw);
         if (raw == 0 || room <= c->arena_size) break;
@@ -99,7 +98,6 @@ static int pulldown_hits(zk_ctx* c, const zk_bait_table* baits, const zk_bait_ta
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->pulldown_vetoed));
-    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     *n_pairs = n;
     *n_vetoed = c->h_scalars->pulldown_vetoed;

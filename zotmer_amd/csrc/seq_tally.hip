@@ -201,7 +201,6 @@ int zk_sequence_tally(zk_ctx* c, const zk_bait_table* table, const uint8_t* d_te
     hipLaunchKernelGGL(seq_state_kernel, dim3(1), dim3(64), 0, c->stream, (const u8*)d_text, (u64)n, K, sv, sr, d);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch_span(c, c->h_scalars->seqtally, sizeof(c->h_scalars->seqtally)));
-    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     const u64* h = c->h_scalars->seqtally;
     *n_windows = h[0];

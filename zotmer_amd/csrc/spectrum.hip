@@ -138,13 +138,9 @@ int project_sum(zk_ctx* c, const u64* keys, const void* cnts, int count_bits, ui
     hipLaunchKernelGGL(project_count_kernel, dim3((u32)tiles), dim3(PS_BLOCK), 0, c->stream, keys, (u64)n, shift, heads);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(scan64_inclusive(c, heads, tiles));
-    ZK_TRY(fetch(c, &c->h_scalars->project_heads, heads + tiles - 1));
-    ZK_TRY(stream_sync(c));
-    ZK_TRY(check_device_error(c));
-    const uint64_t m = c->h_scalars->project_heads;
-    *n_out = m;
-    if (m > cap) return fail(c, ZK_ENOSPC, "zk_project_sum: %llu distinct prefixes, room for %llu", (unsigned long long)m, (unsigned long long)cap);
+    ZK_TRY(scan_total(c, heads, tiles, n_out));
+    const uint64_t m = *n_out;
+    if (m > cap) return no_room(c, "zk_project_sum", "distinct prefixes", m, cap);
     ZK_HIP(c, hipMemsetAsync(out_s, 0, 8 * m, c->stream));
     prof_begin(c, ZK_PROF_PROJECT_SUM, (8 + count_bits / 8) * n + 16 * m);
     if (count_bits == 32)

@@ -259,15 +259,14 @@ static int spike_pairs(zk_ctx* c, SpikeArgs a, u8* out1, uint64_t cap1, u8* out2
     ZK_TRY(scan64_inclusive(c, len2, n));
     prof_end(c);
     ZK_TRY(fetch(c, &c->h_scalars->spike_bad));
-    ZK_TRY(fetch(c, &c->h_scalars->spike_total[0], len1 + n - 1));
-    ZK_TRY(fetch(c, &c->h_scalars->spike_total[1], len2 + n - 1));
-    ZK_TRY(stream_sync(c));
+    ZK_TRY(fetch(c, &c->h_scalars->scan_landing[0], len1 + n - 1));
+    ZK_TRY(fetch(c, &c->h_scalars->scan_landing[1], len2 + n - 1));
     ZK_TRY(check_device_error(c));
     if (c->h_scalars->spike_bad)
         return fail(c, ZK_EINVAL, "zk_spike_pairs: a pair of [%llu, %llu) has no zone in the tables, or its fragment leaves its window",
                     (unsigned long long)a.p0, (unsigned long long)(a.p0 + n));
-    n_bytes[0] = c->h_scalars->spike_total[0];
-    n_bytes[1] = c->h_scalars->spike_total[1];
+    n_bytes[0] = c->h_scalars->scan_landing[0];
+    n_bytes[1] = c->h_scalars->scan_landing[1];
     if (n_bytes[0] > cap1 || n_bytes[1] > cap2)
         return fail(c, ZK_ENOSPC, "zk_spike_pairs: %llu and %llu bytes of records, room for %llu and %llu", (unsigned long long)n_bytes[0],
                     (unsigned long long)n_bytes[1], (unsigned long long)cap1, (unsigned long long)cap2);
@@ -275,7 +274,6 @@ static int spike_pairs(zk_ctx* c, SpikeArgs a, u8* out1, uint64_t cap1, u8* out2
     hipLaunchKernelGGL(spike_write_kernel, dim3(grid), dim3(256), 0, c->stream, a, len1, len2, out1, (u64)cap1, out2, (u64)cap2);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 
@@ -295,7 +293,6 @@ int zk_spike_zone_counts(zk_ctx* c, const uint64_t* d_cum, uint64_t n_zones, uin
                        (u64)n_zones, sp_mix64(seed + SP_T_ZONE), (u64)first, (u64)count, (u64*)d_counts, d_bad);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->spike_bad));
-    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     if (c->h_scalars->spike_bad) return fail(c, ZK_EINVAL, "zk_spike_zone_counts: the zones have no length");
     return ZK_OK;

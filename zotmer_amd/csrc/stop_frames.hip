@@ -224,7 +224,6 @@ static int stop_frames(zk_ctx* c, const zk_bait_table* anchors, const u32* start
     hipLaunchKernelGGL(stop_long_kernel, dim3(grid), dim3(SF_BLOCK), 0, c->stream, bt, text, lines, (u64)n_reads, K, (u64)pad, d_long);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->stop_long));
-    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     if (c->h_scalars->stop_long)
         return fail(c, ZK_ERANGE, "zk_stop_frames: a sequence line longer than pad = %u has a hit: its frames could name another transcript", pad);
@@ -235,23 +234,17 @@ static int stop_frames(zk_ctx* c, const zk_bait_table* anchors, const u32* start
                        sf_mix64(seed + SF_T_STOP), (u64)first, sel, cnt);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(scan64_inclusive(c, cnt, n_reads));
-    ZK_TRY(fetch(c, &c->h_scalars->stop_total, cnt + n_reads - 1));
-    ZK_TRY(stream_sync(c));
-    ZK_TRY(check_device_error(c));
-    const uint64_t total = c->h_scalars->stop_total;
-    *n_out = total;
+    ZK_TRY(scan_total(c, cnt, n_reads, n_out));
+    const uint64_t total = *n_out;
     if (total >= (1ull << 32))
         return fail(c, ZK_ERANGE, "zk_stop_frames: %llu stops in one batch (at most 2^32 - 1); use smaller batches", (unsigned long long)total);
-    if (total > cap)
-        return fail(c, ZK_ENOSPC, "zk_stop_frames: %llu stops, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    if (total > cap) return no_room(c, "zk_stop_frames", "stops", total, cap);
     if (total == 0) return ZK_OK;
     prof_begin(c, ZK_PROF_STOP_EMIT, 16 * n_reads + 12 * total);
     hipLaunchKernelGGL(stop_emit_kernel, dim3(grid), dim3(SF_BLOCK), 0, c->stream, starts, (u32)n_tx, text, lines, (u64)n_reads, K, pad, sel, cnt, tx,
                        kmers, (u64)cap);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 
@@ -331,7 +324,6 @@ static int stop_nearest(zk_ctx* c, const u32* tx, const u64* kmers, uint64_t m, 
                        (u32)n_tx, known, (u64)n_known, dist, near, flags);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 

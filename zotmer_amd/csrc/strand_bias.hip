@@ -59,12 +59,10 @@ static int strand_keys(zk_ctx* c, const u8* text, const u64* lines, uint64_t n_r
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(fetch(c, &c->h_scalars->strand_cursor));
-    ZK_TRY(stream_sync(c));
     ZK_TRY(check_device_error(c));
     *n_keys = c->h_scalars->strand_cursor;
     prof_add_bytes(c, ZK_PROF_STRAND_KEYS, 8 * (*n_keys < cap ? *n_keys : cap));
-    if (*n_keys > cap)
-        return fail(c, ZK_ENOSPC, "zk_strand_keys: %llu keys, room for %llu", (unsigned long long)*n_keys, (unsigned long long)cap);
+    if (*n_keys > cap) return no_room(c, "zk_strand_keys", "keys", *n_keys, cap);
     return ZK_OK;
 }
 
@@ -137,16 +135,11 @@ static int strand_pairs(zk_ctx* c, const u64* keys, const void* cnts, int count_
     hipLaunchKernelGGL(strand_count_kernel, dim3((u32)tiles), dim3(CP_BLOCK), 0, c->stream, keys, (u64)n, K, (int)orphans, cnt, d_sums);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(scan64_inclusive(c, cnt, tiles));
     ZK_TRY(fetch(c, &c->h_scalars->strand_sums));
-    ZK_TRY(fetch(c, &c->h_scalars->strand_n_pairs, cnt + tiles - 1));
-    ZK_TRY(stream_sync(c));
-    ZK_TRY(check_device_error(c));
+    ZK_TRY(scan_total(c, cnt, tiles, &st->n_pairs));
     st->n_orphans = c->h_scalars->strand_sums[0];
     st->n_palindromes = c->h_scalars->strand_sums[1];
-    st->n_pairs = c->h_scalars->strand_n_pairs;
-    if (st->n_pairs > cap)
-        return fail(c, ZK_ENOSPC, "zk_strand_pairs: %llu lines, room for %llu", (unsigned long long)st->n_pairs, (unsigned long long)cap);
+    if (st->n_pairs > cap) return no_room(c, "zk_strand_pairs", "lines", st->n_pairs, cap);
     prof_begin(c, ZK_PROF_STRAND_PAIRS, (8 + count_bits / 8) * n + 16 * st->n_pairs);
     if (count_bits == 32) {
         StrandLines<u32> p{keys, (const u32*)cnts, (u64)n, K, seed, orphans, a, b};
@@ -156,7 +149,6 @@ static int strand_pairs(zk_ctx* c, const u64* keys, const void* cnts, int count_
         ZK_TRY(compact_write(c, p, n, cnt));
     }
     prof_end(c);
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 
@@ -192,18 +184,12 @@ static int format_pairs(zk_ctx* c, const u64* a, const u64* b, uint64_t n, u8* o
     hipLaunchKernelGGL(line_len_kernel, dim3(g), dim3(256), 0, c->stream, a, b, (u64)n, len);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_TRY(scan64_inclusive(c, len, n));
-    ZK_TRY(fetch(c, &c->h_scalars->format_bytes, len + n - 1));
-    ZK_TRY(stream_sync(c));
-    ZK_TRY(check_device_error(c));
-    *n_bytes = c->h_scalars->format_bytes;
-    if (*n_bytes > cap)
-        return fail(c, ZK_ENOSPC, "zk_format_pairs: %llu bytes of lines, room for %llu", (unsigned long long)*n_bytes, (unsigned long long)cap);
+    ZK_TRY(scan_total(c, len, n, n_bytes));
+    if (*n_bytes > cap) return no_room(c, "zk_format_pairs", "bytes of lines", *n_bytes, cap);
     prof_begin(c, ZK_PROF_FORMAT_PAIRS, 24 * n + *n_bytes);
     hipLaunchKernelGGL(line_write_kernel, dim3(g), dim3(256), 0, c->stream, a, b, (u64)n, len, out);
     prof_end(c);
     ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
     return check_device_error(c);
 }
 

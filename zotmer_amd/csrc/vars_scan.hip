@@ -255,10 +255,8 @@ static int vars_scan(zk_ctx* c, const VarsLists& L, double threshold, u64* d_ctx
     st->n_mixed = h[2];
     st->first_missing = h[1] ? h[3] : 0;
     st->n_rows = n_rows;
-    if (n_rows > cap_rows)
-        return fail(c, ZK_ENOSPC, "vars scan: %llu rows, room for %llu", (unsigned long long)n_rows, (unsigned long long)cap_rows);
+    if (n_rows > cap_rows) return no_room(c, "vars scan", "rows", n_rows, cap_rows);
     ZK_TRY(compact_write(c, vr, L.n_sam, cnt));
-    ZK_TRY(stream_sync(c));
     return check_device_error(c);
 }
 

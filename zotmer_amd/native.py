@@ -380,6 +380,21 @@ class Context:
         if rc != ZK_OK:
             raise ZotkError(rc, self.lib.zk_last_error(self.h).decode(errors="replace"))
 
+    def _sized(self, rc, n, unfit=(ZK_ENOSPC,)):
+        """the end of a sized entry -> (n, whether the result fit): a code of `unfit` is no error, n then says what is needed"""
+        if rc not in unfit:
+            self._check(rc)
+        return n, rc == ZK_OK
+
+    def _fit(self, into, bufs, grow):
+        """into(*bufs) -> (n, fit); when the result did not fit, once more into grow(n).  -> (n, bufs)"""
+        n, fit = into(*bufs)
+        if not fit:
+            bufs = grow(n)
+            n, fit = into(*bufs)
+            assert fit
+        return n, bufs
+
     # ---- memory ---------------------------------------------------------------------------
     def mem_info(self):
         f, t = C.c_uint64(0), C.c_uint64(0)
@@ -893,45 +908,31 @@ class Context:
     def line_ends(self, text, out=None):
         """positions of the '\\n' bytes of a device text -> u64 DeviceArray view (out: a buffer to reuse; grown when too small)"""
         n = C.c_uint64(0)
-        if out is None:
-            out = self.empty(text.n // 8 + 64, np.uint64)
-        rc = self.lib.zk_line_ends(self.h, text.ptr, text.n, out.ptr, out.n, C.byref(n))
-        if rc == ZK_ENOSPC:
-            out = self.empty(n.value + 64, np.uint64)
-            rc = self.lib.zk_line_ends(self.h, text.ptr, text.n, out.ptr, out.n, C.byref(n))
-        self._check(rc)
-        return out.view(n.value)
+        into = lambda o: self._sized(self.lib.zk_line_ends(self.h, text.ptr, text.n, o.ptr, o.n, C.byref(n)), n.value)
+        first = out if out is not None else self.empty(text.n // 8 + 64, np.uint64)
+        m, (out,) = self._fit(into, (first,), lambda m: (self.empty(m, np.uint64),))
+        return out.view(m)
 
     def capture_hits(self, table, read_K, text1, lines1, n_reads, text2=None, lines2=None, veto=None, out=None):
         """distinct (bait, read) pairs as bait << 32 | read, ascending -> u64 DeviceArray view (out: a buffer to reuse)"""
         assert 4 * n_reads <= lines1.n and (lines2 is None or 4 * n_reads <= lines2.n)
         n = C.c_uint64(0)
-        if out is None:
-            out = self.empty(2 * n_reads + 1024, np.uint64)
-        args = lambda o: (self.h, table.h, veto.h if veto is not None else None, int(read_K), text1.ptr, lines1.ptr,
-                          text2.ptr if text2 is not None else None, lines2.ptr if lines2 is not None else None, int(n_reads), o.ptr,
-                          o.n, C.byref(n))
-        rc = self.lib.zk_capture_hits(*args(out))
-        if rc == ZK_ENOSPC:
-            out = self.empty(n.value + 1024, np.uint64)
-            rc = self.lib.zk_capture_hits(*args(out))
-        self._check(rc)
-        return out.view(n.value)
+        into = lambda o: self._sized(self.lib.zk_capture_hits(
+            self.h, table.h, veto.h if veto is not None else None, int(read_K), text1.ptr, lines1.ptr, text2.ptr if text2 is not None else None,
+            lines2.ptr if lines2 is not None else None, int(n_reads), o.ptr, o.n, C.byref(n)), n.value)
+        first = out if out is not None else self.empty(2 * n_reads + 1024, np.uint64)
+        m, (out,) = self._fit(into, (first,), lambda m: (self.empty(m, np.uint64),))
+        return out.view(m)
 
     def capture_gather(self, pairs, n_baits, text, lines, out=None):
         """the captured records, bait by bait -> (uint8 DeviceArray view, pair offsets u64[n_baits + 1], byte offsets u64[n_baits + 1])"""
         spans = np.zeros(2 * (n_baits + 1), dtype=np.uint64)
         n = C.c_uint64(0)
-        if out is None:
-            out = self.empty(text.n + 1024, np.uint8)
-        args = lambda o: (self.h, pairs.ptr, pairs.n, int(n_baits), text.ptr, lines.ptr, lines.n, o.ptr, o.n,
-                          spans.ctypes.data_as(_pu64), C.byref(n))
-        rc = self.lib.zk_capture_gather(*args(out))
-        if rc == ZK_ENOSPC:
-            out = self.empty(n.value + 1024, np.uint8)
-            rc = self.lib.zk_capture_gather(*args(out))
-        self._check(rc)
-        return out.view(n.value), spans[:n_baits + 1], spans[n_baits + 1:]
+        into = lambda o: self._sized(self.lib.zk_capture_gather(self.h, pairs.ptr, pairs.n, int(n_baits), text.ptr, lines.ptr, lines.n, o.ptr, o.n,
+                                                                spans.ctypes.data_as(_pu64), C.byref(n)), n.value)
+        first = out if out is not None else self.empty(text.n + 1024, np.uint8)
+        m, (out,) = self._fit(into, (first,), lambda m: (self.empty(m, np.uint8),))
+        return out.view(m), spans[:n_baits + 1], spans[n_baits + 1:]
 
     # ---- read pairs per bait (csrc/pulldown.hip) --------------------------------------------------------------
     def pulldown_hits(self, table, read_K, text1, lines1, n_reads, text2=None, lines2=None, veto=None, out=None):
@@ -939,18 +940,13 @@ class Context:
         numpy u64[n_records + 1] with hist[n] = the reads that are not vetoed and hit n distinct baits, the vetoed reads)"""
         assert 4 * n_reads <= lines1.n and (lines2 is None or 4 * n_reads <= lines2.n)
         n, nv = C.c_uint64(0), C.c_uint64(0)
-        if out is None:
-            out = self.empty(2 * n_reads + 1024, np.uint64)
         hist = self.empty(table.n_records + 1, np.uint64)
-        args = lambda o: (self.h, table.h, veto.h if veto is not None else None, int(read_K), text1.ptr, lines1.ptr,
-                          text2.ptr if text2 is not None else None, lines2.ptr if lines2 is not None else None, int(n_reads), o.ptr,
-                          o.n, C.byref(n), hist.ptr, hist.n, C.byref(nv))
-        rc = self.lib.zk_pulldown_hits(*args(out))
-        if rc == ZK_ENOSPC:
-            out = self.empty(n.value + 1024, np.uint64)
-            rc = self.lib.zk_pulldown_hits(*args(out))
-        self._check(rc)
-        return out.view(n.value), hist.to_host(), nv.value
+        into = lambda o: self._sized(self.lib.zk_pulldown_hits(
+            self.h, table.h, veto.h if veto is not None else None, int(read_K), text1.ptr, lines1.ptr, text2.ptr if text2 is not None else None,
+            lines2.ptr if lines2 is not None else None, int(n_reads), o.ptr, o.n, C.byref(n), hist.ptr, hist.n, C.byref(nv)), n.value)
+        first = out if out is not None else self.empty(2 * n_reads + 1024, np.uint64)
+        m, (out,) = self._fit(into, (first,), lambda m: (self.empty(m, np.uint64),))
+        return out.view(m), hist.to_host(), nv.value
 
     # ---- strand bias (csrc/strand_bias.hip) ------------------------------------------------------------------
     def strand_keys(self, text, lines, n_reads, K, reverse, T, out, offset=0, seed=17):
@@ -960,9 +956,7 @@ class Context:
         n = C.c_uint64(0)
         rc = self.lib.zk_strand_keys(self.h, text.ptr, lines.ptr, int(n_reads), int(K), int(bool(reverse)), int(seed), int(T),
                                      out.ptr + 8 * offset, out.n - offset, C.byref(n))
-        if rc != ZK_ENOSPC:
-            self._check(rc)
-        return n.value, rc == ZK_OK
+        return self._sized(rc, n.value)
 
     def strand_pairs(self, keys, counts, K, orphans=False, seed=17):
         """ascending distinct tagged keys + counts (u32 | u64) -> (a u64 view, b u64 view, StrandStats): the lines of `zot strand`"""
@@ -977,14 +971,10 @@ class Context:
         """'%d\\t%d\\n' per pair -> uint8 DeviceArray view (out: a buffer to reuse; grown when too small)"""
         assert a.n == b.n
         n = C.c_uint64(0)
-        if out is None:
-            out = self.empty(8 * a.n + 1024, np.uint8)
-        rc = self.lib.zk_format_pairs(self.h, a.ptr, b.ptr, a.n, out.ptr, out.n, C.byref(n))
-        if rc == ZK_ENOSPC:
-            out = self.empty(n.value + 1024, np.uint8)
-            rc = self.lib.zk_format_pairs(self.h, a.ptr, b.ptr, a.n, out.ptr, out.n, C.byref(n))
-        self._check(rc)
-        return out.view(n.value)
+        into = lambda o: self._sized(self.lib.zk_format_pairs(self.h, a.ptr, b.ptr, a.n, o.ptr, o.n, C.byref(n)), n.value)
+        first = out if out is not None else self.empty(8 * a.n + 1024, np.uint8)
+        m, (out,) = self._fit(into, (first,), lambda m: (self.empty(m, np.uint8),))
+        return out.view(m)
 
     # ---- probe presence (csrc/probe_scan.hip) -----------------------------------------------------------------
     def probe_scan(self, kmers, K, windows):
@@ -1076,15 +1066,11 @@ class Context:
         assert nodes.dtype.itemsize == 4 and offs.dtype.itemsize == 8 and offs.n >= 1
         n_contigs = offs.n - 1
         n = C.c_uint64(0)
-        if out is None:
-            out = self.empty(nodes.n + n_contigs * (int(K) + 19), np.uint8)
-        args = lambda o: (self.h, kmers.ptr, kmers.n, int(K), nodes.ptr, nodes.n, offs.ptr, n_contigs, o.ptr, o.n, C.byref(n))
-        rc = self.lib.zk_contig_render(*args(out))
-        if rc == ZK_ENOSPC:
-            out = self.empty(n.value, np.uint8)
-            rc = self.lib.zk_contig_render(*args(out))
-        self._check(rc)
-        return out.view(n.value)
+        into = lambda o: self._sized(self.lib.zk_contig_render(self.h, kmers.ptr, kmers.n, int(K), nodes.ptr, nodes.n, offs.ptr, n_contigs, o.ptr, o.n,
+                                                               C.byref(n)), n.value)
+        first = out if out is not None else self.empty(nodes.n + n_contigs * (int(K) + 19), np.uint8)
+        m, (out,) = self._fit(into, (first,), lambda m: (self.empty(m, np.uint8),))
+        return out.view(m)
 
     # ---- reads piled up on reference zones (csrc/pileup.hip) ----------------------------------------------------
     def anchor_pileup(self, table, text, lines, n_reads, K, pad, out=None):
@@ -1095,13 +1081,10 @@ class Context:
         n = C.c_uint64(0)
         oc, ok = out if out is not None else (self.empty(text.n + 1024, np.uint32), self.empty(text.n + 1024, np.uint64))
         assert oc.dtype.itemsize == 4 and ok.dtype.itemsize == 8
-        args = lambda a, b: (self.h, table.h, text.ptr, lines.ptr, int(n_reads), int(K), int(pad), a.ptr, b.ptr, min(a.n, b.n), C.byref(n))
-        rc = self.lib.zk_anchor_pileup(*args(oc, ok))
-        if rc == ZK_ENOSPC:
-            oc, ok = self.empty(n.value, np.uint32), self.empty(n.value, np.uint64)
-            rc = self.lib.zk_anchor_pileup(*args(oc, ok))
-        self._check(rc)
-        return oc.view(n.value), ok.view(n.value)
+        into = lambda a, b: self._sized(self.lib.zk_anchor_pileup(self.h, table.h, text.ptr, lines.ptr, int(n_reads), int(K), int(pad), a.ptr, b.ptr,
+                                                                  min(a.n, b.n), C.byref(n)), n.value)
+        m, (oc, ok) = self._fit(into, (oc, ok), lambda m: (self.empty(m, np.uint32), self.empty(m, np.uint64)))
+        return oc.view(m), ok.view(m)
 
     def pileup_count(self, coords, kmers, K):
         """pairs of zk_anchor_pileup -> (coordinates u32, k-mers u64, counts u32) views: the distinct pairs, ascending by
@@ -1125,9 +1108,7 @@ class Context:
         n = C.c_uint64(0)
         rc = self.lib.zk_pileup_merge(self.h, a[0].ptr, a[1].ptr, a[2].ptr, a[0].n, b[0].ptr, b[1].ptr, b[2].ptr, 8 * b[2].dtype.itemsize, b[0].n,
                                       out[0].ptr, out[1].ptr, out[2].ptr, min(o.n for o in out), C.byref(n))
-        if rc != ZK_ENOSPC:
-            self._check(rc)
-        return n.value, rc == ZK_OK
+        return self._sized(rc, n.value)
 
     def pileup_merge(self, a, b, out=None):
         """the union of two counted lists as (coordinates u32, k-mers u64, counts u64) views, the counts of a pair that both
@@ -1135,11 +1116,8 @@ class Context:
         they are too small."""
         o = out if out is not None else (self.empty(a[0].n + b[0].n, np.uint32), self.empty(a[0].n + b[0].n, np.uint64),
                                          self.empty(a[0].n + b[0].n, np.uint64))
-        n, fit = self.pileup_merge_into(a, b, o)
-        if not fit:
-            o = (self.empty(n, np.uint32), self.empty(n, np.uint64), self.empty(n, np.uint64))
-            n, fit = self.pileup_merge_into(a, b, o)
-            assert fit
+        n, o = self._fit(lambda *o: self.pileup_merge_into(a, b, o), o,
+                         lambda n: (self.empty(n, np.uint32), self.empty(n, np.uint64), self.empty(n, np.uint64)))
         return tuple(x.view(n) for x in o)
 
     def narrow_counts(self, counts):
@@ -1161,22 +1139,19 @@ class Context:
         rc = self.lib.zk_capture_kmers(self.h, pairs.ptr, pairs.n, text1.ptr, lines1.ptr, text2.ptr if text2 is not None else None,
                                        lines2.ptr if lines2 is not None else None, int(n_reads), int(K), out_baits.ptr, out_kmers.ptr,
                                        min(out_baits.n, out_kmers.n), C.byref(n))
-        if rc not in (ZK_ENOSPC, ZK_ERANGE):
-            self._check(rc)
-        return n.value, rc == ZK_OK
+        return self._sized(rc, n.value, (ZK_ENOSPC, ZK_ERANGE))
 
     def capture_kmers(self, pairs, text1, lines1, n_reads, K, text2=None, lines2=None, out=None):
         """pairs of capture_hits (or a slice of them) -> (baits u32 view, k-mers u64 view): (bait, x) and (bait, rc x) for every
         window x of the pair's read in each text, in no order (zk_capture_kmers).  out: (baits, kmers) arrays to write into
         first; grown when too small."""
         ob, ok = out if out is not None else (self.empty(256 * pairs.n + 1024, np.uint32), self.empty(256 * pairs.n + 1024, np.uint64))
-        n, fit = self.capture_kmers_into(pairs, text1, lines1, n_reads, K, text2, lines2, ob, ok)
-        if not fit:
+        def grow(n):
             if n >= 1 << 32:
                 raise ZotkError(ZK_ERANGE, "zk_capture_kmers: %d entries in one call (at most 2^32 - 1); pass fewer pairs" % n)
-            ob, ok = self.empty(n, np.uint32), self.empty(n, np.uint64)
-            n, fit = self.capture_kmers_into(pairs, text1, lines1, n_reads, K, text2, lines2, ob, ok)
-            assert fit
+            return self.empty(n, np.uint32), self.empty(n, np.uint64)
+
+        n, (ob, ok) = self._fit(lambda *o: self.capture_kmers_into(pairs, text1, lines1, n_reads, K, text2, lines2, *o), (ob, ok), grow)
         return ob.view(n), ok.view(n)
 
     def path_scan(self, baits, kmers, counts, K, windows, out=None):
@@ -1188,13 +1163,10 @@ class Context:
         nw = len(windows)
         n = C.c_uint64(0)
         ow, oe = out if out is not None else (self.empty(4 * nw + 1024, np.uint32), self.empty(4 * nw + 1024, np.uint32))
-        args = lambda a, b: (self.h, baits.ptr, kmers.ptr, counts.ptr, baits.n, int(K), arr, nw, a.ptr, b.ptr, min(a.n, b.n), C.byref(n))
-        rc = self.lib.zk_path_scan(*args(ow, oe))
-        if rc == ZK_ENOSPC:
-            ow, oe = self.empty(n.value, np.uint32), self.empty(n.value, np.uint32)
-            rc = self.lib.zk_path_scan(*args(ow, oe))
-        self._check(rc)
-        return ow.to_host(n.value), oe.to_host(n.value)
+        into = lambda a, b: self._sized(self.lib.zk_path_scan(self.h, baits.ptr, kmers.ptr, counts.ptr, baits.n, int(K), arr, nw, a.ptr, b.ptr,
+                                                              min(a.n, b.n), C.byref(n)), n.value)
+        m, (ow, oe) = self._fit(into, (ow, oe), lambda m: (self.empty(m, np.uint32), self.empty(m, np.uint32)))
+        return ow.to_host(m), oe.to_host(m)
 
     # ---- gene alleles from a k-mer set (csrc/lcp_scan.hip) -------------------------------------------------------
     def lcp_resolve(self, S, X, K, out=None):
@@ -1243,20 +1215,15 @@ class Context:
         rc = self.lib.zk_spike_pairs(self.h, text.ptr, text.n, zones.ptr, first_pair.ptr, nz, heads.ptr, head_offs.ptr, heads.n,
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(L), int(I), int(sd_q), int(thr_v), int(thr_e), int(first), int(count),
                                      out1.ptr, out1.n, out2.ptr, out2.n, nb)
-        if rc != ZK_ENOSPC:
-            self._check(rc)
-        return (int(nb[0]), int(nb[1])), rc == ZK_OK
+        return self._sized(rc, (int(nb[0]), int(nb[1])))
 
     def spike_pairs(self, text, zones, first_pair, heads, head_offs, seed, L, I, sd_q, thr_v, thr_e, first, count, out=None):
         """-> (mate 1 text, mate 2 text) as uint8 DeviceArray views.  out: (out1, out2) buffers to write into first; grown when
         too small."""
         o1, o2 = out if out is not None else (self.empty(0, np.uint8), self.empty(0, np.uint8))
         args = (text, zones, first_pair, heads, head_offs, seed, L, I, sd_q, thr_v, thr_e, first, count)
-        nb, fit = self.spike_pairs_into(*args, o1, o2)
-        if not fit:
-            o1, o2 = self.empty(nb[0], np.uint8), self.empty(nb[1], np.uint8)
-            nb, fit = self.spike_pairs_into(*args, o1, o2)
-            assert fit
+        nb, (o1, o2) = self._fit(lambda *o: self.spike_pairs_into(*args, *o), (o1, o2),
+                                 lambda nb: (self.empty(nb[0], np.uint8), self.empty(nb[1], np.uint8)))
         return o1.view(nb[0]), o2.view(nb[1])
 
     # ---- candidate-SNP k-mers of a set (csrc/ksnp.hip) ---------------------------------------------------------------
@@ -1269,19 +1236,13 @@ class Context:
             rc = self.lib.zk_ksnp_flank(self.h, kmers.ptr, kmers.n, int(K), out.ptr, out.n, C.byref(n))
         else:
             rc = self.lib.zk_ksnp_components(self.h, kmers.ptr, kmers.n, int(K), int(metric), min(int(d), 1 << 62), out.ptr, out.n, C.byref(n))
-        if rc != ZK_ENOSPC:
-            self._check(rc)
-        return n.value, rc == ZK_OK
+        return self._sized(rc, n.value)
 
     def ksnp(self, kmers, K, metric=None, d=0, out=None):
         """ascending k-mers of a set -> the candidate-SNP k-mers among them, ascending, as a uint64 DeviceArray view.  out: an
         array to write into first; one retry with the length the entry reports when it is too small."""
         o = out if out is not None else self.empty(max(kmers.n // 8, 1024), np.uint64)
-        n, fit = self.ksnp_into(kmers, K, o, metric, d)
-        if not fit:
-            o = self.empty(n, np.uint64)
-            n, fit = self.ksnp_into(kmers, K, o, metric, d)
-            assert fit
+        n, (o,) = self._fit(lambda o: self.ksnp_into(kmers, K, o, metric, d), (o,), lambda n: (self.empty(n, np.uint64),))
         return o.view(n)
 
     # ---- in-frame stop codons of reads placed on transcripts (csrc/stop_frames.hip) ----------------------------------
@@ -1292,9 +1253,7 @@ class Context:
         n = C.c_uint64(0)
         rc = self.lib.zk_stop_frames(self.h, table.h, starts.ptr, starts.n, text.ptr, lines.ptr, int(n_reads), int(K), int(pad),
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), out_tx.ptr, out_kmers.ptr, min(out_tx.n, out_kmers.n), C.byref(n))
-        if rc != ZK_ENOSPC:
-            self._check(rc)
-        return n.value, rc == ZK_OK
+        return self._sized(rc, n.value)
 
     def stop_frames(self, table, starts, text, lines, n_reads, K, pad, seed, first, out=None):
         """a batch of single FASTQ reads, the first of which is read `first` of the run, against a table whose ids are anchors
@@ -1302,11 +1261,8 @@ class Context:
         view): the in-frame stops of the frame drawn for every read, in no order (zk_stop_frames).  out: (tx, kmers) arrays
         to write into first; one retry with the length the entry reports when they are too small."""
         ot, ok = out if out is not None else (self.empty(max(n_reads, 1024), np.uint32), self.empty(max(n_reads, 1024), np.uint64))
-        n, fit = self.stop_frames_into(table, starts, text, lines, n_reads, K, pad, seed, first, ot, ok)
-        if not fit:
-            ot, ok = self.empty(n, np.uint32), self.empty(n, np.uint64)
-            n, fit = self.stop_frames_into(table, starts, text, lines, n_reads, K, pad, seed, first, ot, ok)
-            assert fit
+        n, (ot, ok) = self._fit(lambda *o: self.stop_frames_into(table, starts, text, lines, n_reads, K, pad, seed, first, *o), (ot, ok),
+                                lambda n: (self.empty(n, np.uint32), self.empty(n, np.uint64)))
         return ot.view(n), ok.view(n)
 
     def stop_nearest(self, tx, kmers, K, tk, tk_offs, known):
@@ -1331,9 +1287,7 @@ class Context:
         rc = self.lib.zk_fizzle_votes(self.h, table.h, int(K), text1.ptr, lines1.ptr, text2.ptr, lines2.ptr, int(n_reads), table.n_records,
                                       single.ptr, hist.ptr, hist.n, out_rec.ptr, out_cls.ptr, out_cnt.ptr,
                                       min(out_rec.n, out_cls.n, out_cnt.n), C.byref(n))
-        if rc != ZK_ENOSPC:
-            self._check(rc)
-        return n.value, rc == ZK_OK
+        return self._sized(rc, n.value)
 
     def fizzle_votes(self, table, K, text1, lines1, text2, lines2, n_reads, single, hist, out=None):
         """a batch of FASTQ read pairs against a table whose every key lists its class: the records with one class are added to
@@ -1341,11 +1295,8 @@ class Context:
         = orientation o of pair p (zk_fizzle_votes).  out: (rec, cls, cnt) arrays to write into first; one retry with the length
         the entry reports when they are too small."""
         o = out if out is not None else tuple(self.empty(4 * n_reads + 1024, np.uint32) for _ in range(3))
-        n, fit = self.fizzle_votes_into(table, K, text1, lines1, text2, lines2, n_reads, single, hist, *o)
-        if not fit:
-            o = tuple(self.empty(n, np.uint32) for _ in range(3))
-            n, fit = self.fizzle_votes_into(table, K, text1, lines1, text2, lines2, n_reads, single, hist, *o)
-            assert fit
+        n, o = self._fit(lambda *o: self.fizzle_votes_into(table, K, text1, lines1, text2, lines2, n_reads, single, hist, *o), o,
+                         lambda n: tuple(self.empty(n, np.uint32) for _ in range(3)))
         return tuple(a.view(n) for a in o)
 
     # ---- candidate tandem duplications of `zot vardyger` (csrc/dup_join.hip) ---------------------------------------
@@ -1359,9 +1310,7 @@ class Context:
         n = C.c_uint64(0)
         rc = self.lib.zk_dup_join(self.h, baits.ptr, kmers.ptr, counts.ptr, baits.n, rseq.ptr, rkmer.ptr, rpos.ptr, by_second.ptr, rseq.n,
                                   int(K), int(min_count), cover.ptr, out_e.ptr, out_i.ptr, out_j.ptr, min(out_e.n, out_i.n, out_j.n), C.byref(n))
-        if rc != ZK_ENOSPC:
-            self._check(rc)
-        return n.value, rc == ZK_OK
+        return self._sized(rc, n.value)
 
     def dup_join(self, baits, kmers, counts, rseq, rkmer, rpos, by_second, K, min_count, out=None):
         """a counted (bait, k-mer) list as pileup_count gives it + the occurrence table of the baits' sequences (u32 sequence,
@@ -1371,11 +1320,8 @@ class Context:
         write the rows into first; one retry with the length the entry reports when they are too small."""
         cover = self.empty(rseq.n, np.uint32)
         o = out if out is not None else tuple(self.empty(1024, np.uint32) for _ in range(3))
-        n, fit = self.dup_join_into(baits, kmers, counts, rseq, rkmer, rpos, by_second, K, min_count, cover, *o)
-        if not fit:
-            o = tuple(self.empty(n, np.uint32) for _ in range(3))
-            n, fit = self.dup_join_into(baits, kmers, counts, rseq, rkmer, rpos, by_second, K, min_count, cover, *o)
-            assert fit
+        n, o = self._fit(lambda *o: self.dup_join_into(baits, kmers, counts, rseq, rkmer, rpos, by_second, K, min_count, cover, *o), o,
+                         lambda n: tuple(self.empty(n, np.uint32) for _ in range(3)))
         return (cover.to_host(),) + tuple(a.to_host(n) for a in o)
 
     # ---- random variants of `zot hgvs-gen` (csrc/hgvs_gen.hip) -----------------------------------------------------
@@ -1394,21 +1340,16 @@ class Context:
         n = (C.c_uint64 * 2)(0, 0)
         rc = self.lib.zk_hgvs_draw(self.h, text.ptr, text.n, zones.ptr, first_var.ptr, nz, thr, geom.ptr, gn, int(mix_thr),
                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(count), rows.ptr, rows.n // self.HGVS_ROW_WORDS, pool.ptr, pool.n, n)
-        if rc != ZK_ENOSPC:
-            self._check(rc)
-        return (int(n[0]), int(n[1])), rc == ZK_OK
+        return self._sized(rc, (int(n[0]), int(n[1])))
 
     def hgvs_draw(self, text, zones, first_var, type_thr, geom, geom_n, mix_thr, seed, first, count, out=None):
         """-> (rows u64 view of 6 * count words, pool u8 view).  out: (rows, pool) buffers to write into first; grown when too
         small."""
         rows, pool = out if out is not None else (self.empty(self.HGVS_ROW_WORDS * count, np.uint64), self.empty(2 * count + 64, np.uint8))
         args = (text, zones, first_var, type_thr, geom, geom_n, mix_thr, seed, first, count)
-        n, fit = self.hgvs_draw_into(*args, rows, pool)
-        if not fit:
-            rows = rows if rows.n >= self.HGVS_ROW_WORDS * n[0] else self.empty(self.HGVS_ROW_WORDS * n[0], np.uint64)
-            pool = pool if pool.n >= n[1] else self.empty(n[1], np.uint8)
-            n, fit = self.hgvs_draw_into(*args, rows, pool)
-            assert fit
+        grow = lambda n: (rows if rows.n >= self.HGVS_ROW_WORDS * n[0] else self.empty(self.HGVS_ROW_WORDS * n[0], np.uint64),
+                          pool if pool.n >= n[1] else self.empty(n[1], np.uint8))
+        n, (rows, pool) = self._fit(lambda *o: self.hgvs_draw_into(*args, *o), (rows, pool), grow)
         return rows.view(self.HGVS_ROW_WORDS * n[0]), pool.view(n[1])
 
     def hgvs_render_into(self, rows, pool, text, zones, accs, acc_offs, names, name_offs, first_var, first, flags, out):
@@ -1424,19 +1365,13 @@ class Context:
                                      acc_offs.ptr, accs.n, names.ptr if names is not None else None, name_offs.ptr if name_offs is not None else None,
                                      names.n if names is not None else 0, first_var.ptr if first_var is not None else None, int(first), int(flags),
                                      out.ptr, out.n, C.byref(nb))
-        if rc != ZK_ENOSPC:
-            self._check(rc)
-        return nb.value, rc == ZK_OK
+        return self._sized(rc, nb.value)
 
     def hgvs_render(self, rows, pool, text, zones, accs, acc_offs, names=None, name_offs=None, first_var=None, first=0, flags=0, out=None):
         """-> the lines as a uint8 DeviceArray view.  out: a buffer to write into first; grown when too small."""
         o = out if out is not None else self.empty(48 * (rows.n // self.HGVS_ROW_WORDS) + 64, np.uint8)
         args = (rows, pool, text, zones, accs, acc_offs, names, name_offs, first_var, first, flags)
-        nb, fit = self.hgvs_render_into(*args, o)
-        if not fit:
-            o = self.empty(nb, np.uint8)
-            nb, fit = self.hgvs_render_into(*args, o)
-            assert fit
+        nb, (o,) = self._fit(lambda o: self.hgvs_render_into(*args, o), (o,), lambda nb: (self.empty(nb, np.uint8),))
         return o.view(nb)
 
     def capture_filter(self, stream, K, baits):
