@@ -1051,6 +1051,19 @@ typedef struct {
 int zk_spectrum_sums(zk_ctx* ctx, const uint64_t* d_xk, const uint64_t* d_xs, uint64_t nx, const uint64_t* d_yk, const uint64_t* d_ys,
                      uint64_t ny, double cx, double cy, zk_spectrum* out);
 
+/* One row of a distance matrix: the spectrum x against m others in three launches, one read-back and one synchronise, whatever
+ * m is.  d_yk, d_ys, ny and cy are HOST arrays of m entries (d_yk[j], d_ys[j]: device pointers, as zk_merge_n takes its
+ * lists); out is a HOST array of m entries, and out[j] is what zk_spectrum_sums(x, y_j, cx, cy[j]) defines.  The six integers
+ * are exact and equal that entry's.  The two doubles have the same terms, each computed operation by operation in the same
+ * way, added in an order that is a function of (nx, ny[j]) alone: the same pair returns the same bits wherever it stands in
+ * a row, whatever else the row holds and whatever the device's number of compute units -- but not necessarily the bits of
+ * zk_spectrum_sums, whose order depends on its grid.  An empty x or an empty y_j gives a zero struct (its pointers are not
+ * read); m = 0 does nothing.  m > ZK_SPECTRUM_ROW_MAX is ZK_EINVAL: callers cut longer rows. */
+#define ZK_SPECTRUM_ROW_MAX 4096
+int zk_spectrum_sums_row(zk_ctx* ctx, const uint64_t* d_xk, const uint64_t* d_xs, uint64_t nx, double cx, uint32_t m,
+                         const uint64_t* const* d_yk, const uint64_t* const* d_ys, const uint64_t* ny, const double* cy,
+                         zk_spectrum* out /* HOST, m entries */);
+
 /* positions[q] = how many elements of the sorted device array are < queries[q] (HOST arrays of m
  * entries): the cut points of a value-range partition for the multi-GPU exchange. */
 int zk_lower_bound(zk_ctx* ctx, const uint64_t* d_sorted, uint64_t n, const uint64_t* queries, uint32_t m, uint64_t* positions);

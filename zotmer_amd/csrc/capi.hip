@@ -280,6 +280,15 @@ int zk_spectrum_sums(zk_ctx* c, const uint64_t* d_xk, const uint64_t* d_xs, uint
     return spectrum_sums(c, (const u64*)d_xk, (const u64*)d_xs, nx, (const u64*)d_yk, (const u64*)d_ys, ny, cx, cy, out);
 }
 
+int zk_spectrum_sums_row(zk_ctx* c, const uint64_t* d_xk, const uint64_t* d_xs, uint64_t nx, double cx, uint32_t m,
+                         const uint64_t* const* d_yk, const uint64_t* const* d_ys, const uint64_t* ny, const double* cy, zk_spectrum* out) {
+    ZK_ARGS(c, m <= ZK_SPECTRUM_ROW_MAX && (m == 0 || (d_yk && d_ys && ny && cy && out)) && (nx == 0 || (d_xk && d_xs)));
+    for (uint32_t j = 0; j < m; j++)
+        if (ny[j] && !(d_yk[j] && d_ys[j])) return fail(c, ZK_EINVAL, "zk_spectrum_sums_row: list %u has a length and no arrays", j);
+    arena_reset(c);
+    return spectrum_sums_row(c, (const u64*)d_xk, (const u64*)d_xs, nx, cx, m, (const u64* const*)d_yk, (const u64* const*)d_ys, ny, cy, out);
+}
+
 int zk_trim(zk_ctx* c, const uint64_t* d_kmers, const void* d_counts, int count_bits, uint64_t n, uint64_t lo, uint64_t hi,
             uint64_t* d_ok, void* d_oc, uint64_t cap, uint64_t* n_out) {
     ZK_ARGS(c, n_out && (count_bits == 32 || count_bits == 64));

@@ -254,6 +254,7 @@ void zk_destroy(zk_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) (void)zk_comm_destroy(c);
     ring_destroy(c);
+    if (c->row_stage) (void)hipHostFree(c->row_stage);
     for (auto& r : c->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     if (c->arena) (void)hipFree(c->arena);
     if (c->aux) (void)hipFree(c->aux);

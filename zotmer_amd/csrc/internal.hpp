@@ -161,6 +161,7 @@ struct zk_ctx {
                                         // all-reduces through ncclAllReduce (the RCCL calls of comm.hip on a box with one GPU)
 
     void* ring = nullptr;               // page-locked staging ring + copy stream of the file <-> device paths (ingest.hip)
+    void* row_stage = nullptr;          // page-locked block of zk_spectrum_sums_row: descriptors up, results down (spectrum.hip; made on first use)
 
     // optional per-launch timing with HIP events on this stream (zk_profile_*)
     struct ProfRec { int tag; uint64_t bytes; hipEvent_t a, b; };
@@ -396,6 +397,8 @@ int make_partition(zk_ctx* c, const u64* A, u64 nA, const u64* B, u64 nB, u64** 
 int project_sum(zk_ctx* c, const u64* keys, const void* cnts, int count_bits, uint64_t n, int shift, u64* out_k, u64* out_s, uint64_t cap,
                 uint64_t* n_out, uint64_t* total);
 int spectrum_sums(zk_ctx* c, const u64* A, const u64* sA, u64 nA, const u64* B, const u64* sB, u64 nB, double cx, double cy, zk_spectrum* out);
+int spectrum_sums_row(zk_ctx* c, const u64* A, const u64* sA, u64 nA, double cx, u32 m, const u64* const* yk, const u64* const* ys,
+                      const uint64_t* ny, const double* cy, zk_spectrum* out);
 // lcp_scan.hip: zk_lcp_resolve and zk_scan_place; nothing of it is called from another unit
 // pileup_merge.hip: zk_pileup_merge and zk_narrow_counts; nothing of it is called from another unit
 }  // namespace zk

@@ -177,3 +177,109 @@ def device_read_kmers_shard(ctx, z, rank, world, comm):
         ctx.add_u64(vals, base)
         ctx.sync()
     return vals
+
+
+def count_shard_moves(klens, clens, rank):
+    """The one all-to-all-v that brings every count to the rank that holds its k-mer.  klens[r] / clens[r] = the k-mers / counts
+    rank r decoded from its words of the two members: rank r holds the k-mers [e0, e1) and the counts [f0, f1) of the set (the
+    prefix sums of the two lists), and the two intervals need not coincide.  Both interval lists ascend with the rank, so what
+    goes from one rank to another is one contiguous slice: an intersection.
+    -> (send, send_off, recv, recv_off): counts and offsets per peer, send_off into this rank's counts, recv_off into its piece"""
+    def edges(lens):
+        e = [0]
+        for n in lens:
+            e.append(e[-1] + n)
+        return e
+
+    def cut(lo, hi, peers):
+        cnt, off = [], []
+        for q in range(len(peers) - 1):
+            a, b = max(lo, peers[q]), min(hi, peers[q + 1])
+            cnt.append(max(b - a, 0))
+            off.append(min(max(a, lo), hi) - lo)
+        return cnt, off
+
+    e, f = edges(klens), edges(clens)
+    send, send_off = cut(f[rank], f[rank + 1], e)
+    recv, recv_off = cut(e[rank], e[rank + 1], f)
+    return send, send_off, recv, recv_off
+
+
+class DeviceShardIO:
+    """What device_read_kmers_and_counts_shard does to values, on the device (tests restate it with numpy on CPU tensors)"""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def decode(self, words):
+        """codec64 words (numpy) -> (int64 tensor of the raw values, their number)"""
+        import torch
+        if len(words) == 0:
+            return torch.empty(1, dtype=torch.int64, device="cuda"), 0
+        vals = _check_codec(self.ctx.codec_decode, self.ctx.upload(words), False)
+        t = torch.empty(max(vals.n, 1), dtype=torch.int64, device="cuda")
+        if vals.n:
+            self.ctx._check(self.ctx.lib.zk_copy(self.ctx.h, t.data_ptr(), vals.ptr, vals.nbytes))
+            self.ctx.sync()
+        return t, vals.n
+
+    def _arr(self, t, n, off=0):
+        return native.DeviceArray.borrow(self.ctx, t.data_ptr() + 8 * off, np.uint64, n, keep=t)
+
+    def undelta(self, t, n):
+        """in-place prefix sum -> the last value (0 when n = 0)"""
+        if n == 0:
+            return 0
+        self.ctx.undelta(self._arr(t, n), 0)
+        return int(self._arr(t, 1, n - 1).to_host()[0])
+
+    def add(self, t, n, base):
+        if base and n:
+            self.ctx.add_u64(self._arr(t, n), base)
+            self.ctx.sync()
+
+    def empty(self, n):
+        import torch
+        return torch.empty(max(int(n), 1), dtype=torch.int64, device="cuda")
+
+    def before_comm(self):
+        self.ctx.sync()
+
+    def after_comm(self):
+        import torch
+        torch.cuda.synchronize()
+
+
+def device_read_kmers_and_counts_shard(ctx, z, rank, world, comm, io=None):
+    """This rank's contiguous piece of a counted set, k-mers and counts (both int64 tensors carrying unsigned words, and their
+    number), for the spectrum measures of the multi-GPU `zot dist`.  The k-mers as device_read_kmers_shard reads them: they give
+    this rank the elements [e0, e1).  The 'counts' member is cut by words in the same way; its words decode independently and
+    carry no delta, which gives the elements [f0, f1) -- not [e0, e1) in general, a word holds a varying number of values -- so
+    one all-to-all-v of contiguous slices moves each count to the rank that holds its k-mer (count_shard_moves).  The piece
+    lengths travel in the all-reduce of the delta sums.  A set whose two members decode to different numbers of values is
+    damaged: every rank raises CodecError."""
+    io = io if io is not None else DeviceShardIO(ctx)
+
+    def words_of(member):
+        nw = z.member_size(member) // 8
+        w0, w1 = nw * rank // world, nw * (rank + 1) // world
+        return np.frombuffer(z.read_range(member, 8 * w0, 8 * (w1 - w0)), dtype="<u8") if w1 > w0 else np.zeros(0, dtype="<u8")
+
+    k, nk = io.decode(words_of("kmers"))
+    last = io.undelta(k, nk)
+    c, nc = io.decode(words_of("counts")) if "counts" in z.toc and z.member_size("counts") else io.decode(np.zeros(0, dtype="<u8"))
+    v = [0] * (3 * world)
+    v[rank], v[world + rank], v[2 * world + rank] = last, nk, nc
+    v = comm.all_reduce(v)
+    sums, klens, clens = v[:world], v[world:2 * world], v[2 * world:]
+    if sum(klens) != sum(clens):
+        raise CodecError("k-mer and count vectors differ in length (%d vs %d)" % (sum(klens), sum(clens)))
+    io.add(k, nk, sum(sums[:rank]) & 0xFFFFFFFFFFFFFFFF)
+    send, send_off, recv, recv_off = count_shard_moves(klens, clens, rank)
+    if world == 1:
+        return k, c, nk
+    out = io.empty(nk)
+    io.before_comm()
+    comm.all_to_all_v(out, c, recv, send, send_off + [nc], recv_off + [nk])
+    io.after_comm()
+    return k, out, nk

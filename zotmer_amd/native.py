@@ -135,6 +135,7 @@ SIGNATURES = {
     "zk_split": (_i, [_vp, _vp, _u64, _vp, _u64, _pu64]),
     "zk_project_sum": (_i, [_vp, _vp, _vp, _i, _u64, _i, _vp, _vp, _u64, _pu64, _pu64]),
     "zk_spectrum_sums": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _d, _d, C.POINTER(Spectrum)]),
+    "zk_spectrum_sums_row": (_i, [_vp, _vp, _vp, _u64, _d, _u32, C.POINTER(_vp), C.POINTER(_vp), _pu64, C.POINTER(_d), C.POINTER(Spectrum)]),
     "zk_lower_bound": (_i, [_vp, _vp, _u64, _pu64, _u32, _pu64]),
     "zk_trim": (_i, [_vp, _vp, _vp, _i, _u64, _u64, _u64, _vp, _vp, _u64, _pu64]),
     "zk_codec64_encode": (_i, [_vp, _u64, _i, _vp, _u64, _pu64]),
@@ -684,6 +685,32 @@ class Context:
         self._check(self.lib.zk_spectrum_sums(self.h, xk.ptr, xs.ptr, xk.n, yk.ptr, ys.ptr, yk.n, float(cx), float(cy), C.byref(r)))
         return dict(cx=int(cx), cy=int(cy), n_shared=int(r.n_shared), S_min=int(r.s_min), X_shared=int(r.x_shared),
                     Y_shared=int(r.y_shared), S_xy=int(r.s_xy_lo) | (int(r.s_xy_hi) << 64), S_sqrt=float(r.s_sqrt), S_js=float(r.s_js))
+
+    SPECTRUM_ROW_MAX = 4096             # ZK_SPECTRUM_ROW_MAX: the pairs of one zk_spectrum_sums_row call; longer rows are cut here
+
+    def spectrum_sums_row(self, x, ys):
+        """x = (keys, u64 sums, total) against every (keys, u64 sums, total) of ys in one device call per SPECTRUM_ROW_MAX pairs
+        (zk_spectrum_sums_row) -> the list of dicts spectrum_sums returns pair by pair.  The integers are that entry's; the two
+        doubles have its terms in an order of their own (the same pair gives the same bits in whatever row it stands)."""
+        xk, xs, cx = x
+        assert xs.n == xk.n and xs.dtype.itemsize == 8
+        out = []
+        for lo in range(0, len(ys), self.SPECTRUM_ROW_MAX):
+            part = ys[lo:lo + self.SPECTRUM_ROW_MAX]
+            m = len(part)
+            assert all(s.n == k.n and s.dtype.itemsize == 8 for k, s, _ in part)
+            pk = (_vp * m)(*[k.ptr if k.n else None for k, _, _ in part])
+            ps = (_vp * m)(*[s.ptr if s.n else None for _, s, _ in part])
+            ns = (C.c_uint64 * m)(*[k.n for k, _, _ in part])
+            cys = (C.c_double * m)(*[float(cy) for _, _, cy in part])
+            res = (Spectrum * m)()
+            self._check(self.lib.zk_spectrum_sums_row(self.h, xk.ptr if xk.n else None, xs.ptr if xs.n else None, xk.n, float(cx), m,
+                                                      pk, ps, ns, cys, res))
+            for r, (_, _, cy) in zip(res, part):
+                out.append(dict(cx=int(cx), cy=int(cy), n_shared=int(r.n_shared), S_min=int(r.s_min), X_shared=int(r.x_shared),
+                                Y_shared=int(r.y_shared), S_xy=int(r.s_xy_lo) | (int(r.s_xy_hi) << 64), S_sqrt=float(r.s_sqrt),
+                                S_js=float(r.s_js)))
+        return out
 
     def codec_encode(self, values, delta):
         """uint64 (or, delta=False, uint32) device values -> device codec64 words (delta=True: ascending k-mers, stored as

@@ -305,6 +305,33 @@ class GpuOps:
     def hist(self, c):
         return self.ctx.hist(c)
 
+    # ---- the spectrum measures of `zot dist` (SpectrumDist) -------------------------------------------
+    def project_sum(self, k, c, n, shift):
+        """Measure.prep in vector mode (commands/dist.py:35-41) on the first n entries of k / c (tensors or library arrays)
+        -> (prefixes tensor, u64 sums tensor, their number, the sum of all counts): zk_project_sum"""
+        import ctypes as C
+        out_k, out_s = self.empty(n, torch.int64), self.empty(n, torch.int64)
+        ptr = lambda a: a.data_ptr() if hasattr(a, "data_ptr") else a.ptr                               # noqa: E731
+        bits = 8 * (c.element_size() if hasattr(c, "element_size") else c.dtype.itemsize)
+        m, total = C.c_uint64(0), C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.zk_project_sum(self.ctx.h, ptr(k) if n else None, ptr(c) if n else None, bits, int(n), int(shift),
+                                                    out_k.data_ptr(), out_s.data_ptr(), int(n), C.byref(m), C.byref(total)))
+        return out_k, out_s, m.value, total.value
+
+    def peek(self, t, i):
+        """element i of a tensor of 64-bit words, as an unsigned Python int"""
+        return int(self.k_array(t, 1, i).to_host()[0])
+
+    def add_at(self, sums_t, i, value):
+        """sums[i] += value (zk_add_u64 on a one-element view)"""
+        self.ctx.add_u64(self.k_array(sums_t, 1, i), int(value))
+        self.ctx.sync()
+
+    def spectrum_row(self, x, ys):
+        """x, ys[j] = (keys tensor, sums tensor, n, total) -> [dict of the sums] (zk_spectrum_sums_row: one call for the row)"""
+        arr = lambda k, s, n, t: (self.k_array(k, n), self.k_array(s, n), t)                             # noqa: E731
+        return self.ctx.spectrum_sums_row(arr(*x), [arr(*y) for y in ys])
+
     def to_tensors(self, k, c):
         """library arrays -> torch tensors (a copy: the library's buffers are reused by the next step)"""
         kt = self.empty(k.n, torch.int64)
@@ -543,6 +570,124 @@ class Exchange:
         if self.owner == "hash" or self.by_canonical:
             return ops.merge_segments(rk, rc, segs)
         return ops.merge_segments(rk, rc, [(0, total)])
+
+
+# ---------------------------------------------------------------------------------------------------
+# the spectrum measures of `zot dist` over the ranks: the counted exchange
+# ---------------------------------------------------------------------------------------------------
+def seam_verdict(table, rank):
+    """table[r] = (n, first key, first sum, last key) of rank r's local spectrum (position-sharded: rank order = value order;
+    the keys and sums of a rank with n = 0 are not looked at).  A prefix whose k-mers a shard boundary cuts heads the next
+    rank's list too.  -> (drop, add) for `rank`: drop = its first entry repeats the last key of the nearest earlier non-empty
+    rank and goes; add = what the ranks after it dropped of ITS last key, added to its last entry when it is the earliest rank
+    of that chain.  A chain runs on through ranks whose whole list is the one key.  Afterwards the lists of all ranks, in rank
+    order, ascend strictly."""
+    n, first, _, last = table[rank]
+    if n == 0:
+        return False, 0
+    prev = [q for q in range(rank) if table[q][0]]
+    drop = bool(prev) and table[prev[-1]][3] == first
+    if drop and n == 1:
+        return True, 0                      # the whole list was another rank's key: that rank collects
+    add = 0
+    for q in range(rank + 1, len(table)):
+        qn, qfirst, qsum, _ = table[q]
+        if qn == 0:
+            continue
+        if qfirst != last:
+            break
+        add += qsum
+        if qn > 1:
+            break
+    return drop, add
+
+
+class SpectrumDist:
+    """The *.quant / *.ab / jensen.shannon measures of `zot dist` over the ranks.  Every sum they are functions of is additive
+    over a partition of the key space, so: per file, every rank projects and sums its own shard (prepare), the seams between
+    the shards are settled from a table of a few words per rank, and the file's spectrum is cut by the owner function and
+    exchanged ONCE (exchange_all; Exchange.dist_pair cuts and exchanges again for every pair).  Per row of the distance
+    matrix one device call compares the owned piece of file i with those of the files after it (row), and one all-reduce
+    adds the ranks' sums."""
+
+    def __init__(self, ex):
+        self.ex, self.ops, self.comm = ex, ex.ops, ex.comm
+        self.local = []             # per file: (keys tensor, sums tensor, n), seams settled
+        self.totals = []            # per file: the global sum of its counts
+        self.pieces = None          # per file: (keys tensor, sums tensor, n) this rank owns
+
+    def prepare(self, k, c, n, shift):
+        """k / c: this rank's shard of a counted set (first n entries), shift = 2 * (the file's K - <k>).  Collective.
+        Returns the file's index; its global total is self.totals[index] (0: the set holds no k-mers)."""
+        ops, W, rank = self.ops, self.comm.world, self.comm.rank
+        pk, ps, m, total = ops.project_sum(k, c, n, shift)
+        mat = [0] * (4 * W + 1)
+        if m:
+            mat[4 * rank: 4 * rank + 4] = [m, ops.peek(pk, 0), ops.peek(ps, 0), ops.peek(pk, m - 1)]
+        mat[4 * W] = total
+        mat = self.comm.all_reduce(mat)
+        drop, add = seam_verdict([tuple(mat[4 * r: 4 * r + 4]) for r in range(W)], rank)
+        if add:
+            ops.add_at(ps, m - 1, add)
+        if drop:
+            pk, ps, m = pk[1:], ps[1:], m - 1
+        if m == 0:
+            pk, ps = ops.empty(0, torch.int64), ops.empty(0, torch.int64)
+        self.local.append((pk, ps, m))
+        self.totals.append(mat[4 * W])
+        return len(self.local) - 1
+
+    def exchange_all(self, key_bits):
+        """Once, after every file is prepared: cuts balanced over ALL files' lists (range owner), then each file's keys and
+        64-bit sums go to their owners in one exchange.  The owned piece is kept in arrays of its own (Exchange reuses its
+        receive buffers)."""
+        ex, ops = self.ex, self.ops
+        if ex.owner == "range":
+            ex.balanced_cuts([(pk, m) for pk, _, m in self.local], key_bits=key_bits)
+        self.pieces = []
+        for pk, ps, m in self.local:
+            rk, rc, segs = ex.exchange(pk, ps, m)
+            total = sum(s[1] for s in segs)
+            if ex.owner == "hash":              # the ranks' pieces are disjoint but interleaved: one k-way merge
+                mk, mc = ops.merge_segments(rk, rc, segs)
+                kt, st, total = ops.to_tensors(mk, mc)
+            else:                               # rank order is value order, and the seams are settled: already one ascending list
+                kt, st = rk[:max(total, 1)].clone(), rc[:max(total, 1)].clone()
+                ops.after_comm()
+            self.pieces.append((kt, st, total))
+        self.local = []
+        return self.pieces
+
+    def row(self, i):
+        """File i against every file after it -> [dict of the global sums] (the keys of native.Context.spectrum_sums).  One
+        device call, then one all-reduce: the integers as they are (S_xy in four 32-bit limbs, each limb sum below
+        2^32 * world), the two doubles as bit patterns in a world x 2m matrix with this rank's row filled -- the all-reduce
+        of Exchange._exchange_sizes, on every transport -- and added over the ranks by math.fsum: correctly rounded, so the
+        order of the ranks does not matter."""
+        import math
+        import struct
+        W, rank = self.comm.world, self.comm.rank
+        others = list(range(i + 1, len(self.pieces)))
+        m = len(others)
+        if m == 0:
+            return []
+        x = self.pieces[i] + (self.totals[i],)
+        res = self.ops.spectrum_row(x, [self.pieces[j] + (self.totals[j],) for j in others])
+        vec = [0] * (8 * m + 2 * m * W)
+        for p, r in enumerate(res):
+            sxy = r["S_xy"]
+            vec[8 * p: 8 * p + 8] = [r["n_shared"], r["S_min"], r["X_shared"], r["Y_shared"]] + [(sxy >> (32 * l)) & 0xFFFFFFFF for l in range(4)]
+            at = 8 * m + 2 * m * rank + 2 * p
+            vec[at], vec[at + 1] = struct.unpack("<QQ", struct.pack("<dd", r["S_sqrt"], r["S_js"]))
+        vec = self.comm.all_reduce(vec)
+        out = []
+        for p, j in enumerate(others):
+            v = vec[8 * p: 8 * p + 8]
+            fl = [struct.unpack("<dd", struct.pack("<QQ", *vec[8 * m + 2 * m * r + 2 * p: 8 * m + 2 * m * r + 2 * p + 2])) for r in range(W)]
+            out.append(dict(cx=self.totals[i], cy=self.totals[j], n_shared=v[0], S_min=v[1], X_shared=v[2], Y_shared=v[3],
+                            S_xy=sum(v[4 + l] << (32 * l) for l in range(4)),
+                            S_sqrt=math.fsum(f[0] for f in fl), S_js=math.fsum(f[1] for f in fl)))
+        return out
 
 
 def len_of(a):
